@@ -2,12 +2,18 @@
 """Headline benchmark: contrastive pairs/s of one full training step (forward, fused InfoNCE with
 global negatives, backward, gradient all-reduce, fused RAdam) on synthetic data resident in HBM.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
 `python bench.py --gpus N` with no WORLD_SIZE in the environment starts the N ranks itself (N child processes, one
 per GPU, RCCL rendezvous on 127.0.0.1; the parent makes no GPU call and only relays rank 0's JSON line).
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`, ...).  `--full`
+adds everything measured beside the headline: the instrumented roofline step, the shader clock, the per-tower split, the
+per-step communication, the other arithmetic routes, weak scaling, the three-tower workload and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step computed (loss, parameters after the optimiser step, gradients;
+fixed seeded samples of the large tensors) as DIR/<name>.npy, so two builds can be compared output for output.
 
 Workload (BASELINE.json configs[2] towers; SURVEY.md section 8(d) "headline cfg3"): build-defined ViT-S/8
 image encoder on 64x64x3 cutouts + the reference light-curve TransformerWithTimeEmbeddings (T = 200 =
@@ -241,6 +247,59 @@ def cpu_baseline(sample_b, steps, budget_s=12.0):
                       f"single thread: {n_one} steps, {dt_one:.2f} s/step"}
 
 
+DUMP_SAMPLE = 1 << 16          # elements kept of a larger tensor (a fixed, seeded sample)
+DUMP_BUDGET = 64 << 20         # bytes of all dumped arrays together
+
+
+def dump_outputs(path, model, loss):
+    """What the last timed step handed its caller: the loss, every parameter after the optimiser step and its gradient,
+    float32, one DIR/<kind>.<name>.npy each.  A tensor of more than DUMP_SAMPLE elements is reduced to DUMP_SAMPLE of them
+    at sorted indices drawn from a generator seeded by its name, so the same elements are written on every run."""
+    import zlib
+    import numpy as np
+    arrays = {"loss": np.array([loss], dtype=np.float32)}
+    for name, p in model.named_parameters():
+        for kind, t in (("param", p), ("grad", p.grad)):
+            if t is None:
+                continue
+            flat = t.detach().reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+                idx = torch.randperm(flat.numel(), generator=g)[:DUMP_SAMPLE].sort()[0]
+                flat = flat[idx.to(flat.device)]
+            arrays[f"{kind}.{name}"] = flat.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET}-byte budget")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return len(arrays), total
+
+
+def snapshot_state(model, opt):
+    """Copies of the model's parameters and buffers and of the optimiser's state, to be put back by the returned function
+    (in place: graph-captured addresses stay valid).  Not through state_dict(): it hands out copies of the stacked attention
+    weights (transformer_utils.SelfAttention)."""
+    live = list(model.parameters()) + list(model.buffers())
+    steps = {}
+    for p, st in opt.state.items():
+        live += [v for k, v in st.items() if torch.is_tensor(v) and k != "step"]
+        steps[p] = st.get("step")
+    saved = [t.detach().clone() for t in live]
+
+    def restore():
+        with torch.no_grad():
+            for t, s in zip(live, saved):
+                t.detach().copy_(s)
+        for p, s in steps.items():
+            opt.state[p]["step"] = s
+        # a graph-replayed step keeps its step count on the device too (optim.RAdam._step_captured)
+        for group, items, _, _, _, counter in getattr(opt, "_graph_launches", []):
+            counter.fill_(int(items[0][1]["step"]))
+    return restore
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: start N ranks as CHILD processes (fresh interpreters: nothing is
     exec'ed over a process that has touched the GPU, and this parent never touches it -- torch.cuda.device_count() does
@@ -314,7 +373,7 @@ def main():
     ap.add_argument("--serial-towers", action="store_true",
                     help="towers one after the other on one stream (profiling: with a tower per stream rocprofv3's "
                          "per-kernel durations include whatever the other stream ran meanwhile)")
-    ap.add_argument("--gemm-table", action="store_true", help="per-shape GEMM timing of one step on stderr")
+    ap.add_argument("--gemm-table", action="store_true", help="per-shape GEMM timing of one step on stderr (implies --full)")
     ap.add_argument("--gemm-variant", type=int, default=3, choices=[0, 1, 2, 3, 4],
                     help="fp32 GEMM kernel family: 0 register-staged, 1 / 2 / 3 LDS-DMA rings (3 = default)")
     ap.add_argument("--gemm-tail", type=int, default=1, choices=[0, 1, 2],
@@ -331,7 +390,15 @@ def main():
                     help="N > 1, BatchNorm towers (resnet18_cnn1d, convmixer_lc_sp): batch statistics over all ranks")
     ap.add_argument("--cpu-sample-batch", type=int, default=32)
     ap.add_argument("--cpu-steps", type=int, default=0, help="timed oracle steps (0 = fill about 12 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what goes beside the headline (roofline step, shader clock, towers, communication, other "
+                         "arithmetic, weak scaling, three towers, CPU baseline; the --no-* flags drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, parameters and gradients as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    args.full = args.full or args.gemm_table        # the table is read off the instrumented step of --full
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus, sys.argv[1:])
@@ -404,8 +471,10 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    def timed(fn, warmup, steps):
-        """W untimed steps, then EXACTLY `steps` steps between two (barrier + synchronize) fences; max over ranks."""
+    def timed(fn, warmup, steps, state=None):
+        """W untimed steps, then EXACTLY `steps` steps between two (barrier + synchronize) fences; max over ranks.
+        state = (model, optimiser): the untimed steps past the first W + 1, whose number depends on the speed of the
+        build, are undone before the timed ones, so what the last step computes depends on W and `steps` alone."""
         for _ in range(warmup):
             loss = fn()
         fence()
@@ -419,8 +488,12 @@ def main():
         if world > 1:
             torch.distributed.all_reduce(one, op=torch.distributed.ReduceOp.MAX)
         extra = int(min(200, max(0, 0.6 / max(float(one), 1e-4) - warmup - 1)))
+        restore = snapshot_state(*state) if state is not None and extra else None
         for _ in range(extra):
             loss = fn()
+        if restore is not None:
+            restore()
+            del restore
         fence()
         t0 = time.perf_counter()
         for _ in range(steps):
@@ -431,12 +504,15 @@ def main():
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         return float(t), float(loss.detach()), extra + 1
 
-    dt, loss_value, untimed_extra = timed(step, args.warmup, args.steps)
+    dt, loss_value, untimed_extra = timed(step, args.warmup, args.steps, state=(model, opt))
+    if args.dump_outputs and rank == 0:
+        n_dump, dump_bytes = dump_outputs(args.dump_outputs, model, loss_value)
+        print(f"# wrote {n_dump} arrays ({dump_bytes / 1e6:.1f} MB) to {args.dump_outputs}", file=sys.stderr)
 
     # ---- communication of one step: every collective issued through distributed.py, timed on the compute stream ----
     comm = {"backend": "rccl" if D.backend_name() == "nccl" else D.backend_name(), "ranks": world,
             "rccl_ranks": torch.distributed.get_world_size() if world > 1 and D.backend_name() == "nccl" else None}
-    if world > 1 and not args.graphed:
+    if args.full and world > 1 and not args.graphed:
         D.COMM_LOG = []
         step()
         torch.cuda.synchronize()
@@ -452,6 +528,44 @@ def main():
         comm["all_reduce_ms"] = sum(v["ms"] for k, v in per_kind.items() if "all_reduce" in k)
         comm["note"] = ("ms = time the compute stream was held from issue to completion of the collective (HIP events "
                         "on the issuing stream); the gradient all-reduce is issued from autograd hooks under backward")
+
+    def result_line():
+        """The fields of every run: the headline figure of the timed steps and the configuration behind it."""
+        ms = dt / args.steps * 1e3
+        pairs = b * world * args.steps / dt
+        out = {
+            "metric": "contrastive pairs/sec (image+light-curve) at global batch 1024, 1/2/4/8 GPUs",
+            "value": pairs, "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms, "higher_is_better": True, "scaling": scaling,
+            "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": ("ViT-S/8 image tower (64x64x3, build-defined) + reference light-curve "
+                                    "transformer (T=200, emb 64, 8 heads, depth 5, 2 bands) -> enc_dim 128, "
+                                    "symmetric InfoNCE with all-gathered global negatives, RAdam; full train step")
+                       if headline else WORKLOADS[args.workload] + " (non-headline configuration)",
+                       "per_gpu_batch": b, "global_batch": b * world, "parallelism": f"dp{world}",
+                       "launch": "HIP graph replay" if args.graphed else "eager",
+                       "gemm_precision": args.gemm_precision,
+                       "untimed_steps_after_warmup": untimed_extra,
+                       "loss": loss_value, "algorithmic_gflop_per_pair": flops_per_pair() / 1e9,
+                       "executed_gflop_per_pair": flops_per_pair(executed=True) / 1e9,
+                       "model_tflops": pairs * flops_per_pair(executed=True) / 1e12},
+            "comm": comm,
+        }
+        if not headline:
+            for k in ("algorithmic_gflop_per_pair", "executed_gflop_per_pair", "model_tflops"):
+                out["config"].pop(k)
+        return out
+
+    def finish():
+        if world > 1:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result_line()), flush=True)
+        return finish()
 
     # ---- roofline of the dominant kernel (sgemm_kernel: every dense product of both towers) -----------
     # One extra, identical step with HIP events recorded on the launch stream around every msn_sgemm call.
@@ -698,52 +812,31 @@ def main():
             torch.cuda.empty_cache()
 
     if rank == 0:
-        ms = dt / args.steps * 1e3
-        pairs = b * world * args.steps / dt
-        out = {
-            "metric": "contrastive pairs/sec (image+light-curve) at global batch 1024, 1/2/4/8 GPUs",
-            "value": pairs, "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms, "higher_is_better": True, "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": ("ViT-S/8 image tower (64x64x3, build-defined) + reference light-curve "
-                                    "transformer (T=200, emb 64, 8 heads, depth 5, 2 bands) -> enc_dim 128, "
-                                    "symmetric InfoNCE with all-gathered global negatives, RAdam; full train step")
-                       if headline else WORKLOADS[args.workload] + " (non-headline configuration)",
-                       "per_gpu_batch": b, "global_batch": b * world, "parallelism": f"dp{world}",
-                       "launch": "HIP graph replay" if args.graphed else "eager",
-                       "gemm_arithmetic": GEMM_ARITHMETIC[eff_precision] if args.workload != "vit_b16_bf16_lc" else
-                       "image tower: operands rounded to bf16, resident in HBM (BASELINE cfg5 arithmetic); light-curve tower: native fp32 MFMA",
-                       "untimed_steps_after_warmup": untimed_extra,
-                       "loss": loss_value, "algorithmic_gflop_per_pair": flops_per_pair() / 1e9,
-                       "executed_gflop_per_pair": flops_per_pair(executed=True) / 1e9,
-                       "model_tflops": pairs * flops_per_pair(executed=True) / 1e12},
-            "roofline": {"bound": "mfma", "kernel": kernel_name,
-                         "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-                         "traffic": traffic, "traffic_unit": "bytes per launch (mean), 2 x FETCH_SIZE + WRITE_SIZE",
-                         "traffic_source": traffic_source,
-                         "launches_per_step": len(prof), "ms_per_step_in_kernel": gemm_ms,
-                         "algorithmic_gflop_per_step": gemm_flops / 1e9,
-                         "algorithmic_bytes_per_launch": gemm_bytes_fp32 / max(len(prof), 1),
-                         "algorithmic_bytes_is": "operands + result (+ the aux matrix an epilogue reads or writes) of the launches at 4 bytes per element",
-                         "traffic_over_algorithmic": (traffic / (gemm_bytes_fp32 / max(len(prof), 1))) if traffic else None,
-                         **({"algorithmic_bytes_per_launch_plane_format": gemm_bytes / max(len(prof), 1),
-                             "traffic_over_plane_format_bytes": (traffic / (gemm_bytes / max(len(prof), 1))) if traffic else None}
-                            if products else {}),
-                         "shader_clock_ghz": shader_clock_ghz,
-                         "shader_clock_is": "d s_memtime / d s_memrealtime x 100 MHz of a one-wave probe on a side stream beside one training step (nominal 2.4)",
-                         **({"mfma_products_per_multiply_add": products, "algorithmic_tflops": algorithmic_tflops,
-                             "note": "achieved / peak count EXECUTED bf16 MFMA flops (products x algorithmic); "
-                                     "algorithmic_tflops is the fp32-equivalent rate of the same launches; algorithmic_bytes_per_launch_plane_format "
-                                     "counts plane operands / plane results at their HBM format (2 bytes x planes per element), fp32 matrices at 4"} if products else {}),
-                         **({"fp32_launches": fp32_side} if fp32_side is not None else {}),
-                         **({"attention": attention} if attention is not None else {}),
-                         **({"fused_feed_forward": fused_ff} if fused_ff is not None else {})},
-            "comm": comm,
-        }
-        if not headline:
-            for k in ("algorithmic_gflop_per_pair", "executed_gflop_per_pair", "model_tflops"):
-                out["config"].pop(k)
+        out = result_line()
+        ms = out["ms_per_step"]
+        out["config"]["gemm_arithmetic"] = (GEMM_ARITHMETIC[eff_precision] if args.workload != "vit_b16_bf16_lc" else
+                                            "image tower: operands rounded to bf16, resident in HBM (BASELINE cfg5 arithmetic); light-curve tower: native fp32 MFMA")
+        out["roofline"] = {"bound": "mfma", "kernel": kernel_name,
+                           "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+                           "traffic": traffic, "traffic_unit": "bytes per launch (mean), 2 x FETCH_SIZE + WRITE_SIZE",
+                           "traffic_source": traffic_source,
+                           "launches_per_step": len(prof), "ms_per_step_in_kernel": gemm_ms,
+                           "algorithmic_gflop_per_step": gemm_flops / 1e9,
+                           "algorithmic_bytes_per_launch": gemm_bytes_fp32 / max(len(prof), 1),
+                           "algorithmic_bytes_is": "operands + result (+ the aux matrix an epilogue reads or writes) of the launches at 4 bytes per element",
+                           "traffic_over_algorithmic": (traffic / (gemm_bytes_fp32 / max(len(prof), 1))) if traffic else None,
+                           **({"algorithmic_bytes_per_launch_plane_format": gemm_bytes / max(len(prof), 1),
+                               "traffic_over_plane_format_bytes": (traffic / (gemm_bytes / max(len(prof), 1))) if traffic else None}
+                              if products else {}),
+                           "shader_clock_ghz": shader_clock_ghz,
+                           "shader_clock_is": "d s_memtime / d s_memrealtime x 100 MHz of a one-wave probe on a side stream beside one training step (nominal 2.4)",
+                           **({"mfma_products_per_multiply_add": products, "algorithmic_tflops": algorithmic_tflops,
+                               "note": "achieved / peak count EXECUTED bf16 MFMA flops (products x algorithmic); "
+                                       "algorithmic_tflops is the fp32-equivalent rate of the same launches; algorithmic_bytes_per_launch_plane_format "
+                                       "counts plane operands / plane results at their HBM format (2 bytes x planes per element), fp32 matrices at 4"} if products else {}),
+                           **({"fp32_launches": fp32_side} if fp32_side is not None else {}),
+                           **({"attention": attention} if attention is not None else {}),
+                           **({"fused_feed_forward": fused_ff} if fused_ff is not None else {})}
         if weak is not None:
             out["weak_scaling_256_per_gpu"] = weak
         if three is not None:
@@ -759,9 +852,7 @@ def main():
         elif world == 1:
             out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
-    if world > 1:
-        torch.distributed.barrier()
-        torch.distributed.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -109,3 +109,35 @@ def test_full_batch_plane_path_matches_fp32_path():
     assert abs(l1 - l0) <= 1e-5 * abs(l0), (l0, l1)
     worst = max((float((g1[k] - g0[k]).abs().max()) / (float(g0[k].abs().max()) + 1e-12), k) for k in g0 if k != "logit_bias")
     assert worst[0] < 1e-3, worst
+
+
+def test_plain_bench_run_and_its_dumped_outputs(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: one result line with the headline fields and none of
+    what --full measures beside them; the last timed step's loss, parameters and gradients as float32 arrays within 64 MB, and
+    the same arrays from a second run (the untimed steps that the warm-up adds by speed are undone before the timed ones)."""
+    import json
+    import subprocess
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--global-batch", "64", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["unit"] == "pairs/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+        assert abs(out["value"] - 64 / (out["ms_per_step"] * 1e-3)) <= 1e-6 * out["value"]
+        assert not {"roofline", "cpu_baseline", "alt_arithmetic", "weak_scaling_256_per_gpu", "three_tower", "towers"} & set(out)
+        files = sorted(os.listdir(d))
+        assert "loss.npy" in files and "param.logit_scale.npy" in files and "grad.logit_scale.npy" in files
+        arrays = {f: np.load(d / f) for f in files}
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert float(arrays["loss.npy"][0]) == pytest.approx(out["config"]["loss"], rel=1e-6)
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f, a in dumps[0].items():
+        np.testing.assert_allclose(dumps[1][f], a, rtol=1e-4, atol=1e-5 * float(np.abs(a).max()) + 1e-12, err_msg=f)

@@ -24,7 +24,7 @@ RUNS = [("vit_s8_lc", 1024, "BASELINE cfg3 towers = the headline"), ("vit_s8_lc"
 
 def bench(workload, rows):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--per-gpu-batch", str(rows), "--steps", "10",
-           "--no-cpu-baseline", "--no-alt", "--no-weak", "--no-three-tower"]
+           "--full", "--no-cpu-baseline", "--no-alt", "--no-weak", "--no-three-tower"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if r.returncode != 0 or not lines:
