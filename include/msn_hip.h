@@ -440,7 +440,11 @@ int msn_layernorm_bwd_bf16(const float* dy, int64_t lddy, const float* x, int64_
  * the 1-query nn.MultiheadAttention pooling (:240-246) and the build-defined ViT blocks.
  * q: (B, Tq, H*hd) rows `ldq` apart, batches `q_bstride` apart (0 = one query shared by the batch);
  * k, v: (B, Tk, H*hd); head h lives in columns h*hd .. h*hd+hd-1 (so a packed q|k|v buffer works by
- * pointer offset + ld = 3*H*hd).  key_mask: (B, Tk) bytes or NULL.  hd <= 128.
+ * pointer offset + ld = 3*H*hd).  key_mask: (B, Tk) bytes or NULL.  hd <= 512: up to 32 any width,
+ * above 32 a multiple of 4 on 16-byte aligned rows (MSN_ERR_SHAPE otherwise; ops pads such heads with
+ * zero columns); 132 .. 512 run on their own kernels (attention_wide.hip: the head dimension split over
+ * the waves of a workgroup, keys / queries streamed through LDS in 16-row chunks), under every
+ * msn_set_attention_path mode; hd > 512 is MSN_ERR_SHAPE.
  * lse: (B, H, Tq, 2) = (row max, log of the exp-sum), kept apart because a fully padded sample has
  * max = -1e7 where fp32 cannot hold the sum.  bwd recomputes the probabilities from lse; `delta` is
  * (B, H, Tq) scratch.

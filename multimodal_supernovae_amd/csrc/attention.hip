@@ -477,7 +477,7 @@ static int rows_per_lane(int S, int t, int64_t pairs) {
 
 static int check_attn(const char* who, int B, int H, int Tq, int Tk, int s) {
     MSN_REQUIRE(B > 0 && H > 0 && Tq > 0 && Tk > 0 && s > 0, "%s: empty input", who);
-    MSN_REQUIRE(s <= 128, "%s: head width %d > 128 unsupported", who, s);
+    MSN_REQUIRE(s <= kWideMaxHead, "%s: head width %d > %d unsupported", who, s, kWideMaxHead);
     MSN_REQUIRE(B <= 65535 && H <= 65535, "%s: batch / heads exceed the grid limits", who);
     return MSN_OK;
 }
@@ -498,6 +498,16 @@ extern "C" int msn_attention_fwd(const float* q, int64_t ldq, int64_t q_bstride,
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
     a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.s = head_dim; a.scale = scale;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (head_dim > 128) {                                  // 132 - 512 wide: attention_wide.hip under every path mode, shared query included
+        MAttn m = {};
+        m.q = q; m.k = k; m.v = v; m.out = out; m.mask = key_mask; m.lse = lse;
+        m.ldq = ldq; m.ldk = ldk; m.ldv = ldv; m.ldo = ldo;
+        m.q_bs = q_bstride; m.k_bs = k_bstride; m.v_bs = v_bstride; m.o_bs = o_bstride;
+        m.B = B; m.H = H; m.Tq = Tq; m.Tk = Tk; m.hd = head_dim; m.scale = scale;
+        MSN_REQUIRE(wattn_applicable(m), "msn_attention_fwd: a head width above 32 (%d) must be a multiple of 4 with 16-byte aligned "
+                    "rows (pad the heads with zero columns)", head_dim);
+        return wattn_forward(m, st);
+    }
     if (g_attn_path != 1) {
         MAttn m = {};
         m.q = q; m.k = k; m.v = v; m.out = out; m.mask = key_mask; m.lse = lse;
@@ -551,6 +561,18 @@ extern "C" int msn_attention_bwd(const float* q, int64_t ldq, int64_t q_bstride,
     a.dq = dq; a.dk = dk; a.dv = dv; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
     a.dq_bstride = dq_bstride; a.dk_bstride = dk_bstride; a.dv_bstride = dv_bstride;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (head_dim > 128) {                                  // 132 - 512 wide: attention_wide.hip under every path mode, shared query included
+        MAttn m = {};
+        m.q = q; m.k = k; m.v = v; m.o = out; m.dout = dout; m.dq = dq; m.dk = dk; m.dv = dv;
+        m.mask = key_mask; m.lse = const_cast<float*>(lse); m.delta = delta;
+        m.ldq = ldq; m.ldk = ldk; m.ldv = ldv; m.ldo = ldo; m.ldd = ldd; m.lddq = lddq; m.lddk = lddk; m.lddv = lddv;
+        m.q_bs = q_bstride; m.k_bs = k_bstride; m.v_bs = v_bstride; m.o_bs = o_bstride; m.d_bs = d_bstride;
+        m.dq_bs = dq_bstride; m.dk_bs = dk_bstride; m.dv_bs = dv_bstride;
+        m.B = B; m.H = H; m.Tq = Tq; m.Tk = Tk; m.hd = head_dim; m.scale = scale;
+        MSN_REQUIRE(wattn_applicable(m), "msn_attention_bwd: a head width above 32 (%d) must be a multiple of 4 with 16-byte aligned "
+                    "rows (pad the heads with zero columns)", head_dim);
+        return wattn_backward(m, st);
+    }
     if (g_attn_path != 1) {
         MAttn m = {};
         m.q = q; m.k = k; m.v = v; m.o = out; m.dout = dout; m.dq = dq; m.dk = dk; m.dv = dv;

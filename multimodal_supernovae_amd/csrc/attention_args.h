@@ -27,6 +27,12 @@ bool mattn_applicable(const MAttn& a, bool shared_q = false);
 int mattn_forward(const MAttn& a, hipStream_t st);
 int mattn_backward(const MAttn& a, hipStream_t st);
 
+// attention_wide.hip: heads 132 - 512 wide (multiples of 4), any sequence length, shared query included (q_bs == 0)
+constexpr int kWideMaxHead = 512;
+bool wattn_applicable(const MAttn& a);
+int wattn_forward(const MAttn& a, hipStream_t st);
+int wattn_backward(const MAttn& a, hipStream_t st);
+
 // attention_planes.hip: heads up to 16 wide, any sequence length
 bool pattn_applicable(const MAttn& a);
 int pattn_forward(const MAttn& a, hipStream_t st);
