@@ -173,8 +173,10 @@ int msn_colsum(const float* X, int64_t ldx, int64_t M, int64_t N, float* out, vo
  *        and the upstream gradient `grad_out` (device scalar).  Writes dE1_loc, dE2_loc (the
  *        complete gradient of the global loss w.r.t. the local rows -- no reduce-scatter) and
  *        dscale_dbias[2] = this rank's share of d/dlog_scale and d/dbias (sum over ranks).
- * log_scale, bias, grad_out are DEVICE scalars (no host synchronisation).  Any 1 <= D <= 256 (the reference takes
- * any enc_dim, src/models_multimodal.py:101): tiles are 8/16/32/64/128/256 columns wide, zero beyond column D.
+ * log_scale, bias, grad_out are DEVICE scalars (no host synchronisation).  Embedding width (the reference takes any
+ * enc_dim, src/models_multimodal.py:101): any 1 <= D <= 256 (tiles 8/16/32/64/128/256 columns wide, zero beyond column D),
+ * and 256 < D <= 1024 with D a multiple of 32 (the waves of a workgroup split D); other widths are refused.  Rows of any
+ * stride >= D, 4-byte aligned.
  */
 size_t msn_infonce_workspace_bytes(int b1, int b2, int n1, int n2, int D);
 int msn_infonce_fwd(const float* E1_loc, int64_t ld1, int b1, const float* E2_loc, int64_t ld2, int b2,
@@ -191,7 +193,7 @@ int msn_infonce_bwd(const float* E1_loc, int64_t ld1, int b1, const float* E2_lo
 /* SigLIP-style loss with the reference's sign convention -- sigmoid_loss, src/loss.py:68-83:
  *   Z = -(E2 . E1^T) exp(log_scale) + bias (fp32);  loss = mean_ij softplus(z_ij Z_ij) evaluated in fp64,
  *   z = +1 on the diagonal, -1 elsewhere (mean over all n x n entries).  Same row-sharded calling
- *   convention and workspace as msn_infonce_*; both modalities have b local / n global rows.
+ *   convention, embedding widths and workspace as msn_infonce_*; both modalities have b local / n global rows.
  *   fwd writes this rank's share of the loss; bwd writes dE1_loc, dE2_loc and (dlog_scale, dbias) shares. */
 int msn_sigmoid_loss_fwd(const float* E1_loc, int64_t ld1, const float* E2_loc, int64_t ld2, int b,
                          const float* E1_all, int64_t ld1a, const float* E2_all, int64_t ld2a, int n, int D,
@@ -205,7 +207,8 @@ int msn_sigmoid_loss_bwd(const float* E1_loc, int64_t ld1, const float* E2_loc, 
 
 /* Retrieval rank for the validation "AUC" -- get_ROC_data, src/utils.py:380-411: for unit-norm rows,
  * rank[i] = #{ j != i : <E2_i, E1_j> > <E2_i, E1_i> } (position of the true partner in row i's similarity
- * ranking; the reference sorts every row in a host loop).  workspace: msn_infonce_workspace_bytes(n,n,n,n,D). */
+ * ranking; the reference sorts every row in a host loop).  Widths as msn_infonce_*: 1 <= D <= 256, or 256 < D <= 1024
+ * with D a multiple of 32.  workspace: msn_infonce_workspace_bytes(n,n,n,n,D). */
 int msn_retrieval_rank(const float* E1, int64_t ld1, const float* E2, int64_t ld2, int n, int D, int* rank,
                        void* ws, size_t ws_bytes, msn_stream_t stream);
 

@@ -27,112 +27,14 @@
 //
 // Any embedding width 1 <= D <= 256 (the reference takes any enc_dim, src/models_multimodal.py:101): the tiles are
 // DP = 8 / 16 / 32 / 64 / 128 / 256 columns wide and columns D .. DP-1 are zero in LDS and in the Q fragments -- zero
-// columns change no inner product.
+// columns change no inner product.  Widths 256 < D <= 1024 that are multiples of 32 go to infonce_wide.hip (the waves of a
+// workgroup split D there); the finish kernels below serve both.
 #include <algorithm>
 #include <math.h>
 
-#include "msn_common.h"
+#include "infonce_args.h"
 
 namespace msn {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int QT = 32;        // queries per workgroup
-constexpr int KT = 32;        // keys per tile
-constexpr int NW = 4;         // waves per workgroup, each sweeping its own key tiles
-constexpr int MODE_SOFTMAX = 0, MODE_SIGMOID = 1;
-
-struct Side {
-    const float* Q;      // local rows (queries), [nq][ldq]
-    const float* K;      // all rows of the other modality (keys), [nk][ldk]
-    const float* lse_q;  // bwd: LSE of the queries' own direction, indexed by GLOBAL row id
-    const float* lse_k;  // bwd: LSE of the keys' direction, indexed by global row id
-    float* dQ;           // bwd: [nq][ldd]
-    int64_t ldq, ldk, ldd;
-    int nq, nk;
-};
-
-struct NceArgs {
-    Side side[2];
-    const float* log_scale;  // device scalar (log of the logit scale)
-    const float* bias;       // device scalar
-    const float* grad_out;   // bwd: device scalar
-    int q_offset;            // global row id of local row 0
-    int n_diag;              // n = min(N1, N2)
-    int D;                   // real embedding width (<= the kernel's DP)
-    int ksplit, keys_per_split;
-    float* part_m;           // fwd scratch [2][ksplit][maxq]: running max, sum, positive score of a key split
-    float* part_l;
-    float* part_d;
-    float* slab;             // bwd scratch [2][ksplit][maxq][D] (ksplit > 1 only)
-    double* scal;            // bwd scratch [qtiles * ksplit][2] : partial dscale, dbias; fwd sigmoid partial loss
-    int maxq;
-    int mode;
-};
-
-__device__ __forceinline__ int row_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// A wave re-uses its LDS key buffer: LDS operations of one wave execute in order, this only pins the compiler.
-__device__ __forceinline__ void wave_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ float4 load4_guarded(const float* p, int c0, int D, bool vec_ok) {
-    if (vec_ok && c0 + 3 < D) return *reinterpret_cast<const float4*>(p);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c0 < D) v.x = p[0];
-    if (c0 + 1 < D) v.y = p[1];
-    if (c0 + 2 < D) v.z = p[2];
-    if (c0 + 3 < D) v.w = p[3];
-    return v;
-}
-
-// One wave stages one 32-key tile (rows k0..k0+31 of K, zero beyond k_end and beyond column D) into ITS LDS buffer,
-// row stride DP + 4.
-template <int DP>
-__device__ __forceinline__ void stage_keys(float* Ks, const float* __restrict__ K, int64_t ldk, int k0, int k_end, int D,
-                                           bool vec_ok, int lane) {
-    constexpr int KS = DP + 4;
-    constexpr int PER_ROW = DP / 4;
-#pragma unroll
-    for (int j = 0; j < KT * PER_ROW / 64; ++j) {
-        const int idx = lane + 64 * j;
-        const int r = idx / PER_ROW, q = idx % PER_ROW;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (k0 + r < k_end) v = load4_guarded(K + (int64_t)(k0 + r) * ldk + 4 * q, 4 * q, D, vec_ok);
-        *reinterpret_cast<float4*>(Ks + r * KS + 4 * q) = v;
-    }
-}
-
-template <int DP>
-__device__ __forceinline__ void load_q_frags(float4 (&qf)[DP / 8], const float* __restrict__ Q, int64_t ldq,
-                                             int qrow, int h, int D, bool vec_ok) {
-    const float* p = Q + (int64_t)qrow * ldq + 4 * h;
-#pragma unroll
-    for (int ko = 0; ko < DP / 8; ++ko) qf[ko] = load4_guarded(p + 8 * ko, 8 * ko + 4 * h, D, vec_ok);
-}
-
-// acc[key][query] = sum_d K[key][d] * Q[query][d] for the staged tile; lane col = query (lane & 31).
-template <int DP>
-__device__ __forceinline__ f32x16 score_tile(const float* Ks, const float4 (&qf)[DP / 8], int l32, int h) {
-    constexpr int KS = DP + 4;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int ko = 0; ko < DP / 8; ++ko) {
-        const float4 kf = *reinterpret_cast<const float4*>(Ks + l32 * KS + 8 * ko + 4 * h);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qf[ko].x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qf[ko].y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qf[ko].z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qf[ko].w, acc, 0, 0, 0);
-    }
-    return acc;
-}
-
-constexpr int cmax(int a, int b) { return a > b ? a : b; }
 
 // ------------------------------------------------------------------------------------------ forward
 template <int DP>
@@ -545,36 +447,9 @@ __global__ void nce_rank_finish_kernel(const int* __restrict__ part_cnt, int ksp
     rank[i] = s;
 }
 
-struct Plan {
-    int ksplit, keys_per_split, maxq, qtiles;
-    size_t off_m, off_l, off_d, off_slab, off_scal, total;
-};
-
-// Enough workgroups to fill the chip's 512 slots (two directions x query tiles x key splits); a key split is a whole
-// number of 4-tile rounds so that the four waves of a workgroup carry equal shares.
-static Plan make_plan(int b1, int b2, int n1, int n2, int D) {
-    Plan pl;
-    pl.maxq = std::max(b1, b2);
-    const int maxk = std::max(n1, n2);
-    pl.qtiles = (int)cdiv(pl.maxq, QT);
-    int ks = std::max(1, 512 / (2 * pl.qtiles));
-    ks = std::min(ks, (int)cdiv(maxk, KT * NW));
-    ks = std::max(std::min(ks, 64), 1);
-    pl.keys_per_split = (int)(cdiv(cdiv(maxk, ks), KT * NW) * KT * NW);
-    pl.ksplit = (int)cdiv(maxk, pl.keys_per_split);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
-    pl.off_m = take(sizeof(float) * 2 * pl.ksplit * (size_t)pl.maxq);
-    pl.off_l = take(sizeof(float) * 2 * pl.ksplit * (size_t)pl.maxq);
-    pl.off_d = take(sizeof(float) * 2 * pl.ksplit * (size_t)pl.maxq);
-    pl.off_slab = take(sizeof(float) * 2 * pl.ksplit * (size_t)pl.maxq * D);
-    pl.off_scal = take(sizeof(double) * 2 * (size_t)pl.ksplit * pl.qtiles);
-    pl.total = o;
-    return pl;
-}
-
 static int check_common(const char* who, int b1, int b2, int n1, int n2, int D, int q_offset) {
-    MSN_REQUIRE(D >= 1 && D <= 256, "%s: embedding width D=%d unsupported (1 <= D <= 256)", who, D);
+    MSN_REQUIRE(D >= 1 && (D <= kNceNarrowMaxD || (D <= kNceWideMaxD && D % kNceWideGranule == 0)),
+                "%s: embedding width D=%d unsupported (1 <= D <= 256, or 256 < D <= 1024 with D a multiple of 32)", who, D);
     MSN_REQUIRE(b1 > 0 && b2 > 0 && n1 >= b1 && n2 >= b2 && q_offset >= 0, "%s: bad row counts b1=%d b2=%d N1=%d N2=%d",
                 who, b1, b2, n1, n2);
     return MSN_OK;
@@ -642,8 +517,12 @@ static int infonce_fwd_impl(int mode, const float* E1_loc, int64_t ld1, int b1, 
     hipStream_t st = static_cast<hipStream_t>(stream);
     // the sigmoid loss sums each (i, j) once: direction 0 only
     const dim3 grid(pl.qtiles, pl.ksplit, mode == MODE_SIGMOID ? 1 : 2), block(256);
-    MSN_NCE_DISPATCH(nce_fwd_kernel, grid, block, 0, st, a)
-    MSN_LAUNCH_CHECK();
+    if (D > kNceNarrowMaxD) {
+        if (int rc = nce_wide_fwd(a, grid, st)) return rc;
+    } else {
+        MSN_NCE_DISPATCH(nce_fwd_kernel, grid, block, 0, st, a)
+        MSN_LAUNCH_CHECK();
+    }
     hipLaunchKernelGGL(nce_fwd_finish_kernel, dim3(1), dim3(1024), 0, st, a, lse_row, lse_col, loss,
                        pl.qtiles * pl.ksplit);
     MSN_LAUNCH_CHECK();
@@ -703,8 +582,12 @@ static int infonce_bwd_impl(int mode, const float* E1_loc, int64_t ld1, int b1, 
     a.scal = reinterpret_cast<double*>(w + pl.off_scal);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(pl.qtiles, pl.ksplit, 2), block(256);
-    MSN_NCE_DISPATCH(nce_bwd_kernel, grid, block, 0, st, a)
-    MSN_LAUNCH_CHECK();
+    if (D > kNceNarrowMaxD) {
+        if (int rc = nce_wide_bwd(a, grid, st)) return rc;
+    } else {
+        MSN_NCE_DISPATCH(nce_bwd_kernel, grid, block, 0, st, a)
+        MSN_LAUNCH_CHECK();
+    }
     // key splits > 1: fixed-order sum of the slabs; always: the (dscale, dbias) partials of direction 0
     const int64_t total = (int64_t)pl.maxq * D;
     const int blocks = pl.ksplit > 1 ? (int)std::min<int64_t>(cdiv(total, 256), 1024) : 1;
@@ -727,8 +610,12 @@ extern "C" int msn_retrieval_rank(const float* E1, int64_t ld1, const float* E2,
     int* part = reinterpret_cast<int*>(static_cast<char*>(ws) + pl.off_m);   // [ksplit][maxq] ints fit the (m) slab
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(pl.qtiles, pl.ksplit, 1), block(256);
-    MSN_NCE_DISPATCH(nce_rank_kernel, grid, block, 0, st, a, part)
-    MSN_LAUNCH_CHECK();
+    if (D > kNceNarrowMaxD) {
+        if (int rc = nce_wide_rank(a, grid, part, st)) return rc;
+    } else {
+        MSN_NCE_DISPATCH(nce_rank_kernel, grid, block, 0, st, a, part)
+        MSN_LAUNCH_CHECK();
+    }
     hipLaunchKernelGGL(nce_rank_finish_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, part, pl.ksplit, pl.maxq, n, rank);
     MSN_LAUNCH_CHECK();
     return MSN_OK;
