@@ -589,6 +589,22 @@ int msn_radam_step(const void* table, int n_tensors, int64_t max_numel, float lr
 int msn_radam_step_dev(const void* table, int n_tensors, int64_t max_numel, float* hyper, long long* step_counter,
                        msn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Gradient clipping: torch.nn.utils.clip_grad_norm_ / clip_grad_value_ as pl.Trainer(gradient_clip_val=...,
+ * gradient_clip_algorithm="norm" | "value") calls them after the gradient all-reduce and before optimizer.step().
+ * table: DEVICE array of n_tensors (1 .. 65535) records of two 64-bit words {g*, numel} (fp32 gradients, in place);
+ * max_numel >= every numel of the table.  One launch per pass for the whole model.
+ *   msn_grad_norm: total_norm[0] = ||g||_p over all tensors (norm_type 1, 2 or INFINITY; NaN propagates) and
+ *     coef[0] = min(max_norm / (total_norm + 1e-6), 1) (a NaN stays NaN), both DEVICE floats.  Per-block partials in fp64
+ *     go to `ws` (msn_grad_norm_workspace_bytes) and one block sums them in a fixed order: bitwise reproducible.
+ *   msn_grad_scale: g *= coef[0] (the device-resident coefficient of msn_grad_norm).
+ *   msn_grad_clamp: g = clamp(g, -clip_value, clip_value), NaN kept. */
+size_t msn_grad_norm_workspace_bytes(int n_tensors, int64_t max_numel);
+int msn_grad_norm(const void* table, int n_tensors, int64_t max_numel, float norm_type, float max_norm, float* total_norm,
+                  float* coef, void* ws, size_t ws_bytes, msn_stream_t stream);
+int msn_grad_scale(const void* table, int n_tensors, int64_t max_numel, const float* coef, msn_stream_t stream);
+int msn_grad_clamp(const void* table, int n_tensors, int64_t max_numel, float clip_value, msn_stream_t stream);
+
 /* Channels-last convolution plumbing for the build-defined ResNet-18 / 1-D CNN encoders (not in the
  * reference): cols[(b,oh,ow)][(c,u,v)] = x[b, oh*sh+u-ph, ow*sw+v-pw, c] (0 outside), column order equal to
  * the flattening of a (C_out, C_in, kh, kw) weight, so conv = msn_sgemm(cols, W) ; col2im is its adjoint

@@ -4,7 +4,13 @@ The reference builds `torch.optim.RAdam(self.parameters(), lr=..., **optimizer_k
 configure_optimizers (src/models_multimodal.py:306-310) with torch defaults; this class keeps the
 constructor, `param_groups`, `state` keys (`step`, `exp_avg`, `exp_avg_sq`), `zero_grad` and
 `step`, so optimiser states of reference checkpoints map one to one.
+
+clip_grad_norm_ / clip_grad_value_ restate torch.nn.utils' functions of the same names on the GPU (multi-tensor HIP
+launches, csrc/grad_clip.hip): the gradient clipping pl.Trainer(gradient_clip_val=...) applies before the step.
 """
+import ctypes
+import math
+
 import torch
 
 from . import _lib
@@ -187,3 +193,115 @@ class RAdam(torch.optim.Optimizer):
                 check(lib().msn_radam_step(ptr(table), len(items), max_n, group["lr"], b1, b2, group["eps"],
                                            group["weight_decay"], step, stream_ptr()), "msn_radam_step")
         return loss
+
+
+# ---- gradient clipping (torch.nn.utils.clip_grad_norm_ / clip_grad_value_, as pl.Trainer(gradient_clip_val=...) calls them) --
+# One multi-tensor launch per pass through a device table {g*, numel} per gradient (csrc/grad_clip.hip).  Eager calls stage
+# the table in pinned host memory (two buffers used alternately, as RAdam._staging); under stream capture the table comes
+# from a pinned buffer reserved BEFORE the capture (clip_graph_prepare), is filled at capture time and copied by a copy
+# node of the graph, and the clip coefficient stays on the device -- nothing is written by the host between replays.
+_CLIP_STAGING = [[None, None], [None, None]]
+_CLIP_SLOT = [0]
+_CLIP_RESERVED = []          # pinned tables reserved for captures to come
+_CLIP_CAPTURED = []          # pinned tables read by copy nodes of recorded graphs: kept alive with the process
+
+
+def clip_graph_prepare(parameters):
+    """Call BEFORE a stream capture that will clip the gradients of `parameters` (eager): reserves the pinned descriptor
+    table that the capture fills and its graph copies at every replay.  One reservation per clip call recorded."""
+    params = [parameters] if torch.is_tensor(parameters) else list(parameters)
+    _CLIP_RESERVED.append(torch.empty(max(2 * len(params), 2), dtype=torch.int64).pin_memory())
+
+
+def _clip_grads(parameters, what):
+    params = [parameters] if torch.is_tensor(parameters) else list(parameters)
+    grads = [p.grad for p in params if p.grad is not None]
+    for g in grads:
+        if g.device.type != "cuda":
+            _lib.require_gpu()
+            raise _lib.MsnHipError(f"{what}: gradients must live on the GPU (there is no CPU path)")
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            raise _lib.MsnHipError(f"{what}: contiguous float32 gradients only (got {g.dtype}, "
+                                   f"contiguous={g.is_contiguous()})")
+    if grads and len({g.device for g in grads}) != 1:
+        raise _lib.MsnHipError(f"{what}: all gradients must live on one GPU")
+    return grads
+
+
+def _clip_table(grads):
+    """(device table, max_numel) of the gradients; the host buffer it is copied from is never rewritten while a copy that
+    reads it may still be pending."""
+    words = []
+    for g in grads:
+        words += [g.data_ptr(), g.numel()]
+    max_n = max(g.numel() for g in grads)
+    dev = grads[0].device
+    if torch.cuda.is_current_stream_capturing():
+        fit = [i for i, t in enumerate(_CLIP_RESERVED) if t.numel() >= len(words)]
+        if not fit:
+            raise _lib.MsnHipError("gradient clipping under stream capture needs optim.clip_graph_prepare(parameters) "
+                                   "before the capture begins (the descriptor table must be pinned in advance)")
+        host = _CLIP_RESERVED.pop(fit[0])
+        _CLIP_CAPTURED.append(host)
+        host[:len(words)].copy_(torch.tensor(words, dtype=torch.int64))
+        return host[:len(words)].to(dev, non_blocking=True), max_n        # a copy node of the graph (static content)
+    _CLIP_SLOT[0] ^= 1
+    slot = _CLIP_STAGING[_CLIP_SLOT[0]]
+    if slot[1] is not None:
+        slot[1].synchronize()
+    if slot[0] is None or slot[0].numel() < len(words):
+        slot[0] = torch.empty(max(len(words), 1024), dtype=torch.int64).pin_memory()
+    slot[0][:len(words)] = torch.tensor(words, dtype=torch.int64)
+    table = slot[0][:len(words)].to(dev, non_blocking=True)
+    slot[1] = torch.cuda.Event()
+    slot[1].record()
+    return table, max_n
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """torch.nn.utils.clip_grad_norm_: scales every gradient in place by clamp(max_norm / (total_norm + 1e-6), max=1) and
+    returns the total norm before clipping as a 0-dim float32 device tensor (no host synchronisation unless
+    `error_if_nonfinite`).  norm_type 1, 2 or inf; `foreach` is accepted for torch's signature (always one multi-tensor
+    launch per pass)."""
+    norm_type = float(norm_type)
+    if norm_type not in (1.0, 2.0, float("inf")):
+        raise ValueError(f"clip_grad_norm_: norm_type must be one of 1, 2, inf (got {norm_type})")
+    max_norm = float(max_norm)
+    if not max_norm >= 0.0:
+        raise ValueError(f"clip_grad_norm_: max_norm must be non-negative (got {max_norm})")
+    capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+    if error_if_nonfinite and capturing:
+        raise _lib.MsnHipError("clip_grad_norm_(error_if_nonfinite=True) reads the norm on the host and cannot be recorded "
+                               "in a stream capture")
+    grads = _clip_grads(parameters, "clip_grad_norm_")
+    if not grads:
+        return torch.tensor(0.0)
+    table, max_n = _clip_table(grads)
+    dev = grads[0].device
+    out = torch.empty(2, dtype=torch.float32, device=dev)              # {total norm, clip coefficient}
+    ws = torch.empty(int(lib().msn_grad_norm_workspace_bytes(len(grads), max_n)), dtype=torch.uint8, device=dev)
+    check(lib().msn_grad_norm(ptr(table), len(grads), max_n, norm_type, max_norm, ptr(out), ctypes.c_void_p(out.data_ptr() + 4),
+                              ptr(ws), ws.numel(), stream_ptr()), "msn_grad_norm")
+    total = out[0]
+    if error_if_nonfinite and not math.isfinite(float(total)):
+        raise RuntimeError(f"The total norm of order {norm_type} for gradients from `parameters` is non-finite, so it cannot "
+                           "be clipped. To disable this error and scale the gradients by the non-finite norm anyway, set "
+                           "`error_if_nonfinite=False`")
+    check(lib().msn_grad_scale(ptr(table), len(grads), max_n, ctypes.c_void_p(out.data_ptr() + 4), stream_ptr()),
+          "msn_grad_scale")
+    return total
+
+
+@torch.no_grad()
+def clip_grad_value_(parameters, clip_value, foreach=None):
+    """torch.nn.utils.clip_grad_value_: every gradient clamped in place to [-clip_value, clip_value] (NaN kept)."""
+    clip_value = float(clip_value)
+    if not clip_value >= 0.0:
+        raise ValueError(f"clip_grad_value_: clip_value must be non-negative (got {clip_value})")
+    grads = _clip_grads(parameters, "clip_grad_value_")
+    if not grads:
+        return None
+    table, max_n = _clip_table(grads)
+    check(lib().msn_grad_clamp(ptr(table), len(grads), max_n, clip_value, stream_ptr()), "msn_grad_clamp")
+    return None

@@ -6,7 +6,8 @@ sequence as Lightning's automatic optimisation --
   on_train_epoch_end -> on_validation_start -> validation_step* -> on_validation_epoch_end
 
 -- with the 9-tuple batch moved to the GPU (None / empty placeholders pass through), epoch means
-of train_loss / val_loss, and (multi-process) SUM all-reduce of the gradients before the step.
+of train_loss / val_loss, (multi-process) SUM all-reduce of the gradients before the step, and
+pl.Trainer's gradient clipping (gradient_clip_val / gradient_clip_algorithm) between the all-reduce and the step.
 Checkpointing, early stopping and W&B logging of the reference harness are out of scope.
 """
 import torch
@@ -14,6 +15,7 @@ import torch.distributed as dist
 
 from . import distributed as D
 from . import markers
+from . import optim
 
 
 def _to_device(batch, device):
@@ -73,6 +75,35 @@ def _hook(model, name):
         fn()
 
 
+def _clip_config(gradient_clip_val, gradient_clip_algorithm):
+    """pl.Trainer's clipping arguments -> None (no clipping: value None or 0) or (algorithm, value); algorithm None = "norm"."""
+    algo = "norm" if gradient_clip_algorithm is None else str(gradient_clip_algorithm).lower()
+    if algo not in ("norm", "value"):
+        raise ValueError(f"gradient_clip_algorithm must be 'norm' or 'value' (got {gradient_clip_algorithm!r})")
+    if gradient_clip_val is None:
+        return None
+    val = float(gradient_clip_val)
+    if not val >= 0.0:
+        raise ValueError(f"gradient_clip_val must be non-negative (got {gradient_clip_val!r})")
+    return (algo, val) if val > 0.0 else None
+
+
+def _clip_params(optimizer):
+    """Every parameter of the optimizer's param_groups (Lightning clips what the optimizer steps)."""
+    return [p for group in optimizer.param_groups for p in group["params"]]
+
+
+def _clip_gradients(optimizer, clip):
+    """Lightning's clip_gradients: torch.nn.utils.clip_grad_norm_ / clip_grad_value_ on the GPU (optim.py)."""
+    if clip is None:
+        return
+    algo, val = clip
+    if algo == "norm":
+        optim.clip_grad_norm_(_clip_params(optimizer), val)
+    else:
+        optim.clip_grad_value_(_clip_params(optimizer), val)
+
+
 _SEEDS = {}
 
 
@@ -85,7 +116,11 @@ def _backward_seed(loss):
 
 
 class Trainer:
-    def __init__(self, max_epochs=1, device=None, group=None, log_fn=None, sync_batchnorm=False, graphed_steps=False):
+    def __init__(self, max_epochs=1, device=None, group=None, log_fn=None, sync_batchnorm=False, graphed_steps=False,
+                 gradient_clip_val=None, gradient_clip_algorithm=None):
+        # pl.Trainer(gradient_clip_val=..., gradient_clip_algorithm=...): clip the all-reduced gradients before the step
+        self.clip = _clip_config(gradient_clip_val, gradient_clip_algorithm)
+        self.gradient_clip_val, self.gradient_clip_algorithm = gradient_clip_val, gradient_clip_algorithm
         self.max_epochs = max_epochs
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.group = group
@@ -109,7 +144,9 @@ class Trainer:
         if world > 1:
             _check_sharded_loader(train_dataloaders, self.group, "train_dataloaders")
         scheduler = self._scheduler_of(optim_config)
-        graphed = GraphedTrainStep(model.train(), optimizer, reducer=reducer, group=self.group) if self.graphed_steps else None
+        graphed = GraphedTrainStep(model.train(), optimizer, reducer=reducer, group=self.group,
+                                   gradient_clip_val=self.gradient_clip_val,
+                                   gradient_clip_algorithm=self.gradient_clip_algorithm) if self.graphed_steps else None
         for epoch in range(self.max_epochs):
             model.train()
             _hook(model, "on_train_epoch_start")
@@ -127,6 +164,7 @@ class Trainer:
                 with markers.range("backward"):
                     loss.backward(_backward_seed(loss))
                 reducer.finish()
+                _clip_gradients(optimizer, self.clip)
                 with markers.range("optimiser (RAdam)"):
                     optimizer.step()
                 losses.append(loss.detach())
@@ -248,8 +286,8 @@ class _RecordedStep:
 
 
 class GraphedTrainStep:
-    """One training step (zero_grad -> training_step -> backward -> gradient all-reduce -> RAdam) recorded as HIP graphs
-    and replayed.
+    """One training step (zero_grad -> training_step -> backward -> gradient all-reduce -> [gradient clipping] -> RAdam)
+    recorded as HIP graphs and replayed.
 
     The reference's own batch sizes (32 ... 256) -- and the 128 ... 256 rows a rank keeps when the global batch of 1024 is
     spread over 4 or 8 GPUs -- leave the GPU waiting for the host: a Maven step issues ~1300 launches and takes ~10 ms of
@@ -259,7 +297,7 @@ class GraphedTrainStep:
 
     Data parallel (world size > 1): the step is recorded in SEGMENTS around its exchanges (_RecordedStep): embedding
     all-gather | InfoNCE forward | LSE all-gather | loss all-reduce | backward of the loss and the towers + gather of the
-    gradient buckets | SUM all-reduce of the buckets | RAdam.  The collectives stay host-driven between two graph replays
+    gradient buckets | SUM all-reduce of the buckets | clipping + RAdam.  The collectives stay host-driven between two graph replays
     (gloo cannot be captured at all; RCCL needs no capture support this way), so the gradient reduction is the deferred
     form of GradientReducer (overlap=False: every bucket after backward) -- pass such a reducer or none.
     Restrictions: fixed batch shapes (others run eagerly, with the same reducer); synchronised BatchNorm issues
@@ -272,7 +310,9 @@ class GraphedTrainStep:
         for batch in loader: loss = step(batch)          # `loss` is a device tensor overwritten by the next call
     """
 
-    def __init__(self, model, optimizer, warmup=3, concurrent_towers=None, reducer=None, group=None):
+    def __init__(self, model, optimizer, warmup=3, concurrent_towers=None, reducer=None, group=None, gradient_clip_val=None,
+                 gradient_clip_algorithm=None):
+        self.clip = _clip_config(gradient_clip_val, gradient_clip_algorithm)    # as Trainer's: None = no clipping
         self.concurrent_towers = concurrent_towers      # None: as the model is set (towers fork / join inside the graph)
         self.group = group
         self.world = D.world_size(group)
@@ -291,6 +331,7 @@ class GraphedTrainStep:
         loss.backward()
         if self.reducer is not None:
             self.reducer.finish()
+        _clip_gradients(self.optimizer, self.clip)
         self.optimizer.step()
         return loss
 
@@ -306,6 +347,8 @@ class GraphedTrainStep:
             model.concurrent_towers = bool(self.concurrent_towers)
         self.optimizer.zero_grad(set_to_none=True)
         self.optimizer.graph_prepare()        # device copies of the hyper-parameters and the step count (eager)
+        if self.clip is not None:
+            optim.clip_graph_prepare(_clip_params(self.optimizer))    # the clip's pinned descriptor table (eager)
         import gc
         gc.collect()                          # no autograd graph of an earlier step (bound to other streams) may survive
         device = self.static_device()
@@ -334,7 +377,8 @@ class GraphedTrainStep:
                 self.loss = model.training_step(self.static, 0)
                 self.loss.backward()
                 if self.reducer is not None:
-                    self.reducer.finish()
+                    self.reducer.finish()         # several ranks: the clip below runs in the last segment, after the exchange
+                _clip_gradients(self.optimizer, self.clip)
                 self.optimizer.step()
                 rec.end()
         except Exception as exc:   # noqa: BLE001 -- out of memory in the private pool, an op that is illegal under capture, ...

@@ -19,6 +19,7 @@ CK = dict(dim=8, depth=2, channels=3, kernel_size=5, patch_size=4, n_out=8, drop
 BATCHNORM = "--batchnorm" in sys.argv     # ConvMixer image tower + light curves, synchronised BatchNorm
 TRAINER = "--trainer" in sys.argv         # Trainer.fit with a validation loader whose shards are UNEVEN across the ranks
 GRAPHED = "--graphed" in sys.argv         # GraphedTrainStep under data parallel (segmented capture) == the eager steps, bit for bit
+CLIP = "--clip" in sys.argv               # gradient clipping by norm, eager and graphed, == one process at the doubled batch
 WORLD = int(sys.argv[sys.argv.index("--world") + 1]) if "--world" in sys.argv else 2   # default check only: ranks sharing the GPU (<= 4)
 
 
@@ -127,6 +128,81 @@ def graphed_worker(rank, world, port, out):
     dist.destroy_process_group()
 
 
+def clip_worker(rank, world, port, out):
+    """Five data-parallel steps with gradient clipping by norm engaged at every step, issued eagerly (hook-driven reducer, then
+    optim.clip_grad_norm_ on the all-reduced gradients) and through GraphedTrainStep(gradient_clip_val=...) (two warm-up steps,
+    the recording, two replays: the clip sits in the last segment), against ONE process stepping the doubled batch with the
+    same clip: losses, clipped gradients (p.grad after the step) and parameter updates."""
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0")
+    from multimodal_supernovae_amd import distributed as D
+    from multimodal_supernovae_amd import optim
+    from multimodal_supernovae_amd.trainer import GraphedTrainStep
+    D.init_from_env(backend="gloo")
+    b, steps, v = 8, 5, 0.05
+    full = make_batch(steps * world * b)
+    rows = lambda i, lo, n: tuple(t[lo:lo + n].cuda() if t is not None else None for t in full)
+    local = [rows(i, (i * world + rank) * b, b) for i in range(steps)]
+
+    def snapshot(model):
+        return ([p.detach().clone() for p in model.parameters()],
+                [p.grad.detach().clone() if p.grad is not None else None for p in model.parameters()])
+
+    def eager(model, batches, reducer, totals):
+        opt = model.configure_optimizers()["optimizer"]
+        losses = []
+        for i, batch in enumerate(batches):
+            opt.zero_grad(set_to_none=True)
+            loss = model.training_step(batch, i)
+            loss.backward()
+            if reducer is not None:
+                reducer.finish()
+            totals.append(float(optim.clip_grad_norm_(list(model.parameters()), v)))
+            opt.step()
+            losses.append(float(loss.detach()))
+        return losses
+
+    p0 = [p.detach().clone() for p in make_model().parameters()]
+    model = make_model()
+    D.broadcast_module(model)
+    reducer = D.GradientReducer(model.parameters(), bucket_bytes=64 << 10)
+    totals = []
+    le = eager(model, local, reducer, totals)
+    reducer.remove()
+    torch.cuda.synchronize()
+    res = {"eager": (le,) + snapshot(model)}
+    model = make_model()
+    D.broadcast_module(model)
+    step = GraphedTrainStep(model, model.configure_optimizers()["optimizer"], warmup=2, gradient_clip_val=v)
+    lg = [float(step(batch, i).detach()) for i, batch in enumerate(local)]
+    torch.cuda.synchronize()
+    res["graphed"] = (lg,) + snapshot(model)
+    segments = step.graph.segments if step.graph is not None else 0
+    dist.barrier()
+    dist.destroy_process_group()
+    if rank != 0:
+        return
+    ref = make_model()                     # single process at the global batch, same clip
+    rtot = []
+    lr_ = eager(ref, [rows(i, i * world * b, world * b) for i in range(steps)], None, rtot)
+    torch.cuda.synchronize()
+    rp, rg = snapshot(ref)
+    names = [k for k, _ in ref.named_parameters()]
+    worst = {}
+    for kind, (losses, ps, gs) in res.items():
+        lw = max(abs(x - y) / abs(y) for x, y in zip(losses, lr_))
+        gw = uw = 0.0
+        for k, a, c, ga, gc, q0 in zip(names, ps, rp, gs, rg, p0):
+            if k == "logit_bias" or gc is None:          # analytically zero gradient: rounding noise only
+                continue
+            gw = max(gw, float((ga - gc).abs().max()) / (float(gc.abs().max()) + 1e-12))
+            du = c - q0
+            uw = max(uw, float(((a - q0) - du).abs().max()) / (float(du.abs().max()) + 1e-12))
+        worst[kind] = (lw, gw, uw)
+    out["worst"] = worst
+    out["clip_engaged"] = all(t > v for t in totals) and all(t > v for t in rtot)
+    out["segments"] = segments
+
+
 def worker(rank, world, port, out):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0")
     from multimodal_supernovae_amd import distributed as D
@@ -172,6 +248,16 @@ def worker(rank, world, port, out):
 if __name__ == "__main__":
     ctx = mp.get_context("spawn")
     out = ctx.Manager().dict()
+    if CLIP:
+        procs = [ctx.Process(target=clip_worker, args=(r, 2, 29617, out)) for r in range(2)]
+        [p.start() for p in procs]
+        [p.join(300) for p in procs]
+        print(dict(out), [p.exitcode for p in procs])
+        ok = all(p.exitcode == 0 for p in procs) and "worst" in out and out["clip_engaged"] and out["segments"] >= 4
+        # the tolerances of the default check: losses 1e-4 relative, gradients (and here the updates) 1e-3 of their largest entry
+        ok = ok and all(lw < 1e-4 and gw < 1e-3 and uw < 1e-3 for lw, gw, uw in out["worst"].values())
+        print("DIST CHECK", "OK" if ok else "FAILED")
+        sys.exit(0 if ok else 1)
     if GRAPHED:
         procs = [ctx.Process(target=graphed_worker, args=(r, 2, 29615, out)) for r in range(2)]
         [p.start() for p in procs]
