@@ -682,6 +682,40 @@ int msn_masked_mse_fwd(const float* pred, const float* target, const uint8_t* se
 int msn_masked_mse_bwd(const float* pred, const float* target, const uint8_t* select, int64_t n,
                        const float* stats, const float* grad_out, float* dpred, msn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Supervised heads on the towers (models_finetune.py: ClipMLP): classification / regression loss and validation metrics.
+ * Cross-entropy with the semantics of torch.nn.functional.cross_entropy(logits, target, weight=w, reduction="mean"):
+ * logits (N, C) fp32 with row stride ld, target int64 (N), weight (C) fp32 or NULL (= ones); 2 <= C <= 1024, N >= 1.
+ * A target outside [0, C) -- torch's ignore_index -100 among them -- takes no part (numerator, denominator, gradient) and
+ * is never used as an index.
+ *   fwd: out[3] (DEVICE) = {loss, denom, numerator}: numerator = sum_i w[y_i] (lse_i - x[i, y_i]), denom = sum_i w[y_i],
+ *        loss = numerator / (denom_in ? denom_in[0] : denom) -- denom_in: a DEVICE scalar of the caller's for a mean over
+ *        more rows than this call sees, when it is known before the call (models_finetune.py passes NULL: under data
+ *        parallel the ranks' denominator exists only after this forward, so it divides out[2] by the all-reduced out[1]
+ *        itself and hands that sum to bwd as `denom`); all rows ignored gives nan.  Also lse[i] (N) and
+ *        pred[i] = argmax_c x[i, c] (int32, first maximal index).  Row terms in fp32 (max subtracted, expf / log1pf), sums over
+ *        rows in fp64: ONE launch up to N = 4096 (C <= 16) / N = 64 (wider rows), else per-block partials in `ws`
+ *        (msn_cross_entropy_workspace_bytes) + one finishing block that adds them in a fixed order.  Bitwise reproducible.
+ *   bwd: dlogits[i, c] = grad_out[0] * w[y_i] * (softmax(x_i)[c] - [c == y_i]) / denom[0] (DEVICE scalars; rows of an
+ *        ignored target are zeroed), one launch.  The softmax is recomputed from the logits, not from the fp32 lse
+ *        (which rounds to 4e-6 for logits of magnitude 60). */
+size_t msn_cross_entropy_workspace_bytes(int64_t N, int C);
+int msn_cross_entropy_fwd(const float* logits, int64_t ld, const int64_t* target, const float* weight, int64_t N, int C,
+                          const float* denom_in, float* lse, int* pred, float* out, void* ws, size_t ws_bytes,
+                          msn_stream_t stream);
+int msn_cross_entropy_bwd(const float* logits, int64_t ld, const int64_t* target, const float* weight, int64_t N, int C,
+                          const float* denom, const float* grad_out, float* dlogits, int64_t lddx, msn_stream_t stream);
+/* cm[target[i], pred[i]] += 1 for every row with both in [0, C): cm a caller-owned (C, C) int32 DEVICE matrix that
+ * accumulates over calls (MulticlassFBetaScore / accuracy are formed from it on the host).  Integer adds only; up to
+ * C = 64 every workgroup counts in its own LDS copy and adds each non-zero cell once. */
+int msn_confusion_matrix(const int64_t* target, const int* pred, int64_t N, int C, int* cm, msn_stream_t stream);
+/* acc[6] (DEVICE, fp64, caller-owned, accumulates over calls) += {n, sum|d|, sum d^2, sum y, sum y^2, n_out} with
+ * d = pred - y formed in fp64 and n_out = rows with |d| / (1 + y) > 0.15 (the outlier fraction of photometric redshifts).
+ * Per-block fp64 partials in `ws` (msn_regression_stats_workspace_bytes; none up to N = 4096) + one finishing block. */
+size_t msn_regression_stats_workspace_bytes(int64_t N);
+int msn_regression_stats(const float* pred, const float* target, int64_t N, double* acc, void* ws, size_t ws_bytes,
+                         msn_stream_t stream);
+
 /* feat[r] = (x[r]*m, t[r]*inv_norm*m, m, 0), m = mask[r]: the 4 input channels of the build-defined 1-D CNN
  * encoder for light curves / spectra (value, normalised time / wavelength, validity, pad). */
 int msn_series_features(const float* x, const float* t, const uint8_t* mask, int64_t rows, float inv_norm,

@@ -119,6 +119,12 @@ SIGNATURES = {
     "msn_augment_series": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_f32, c_ptr, c_ptr]),
     "msn_masked_mse_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
     "msn_masked_mse_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "msn_cross_entropy_workspace_bytes": (c_size, [c_i64, c_int]),
+    "msn_cross_entropy_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "msn_cross_entropy_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    "msn_confusion_matrix": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr]),
+    "msn_regression_stats_workspace_bytes": (c_size, [c_i64]),
+    "msn_regression_stats": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
     "msn_series_features": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_f32, c_ptr, c_ptr]),
     "msn_relu_mask": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
     "msn_im2col": (c_int, [c_ptr] + [c_int] * 10 + [c_ptr, c_ptr]),

@@ -1,0 +1,351 @@
+"""Supervised heads on the CLIP towers: supernova classification and redshift regression (SURVEY.md section 2 rows 3, 4,
+9, 11 -- what the reference's main script and its `ClipMLP` / finetune_clip.py train the towers for), with the reference's
+names where SURVEY records them.  The reference's source is not pinned line by line here: the surface is this module's,
+checked against a plain-PyTorch restatement in tests/test_supervised_gpu.py.
+
+    cross_entropy(logits, target, weight=None)      -- F.cross_entropy(..., reduction="mean") on csrc/supervised.hip
+    ClassificationMetrics / RegressionMetrics       -- device accumulators (confusion matrix / six fp64 sums); compute()
+                                                       is the one host copy, its arithmetic a pure function
+    ClipMLP(clip_model, classification=True | regression=True, ...)
+                                                    -- MLP head on the concatenated unit-norm embeddings of a
+                                                       LightCurveImageCLIP, optionally with a frozen backbone
+
+Data parallel: the Trainer SUM-all-reduces parameter gradients, so every rank's loss is its numerator over the GLOBAL
+denominator (rows, or class-weight sum) and the returned value is the all-reduced global loss: a 2-rank step equals the
+single-process step at the doubled batch.
+"""
+import torch
+import torch.nn as nn
+
+from . import _lib
+from . import distributed as D
+from ._lib import check, lib, ptr, stream_ptr
+from .loss import _AllReduceSum
+from .models_multimodal import MLP
+from .models_pretraining import masked_mse
+from .ops import _f32c
+
+_TOWER_ORDER = ("host_galaxy", "lightcurve", "spectral")      # LightCurveImageCLIP.forward's fixed order (img, lc, sp)
+
+
+def _ws(nbytes, device):
+    return torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=device)
+
+
+# ------------------------------------------------------------------------------------------- cross-entropy
+class _CrossEntropy(torch.autograd.Function):
+    """Returns (loss, pred): loss = this process's numerator over the denominator (its own, or the ranks' sum when
+    `sharded`); pred = row arg-max (int32, no gradient)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, group, sharded):
+        _lib.require_gpu()
+        if logits.dim() != 2:
+            raise ValueError(f"cross_entropy: logits must be (N, C) (got {tuple(logits.shape)})")
+        if logits.device.type != "cuda" or logits.dtype != torch.float32:
+            raise _lib.MsnHipError(f"cross_entropy: logits must be float32 on the GPU (got {logits.dtype} on {logits.device}); "
+                                   "there is no CPU path")
+        if logits.stride(1) != 1:
+            logits = logits.contiguous()
+        N, C = logits.shape
+        if target.shape != (N,) or target.dtype != torch.int64 or target.device != logits.device:
+            raise ValueError(f"cross_entropy: target must be int64 of shape ({N},) on {logits.device}")
+        target = target.contiguous()
+        if weight is not None:
+            if weight.shape != (C,):
+                raise ValueError(f"cross_entropy: weight must have shape ({C},)")
+            weight = _f32c(weight.detach(), "weight")
+        dev = logits.device
+        L = lib()
+        lse = torch.empty(N, dtype=torch.float32, device=dev)
+        pred = torch.empty(N, dtype=torch.int32, device=dev)
+        out = torch.empty(3, dtype=torch.float32, device=dev)              # {loss, denominator, numerator}
+        nb = L.msn_cross_entropy_workspace_bytes(N, C)
+        ws = _ws(nb, dev) if nb else None                                  # the shapes of training take one workgroup: no scratch
+        check(L.msn_cross_entropy_fwd(ptr(logits), logits.stride(0), ptr(target), ptr(weight), N, C, ptr(None), ptr(lse),
+                                      ptr(pred), ptr(out), ptr(ws), nb, stream_ptr()), "msn_cross_entropy_fwd")
+        if sharded:
+            denom = D.all_reduce_sum(out[1].clone(), group, kind="loss_denominator_all_reduce")
+            loss = out[2] / denom                                          # this rank's share of the global mean
+        else:
+            denom, loss = out[1], out[0]
+        ctx.save_for_backward(logits, target, weight, denom)
+        ctx.mark_non_differentiable(pred)
+        ctx.set_materialize_grads(False)        # no zero-filled "gradient" of the int32 predictions (a launch per backward)
+        return loss, pred
+
+    @staticmethod
+    def backward(ctx, g, _gpred):
+        if g is None:
+            return None, None, None, None, None
+        logits, target, weight, denom = ctx.saved_tensors
+        N, C = logits.shape
+        g = g.to(torch.float32).reshape(()).contiguous()
+        dx = torch.empty((N, C), dtype=torch.float32, device=logits.device)
+        check(lib().msn_cross_entropy_bwd(ptr(logits), logits.stride(0), ptr(target), ptr(weight), N, C, ptr(denom), ptr(g),
+                                          ptr(dx), C, stream_ptr()), "msn_cross_entropy_bwd")
+        return dx, None, None, None, None
+
+
+def _cross_entropy(logits, target, weight=None, group=None, sharded=None):
+    if sharded is None:
+        sharded = D.world_size(group) > 1
+    share, pred = _CrossEntropy.apply(logits, target, weight, group, bool(sharded))
+    return (_AllReduceSum.apply(share, group) if sharded else share), pred
+
+
+def cross_entropy(logits, target, weight=None, *, group=None):
+    """torch.nn.functional.cross_entropy(logits, target, weight=weight, reduction="mean") for float32 (N, C) logits on the
+    GPU (2 <= C <= 1024), int64 targets, default ignore_index -100 (any target outside [0, C) is ignored likewise).  With
+    torch.distributed initialised over more than one rank every rank passes its LOCAL rows and gets the global mean (see the
+    module docstring); gradients of the ranks are then to be summed."""
+    return _cross_entropy(logits, target, weight, group)[0]
+
+
+def argmax_rows(logits):
+    """Row arg-max of (N, C) logits as int32 (first maximal index, as torch.argmax) from the cross-entropy forward kernel."""
+    fake = torch.zeros(logits.shape[0], dtype=torch.int64, device=logits.device)
+    return _cross_entropy(logits.detach(), fake, sharded=False)[1]
+
+
+# ------------------------------------------------------------------------------------------------- metrics
+def classification_metrics(cm):
+    """Pure host function of a (C, C) confusion matrix cm[true, predicted]: accuracy, per-class F1 = 2 tp / (2 tp + fp + fn),
+    micro F1 from the summed counts, macro F1 = mean over the classes with tp + fp + fn > 0 (a class that neither occurs
+    nor is predicted does not count as a zero: torchmetrics' macro average)."""
+    cm = torch.as_tensor(cm).to(torch.float64)
+    tp = cm.diagonal()
+    fp = cm.sum(dim=0) - tp
+    fn = cm.sum(dim=1) - tp
+    den = 2 * tp + fp + fn
+    seen = den > 0
+    f1 = torch.where(seen, 2 * tp / den.clamp(min=1.0), torch.zeros_like(den))
+    total = float(cm.sum())
+    den_micro = float(den.sum())
+    return {"acc": float(tp.sum()) / total if total > 0 else float("nan"),
+            "f1_macro": float(f1[seen].mean()) if bool(seen.any()) else float("nan"),
+            "f1_micro": 2 * float(tp.sum()) / den_micro if den_micro > 0 else float("nan"),
+            "f1_per_class": [float(v) for v in f1]}
+
+
+def regression_metrics(sums):
+    """Pure host function of the six sums {n, sum|d|, sum d^2, sum y, sum y^2, n_out} (d = prediction - y): the keys of the
+    reference's regression_metrics_list.pkl -- L1, L2 (mean absolute / squared error), R2, OLF (outlier fraction,
+    |d| / (1 + y) > 0.15)."""
+    n, sad, ssd, sy, syy, n_out = (float(v) for v in sums)
+    if n <= 0:
+        return {"L1": float("nan"), "L2": float("nan"), "R2": float("nan"), "OLF": float("nan")}
+    var = syy - sy * sy / n
+    return {"L1": sad / n, "L2": ssd / n, "R2": 1.0 - ssd / var if var != 0 else float("nan"), "OLF": n_out / n}
+
+
+class ClassificationMetrics:
+    """Confusion matrix accumulated on the device over the batches of a validation epoch (msn_confusion_matrix)."""
+
+    def __init__(self, n_classes):
+        self.n_classes = int(n_classes)
+        self.cm = None
+
+    def reset(self):
+        if self.cm is not None:
+            self.cm.zero_()
+
+    def update(self, pred, target):
+        """pred: int32 class per row (cross-entropy's arg-max) or (N, C) logits; target int64.  Enqueue only."""
+        if pred.shape[0] == 0:             # an empty batch counts nothing
+            return
+        if pred.dim() == 2:
+            pred = argmax_rows(pred)
+        pred = pred.to(torch.int32).contiguous()
+        target = target.to(torch.int64).contiguous()
+        if self.cm is None or self.cm.device != pred.device:
+            self.cm = torch.zeros((self.n_classes, self.n_classes), dtype=torch.int32, device=pred.device)
+        check(lib().msn_confusion_matrix(ptr(target), ptr(pred), pred.numel(), self.n_classes, ptr(self.cm), stream_ptr()),
+              "msn_confusion_matrix")
+
+    def all_reduce(self, group=None):
+        if self.cm is not None and D.world_size(group) > 1:
+            D.all_reduce_sum(self.cm, group, kind="metric_all_reduce")
+
+    def compute(self):
+        if self.cm is None:
+            return classification_metrics(torch.zeros((self.n_classes, self.n_classes)))
+        return classification_metrics(self.cm.cpu())
+
+
+class RegressionMetrics:
+    """The six fp64 sums accumulated on the device over the batches of a validation epoch (msn_regression_stats)."""
+
+    def __init__(self):
+        self.sums = None
+
+    def reset(self):
+        if self.sums is not None:
+            self.sums.zero_()
+
+    def update(self, pred, target):
+        pred = _f32c(pred.detach().reshape(-1), "pred")
+        target = _f32c(target.detach().reshape(-1).to(pred.device), "target")
+        if pred.numel() != target.numel():
+            raise ValueError("RegressionMetrics.update: prediction and target differ in length")
+        if pred.numel() == 0:
+            return
+        if self.sums is None or self.sums.device != pred.device:
+            self.sums = torch.zeros(6, dtype=torch.float64, device=pred.device)
+        nb = lib().msn_regression_stats_workspace_bytes(pred.numel())
+        ws = _ws(nb, pred.device) if nb else None
+        check(lib().msn_regression_stats(ptr(pred), ptr(target), pred.numel(), ptr(self.sums), ptr(ws), nb, stream_ptr()),
+              "msn_regression_stats")
+
+    def all_reduce(self, group=None):
+        if self.sums is not None and D.world_size(group) > 1:
+            D.all_reduce_sum(self.sums, group, kind="metric_all_reduce")
+
+    def compute(self):
+        return regression_metrics(self.sums.cpu().tolist() if self.sums is not None else [0.0] * 6)
+
+
+# -------------------------------------------------------------------------------------------------- module
+class ClipMLP(nn.Module):
+    """MLP head on the concatenated embeddings of a (pretrained) LightCurveImageCLIP, trained for classification
+    (cross-entropy against batch[8]) or redshift regression (MSE against batch[7]); Lightning hooks as plain methods,
+    driven by trainer.Trainer / GraphedTrainStep.  state_dict: clip_model.*, mlp.layers.{0,3,6,...}.*, class_weights."""
+
+    def __init__(self, clip_model, learning_rate=1e-3, regression=False, classification=False, n_classes=5, hidden_dim=128,
+                 num_layers=2, dropout=0.0, freeze_backbone=False, class_weights=None, optimizer_kwargs=None):
+        super().__init__()
+        if bool(regression) == bool(classification):
+            raise ValueError("ClipMLP needs exactly one of regression=True / classification=True")
+        if "meta" in clip_model.combinations:
+            raise ValueError("ClipMLP: a clip_model with the 'meta' tower reads redshift and class -- the labels; build it "
+                             "without 'meta' and load the pretrained state_dict with strict=False")
+        self.towers = [c for c in _TOWER_ORDER if c in clip_model.combinations]
+        if not self.towers:
+            raise ValueError("ClipMLP: the clip_model has no tower")
+        if class_weights is not None and not classification:
+            raise ValueError("ClipMLP: class_weights belong to classification")
+        self.clip_model = clip_model
+        self.regression, self.classification = bool(regression), bool(classification)
+        self.n_classes = int(n_classes)
+        self.learning_rate = learning_rate
+        self.optimizer_kwargs = dict(optimizer_kwargs or {})
+        self.freeze_backbone = bool(freeze_backbone)
+        self.mlp = MLP(input_dim=len(self.towers) * clip_model.enc_dim, hidden_dim=hidden_dim,
+                       output_dim=self.n_classes if classification else 1, num_layers=num_layers, dropout=dropout)
+        if class_weights is not None:
+            w = torch.as_tensor(class_weights, dtype=torch.float32).reshape(-1)
+            if w.numel() != self.n_classes:
+                raise ValueError(f"ClipMLP: {self.n_classes} classes need {self.n_classes} class weights (got {w.numel()})")
+            self.register_buffer("class_weights", w.clone())
+        else:
+            self.class_weights = None
+        if self.freeze_backbone:
+            self.clip_model.requires_grad_(False)
+            self.clip_model.eval()
+        self.group = None
+        self.metrics = ClassificationMetrics(self.n_classes) if classification else RegressionMetrics()
+        self._val_batches = 0
+        self._ones = {}
+        self.logged = {}
+
+    def log(self, name, value, **kwargs):
+        # detached: a logged loss must not keep its autograd graph alive into the next step
+        self.logged[name] = value.detach() if torch.is_tensor(value) else value
+
+    def train(self, mode=True):
+        super().train(mode)
+        if self.freeze_backbone:
+            self.clip_model.eval()          # frozen towers: no dropout, BatchNorm on its running statistics
+        return self
+
+    def features(self, *batch):
+        """(B, M * enc_dim): the unit-norm projected embeddings side by side in the order image, light curve, spectrum."""
+        if self.freeze_backbone:
+            with torch.no_grad():
+                embs = self.clip_model(*batch)
+        else:
+            embs = self.clip_model(*batch)
+        return embs[0] if len(embs) == 1 else torch.cat(embs, dim=1)
+
+    def forward(self, *batch):
+        """(B, n_classes) logits, or (B, 1) redshift predictions."""
+        return self.mlp(self.features(*batch))
+
+    def configure_optimizers(self):
+        """RAdam over the parameters that take part: the head, plus towers and projections unless frozen -- never the
+        contrastive logit_scale / logit_bias (no gradient here; coupled weight decay must not move them)."""
+        from .optim import RAdam
+        params = list(self.mlp.parameters())
+        if not self.freeze_backbone:
+            params += [p for n, p in self.clip_model.named_parameters() if n not in ("logit_scale", "logit_bias")]
+        return {"optimizer": RAdam(params, lr=self.learning_rate, **self.optimizer_kwargs)}
+
+    # -- losses ------------------------------------------------------------------------------------------------------
+    def _all_true(self, n, device):
+        """The all-true selection of the masked-MSE kernels (plain MSE = every element selected)."""
+        key = (n, device)
+        if key not in self._ones:
+            ones = torch.ones(n, dtype=torch.uint8, device=device)
+            if torch.cuda.is_current_stream_capturing():
+                return ones               # filled by a node of the recording only: not kept for eager use
+            self._ones[key] = ones
+        return self._ones[key]
+
+    def _mse(self, pred, target, sharded):
+        loss = masked_mse(pred, target, self._all_true(pred.numel(), pred.device))
+        if not sharded:
+            return loss
+        n_local = float(pred.numel())
+        n_global = D.all_reduce_sum(torch.full((), n_local, dtype=torch.float32, device=pred.device), self.group,
+                                    kind="loss_denominator_all_reduce")
+        return _AllReduceSum.apply(loss * (n_local / n_global), self.group)
+
+    def _loss(self, batch, sharded):
+        """-> (loss, prediction, target): class per row (int32) / redshift per row."""
+        out = self(*batch)
+        if self.classification:
+            target = batch[8].to(torch.int64).reshape(-1)
+            loss, pred = _cross_entropy(out, target, self.class_weights, self.group, sharded)
+            return loss, pred, target
+        target = batch[7].to(torch.float32).reshape(-1)
+        pred = out.squeeze(1)
+        return self._mse(pred, target, sharded), pred, target
+
+    def training_step(self, batch, batch_idx):
+        loss, _, _ = self._loss(batch, D.world_size(self.group) > 1)
+        self.log("train_loss", loss, on_epoch=True, on_step=False, prog_bar=True, logger=True)
+        return loss
+
+    def on_validation_start(self):
+        self.metrics.reset()
+        self._val_batches = 0
+
+    def validation_step(self, batch, batch_idx):
+        """Per shard, as the Trainer validates: no collective inside the loop, no host synchronisation."""
+        loss, pred, target = self._loss(batch, False)
+        self.metrics.update(pred.detach(), target)
+        self._val_batches += 1
+        self.log("val_loss", loss, on_epoch=True, on_step=False, prog_bar=True, logger=True)
+        return loss
+
+    def on_validation_epoch_end(self):
+        world = D.world_size(self.group)
+        if world == 1 and not self._val_batches:
+            return
+        if world > 1:
+            if self._val_batches == 0:        # every rank enters the collective, also one whose shard was empty
+                dev = next(self.mlp.parameters()).device
+                if self.classification and self.metrics.cm is None:
+                    self.metrics.cm = torch.zeros((self.n_classes, self.n_classes), dtype=torch.int32, device=dev)
+                if self.regression and self.metrics.sums is None:
+                    self.metrics.sums = torch.zeros(6, dtype=torch.float64, device=dev)
+            self.metrics.all_reduce(self.group)
+        res = self.metrics.compute()
+        kw = dict(on_epoch=True, on_step=False, prog_bar=True, logger=True)
+        if self.classification:
+            self.log("f1_val", res["f1_macro"], **kw)
+            self.log("f1_micro_val", res["f1_micro"], **kw)
+            self.log("acc_val", res["acc"], **kw)
+        else:
+            for k in ("L1", "L2", "R2", "OLF"):
+                self.log(f"{k}_val", res[k], **kw)

@@ -3,8 +3,9 @@ constructor arguments, encoder slots, method names, the 9-tuple batch and the st
 are the reference's; the arithmetic is libmsn_hip's.  torch.nn.Conv2d / BatchNorm2d / Linear /
 Embedding objects are parameter holders only (their forward is never called).
 
-Out of scope here: the supervised `regression` / `classification` heads of
-the reference constructor -- requesting them raises NotImplementedError.
+The supervised `regression` / `classification` heads live in models_finetune.ClipMLP (a head on the
+towers of this module, optionally frozen); requesting them from this constructor raises
+NotImplementedError.
 """
 import math
 from typing import Dict, List, Optional
@@ -114,8 +115,8 @@ class LightCurveImageCLIP(nn.Module):
                  n_classes: int = 5, global_negatives: bool = True):
         super().__init__()
         if regression or classification:
-            raise NotImplementedError("the supervised regression / classification heads are outside the "
-                                      "contrastive hot path this package implements")
+            raise NotImplementedError("this class is the contrastive model; the supervised regression / classification "
+                                      "heads are models_finetune.ClipMLP(clip_model, regression=... / classification=...)")
         default_t = {"n_out": 128, "emb": 256, "heads": 2, "depth": 8, "time_norm": 10000.0}
         transformer_kwargs = dict(transformer_kwargs or default_t)
         transformer_spectral_kwargs = dict(transformer_spectral_kwargs or default_t)
