@@ -580,13 +580,19 @@ int msn_dwconv_bwd(const float* dpre, const float* x, const float* w, int B, int
  * decay, rectification once rho_t > 5) -- the optimiser of src/models_multimodal.py:306-310.
  * table: DEVICE array of n_tensors records of five 64-bit words {p*, g*, m*, v*, numel};
  * step is the 1-based update count.  One launch for the whole model; 28 B of HBM traffic / parameter.
+ * beta1 / beta2 are doubles, as torch holds them: 1 / (1 - beta1^t) and the rectification term are derived from the exact
+ * values, and the kernel receives beta and 1 - beta each rounded to float once (it never forms 1.f - beta).
  */
-int msn_radam_step(const void* table, int n_tensors, int64_t max_numel, float lr, float beta1, float beta2,
+int msn_radam_step(const void* table, int n_tensors, int64_t max_numel, float lr, double beta1, double beta2,
                    float eps, float weight_decay, int64_t step, msn_stream_t stream);
-/* The same step for a training step recorded in a HIP graph: hyper[8] (device) = {lr, beta1, beta2, eps, weight_decay,
- * -, -, -}, step_counter[1] (device int64: steps taken so far).  Every launch increments the counter and derives
- * 1 / (1 - beta1^t) and the rectification term from it ON the device, so replays need no host write. */
-int msn_radam_step_dev(const void* table, int n_tensors, int64_t max_numel, float* hyper, long long* step_counter,
+/* The same step for a training step recorded in a HIP graph.  hyper: DEVICE block of 64 bytes, 8-byte aligned:
+ *   bytes  0 .. 15  double beta1, beta2 (exact)
+ *   bytes 16 .. 43  float lr, beta1, beta2, eps, weight_decay, 1 - beta1, 1 - beta2 (each rounded once from double by the host)
+ *   bytes 44 .. 51  float inv_c1, rect_scale (written by every launch);  bytes 52 .. 63 padding
+ * step_counter[1] (device int64: steps taken so far).  Every launch increments the counter and derives
+ * 1 / (1 - beta1^t) and the rectification term from the exact betas ON the device, so replays need no host write; a changed
+ * hyper-parameter is carried in by rewriting bytes 0 .. 43 on the replaying stream between two replays. */
+int msn_radam_step_dev(const void* table, int n_tensors, int64_t max_numel, void* hyper, long long* step_counter,
                        msn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------

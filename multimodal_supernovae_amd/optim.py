@@ -102,10 +102,8 @@ class RAdam(torch.optim.Optimizer):
             ps = [p for p in group["params"] if len(self.state[p])]
             if not ps:
                 continue
-            b1, b2 = group["betas"]
             dev = ps[0].device
-            hyper = torch.tensor([group["lr"], b1, b2, group["eps"], group["weight_decay"], 0.0, 0.0, 0.0],
-                                 dtype=torch.float32, device=dev)
+            hyper = self._hyper_block(group).to(dev)
             counter = torch.tensor([int(self.state[ps[0]]["step"])], dtype=torch.int64, device=dev)
             table_host = torch.empty(5 * len(group["params"]), dtype=torch.int64).pin_memory()
             self._graph_ready[gi] = (hyper, counter, table_host)
@@ -129,6 +127,18 @@ class RAdam(torch.optim.Optimizer):
         b1, b2 = group["betas"]
         return (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
 
+    @staticmethod
+    def _hyper_block(group):
+        """Host image of the 64-byte device block msn_radam_step_dev reads (csrc/optim.hip, RadamHyperDev), as 8 float64 words:
+        words 0, 1 = the exact betas (radam_prepare_kernel derives the step-dependent terms from them in double); then, as
+        float32, {lr, beta1, beta2, eps, weight_decay, 1 - beta1, 1 - beta2}, each rounded ONCE from the double value, and
+        {inv_c1, rect_scale} which the device writes."""
+        lr, b1, b2, eps, wd = RAdam._hyper_of(group)
+        block = torch.zeros(8, dtype=torch.float64)
+        block[0], block[1] = b1, b2
+        block.view(torch.float32)[4:11] = torch.tensor([lr, b1, b2, eps, wd, 1.0 - b1, 1.0 - b2], dtype=torch.float64)
+        return block
+
     def graph_pre_replay(self):
         """Keep the host-side step counts in line with the device counter a replay increments, and carry a changed
         learning rate / betas / eps / weight decay (an lr scheduler, a manual edit of param_groups) into the device
@@ -143,7 +153,8 @@ class RAdam(torch.optim.Optimizer):
                 st["step"] = step
             now = self._hyper_of(group)
             if seen.setdefault(li, self._graph_hyper_captured.get(id(group), now)) != now:
-                hyper[:5].copy_(torch.tensor(now, dtype=torch.float32), non_blocking=False)
+                # bytes 0 .. 43: the exact betas and the seven rounded scalars; inv_c1 / rect_scale stay the device's
+                hyper.view(torch.float32)[:11].copy_(self._hyper_block(group).view(torch.float32)[:11], non_blocking=False)
                 seen[li] = now
 
     @torch.no_grad()
@@ -189,7 +200,7 @@ class RAdam(torch.optim.Optimizer):
                 table = slot[0][:len(words)].to(dev, non_blocking=True)
                 slot[1] = torch.cuda.Event()
                 slot[1].record()
-                b1, b2 = group["betas"]
+                b1, b2 = group["betas"]                  # passed as doubles: the library rounds beta and 1 - beta once each
                 check(lib().msn_radam_step(ptr(table), len(items), max_n, group["lr"], b1, b2, group["eps"],
                                            group["weight_decay"], step, stream_ptr()), "msn_radam_step")
         return loss
