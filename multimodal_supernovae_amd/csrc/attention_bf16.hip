@@ -23,10 +23,6 @@
 
 namespace msn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
 typedef __attribute__((address_space(1))) const void agptr_t;
 typedef __attribute__((address_space(3))) void alptr_t;
 
@@ -51,24 +47,6 @@ struct BAttn {
 };
 
 __device__ __forceinline__ int aswz(int r) { return (r >> 1) & 7; }
-__device__ __forceinline__ u16 abf(float f) {
-    const __bf16 b = (__bf16)f;
-    return *reinterpret_cast<const u16*>(&b);
-}
-__device__ __forceinline__ float afl(u16 v) { return __uint_as_float((unsigned)v << 16); }
-__device__ __forceinline__ void a_read128(bf16x8& dst, unsigned addr) { asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr)); }
-__device__ __forceinline__ void a_read_tr(bf16x4& dst, unsigned addr) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(dst) : "v"(addr));
-}
-// (the same with an immediate byte offset: the tile index of an image read is added by the instruction, not by the vector ALU)
-template <int OFF>
-__device__ __forceinline__ void a_read128_o(bf16x8& dst, unsigned addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
-template <int OFF>
-__device__ __forceinline__ void a_read_tr_o(bf16x4& dst, unsigned addr) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
 __device__ __forceinline__ void a_wait_lds() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
@@ -195,16 +173,16 @@ __global__ __launch_bounds__(64 * AWAVES) void battn_fwd_kernel(const BAttn p) {
             // scores of 32 keys (tiles 2j, 2j+1): S^T tile = K_tile . Q^T -> lane: query l15, keys 4g..4g+3 of each tile
             const unsigned boff = (unsigned)j * 4096u;
             bf16x8 kf[2][2];
-            a_read128_o<0>(kf[0][0], kb0 + boff);
-            a_read128_o<0>(kf[0][1], kb1 + boff);
-            a_read128_o<2048>(kf[1][0], kb0 + boff);
-            a_read128_o<2048>(kf[1][1], kb1 + boff);
+            ds_read128_o<0>(kf[0][0], kb0 + boff);
+            ds_read128_o<0>(kf[0][1], kb1 + boff);
+            ds_read128_o<2048>(kf[1][0], kb0 + boff);
+            ds_read128_o<2048>(kf[1][1], kb1 + boff);
             // V^T fragments of the same 32 keys for the four d tiles (transposed reads), requested early
             bf16x4 vf[4][2];
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
-                a_read_tr_o<0>(vf[dt][0], vb[dt] + boff);
-                a_read_tr_o<2048>(vf[dt][1], vb[dt] + boff);
+                ds_read_tr_o<0>(vf[dt][0], vb[dt] + boff);
+                ds_read_tr_o<2048>(vf[dt][1], vb[dt] + boff);
             }
             a_wait_lds();
             f32x4 acc[2];
@@ -258,7 +236,7 @@ __global__ __launch_bounds__(64 * AWAVES) void battn_fwd_kernel(const BAttn p) {
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
                 ushort4 v;
-                v.x = abf(o[dt][0] * inv); v.y = abf(o[dt][1] * inv); v.z = abf(o[dt][2] * inv); v.w = abf(o[dt][3] * inv);
+                v.x = f2bf(o[dt][0] * inv); v.y = f2bf(o[dt][1] * inv); v.z = f2bf(o[dt][2] * inv); v.w = f2bf(o[dt][3] * inv);
                 *reinterpret_cast<ushort4*>(op + 16 * dt) = v;
             }
             if (g == 0) p.lse[((int64_t)b * p.H + h) * T + q] = (m + log2f(l)) * (1.f / ALOG2E);
@@ -314,19 +292,19 @@ __global__ __launch_bounds__(64 * AWAVES) void battn_bwd_dq_kernel(const BAttn p
         for (int j = 0; j < nblk; ++j) {
             const unsigned boff = (unsigned)j * 4096u;
             bf16x8 kf[2][2], vf[2][2];
-            a_read128_o<0>(kf[0][0], kb0 + boff);
-            a_read128_o<0>(kf[0][1], kb1 + boff);
-            a_read128_o<2048>(kf[1][0], kb0 + boff);
-            a_read128_o<2048>(kf[1][1], kb1 + boff);
-            a_read128_o<AIMG>(vf[0][0], kb0 + boff);            // (the V image follows the K image)
-            a_read128_o<AIMG>(vf[0][1], kb1 + boff);
-            a_read128_o<AIMG + 2048>(vf[1][0], kb0 + boff);
-            a_read128_o<AIMG + 2048>(vf[1][1], kb1 + boff);
+            ds_read128_o<0>(kf[0][0], kb0 + boff);
+            ds_read128_o<0>(kf[0][1], kb1 + boff);
+            ds_read128_o<2048>(kf[1][0], kb0 + boff);
+            ds_read128_o<2048>(kf[1][1], kb1 + boff);
+            ds_read128_o<AIMG>(vf[0][0], kb0 + boff);            // (the V image follows the K image)
+            ds_read128_o<AIMG>(vf[0][1], kb1 + boff);
+            ds_read128_o<AIMG + 2048>(vf[1][0], kb0 + boff);
+            ds_read128_o<AIMG + 2048>(vf[1][1], kb1 + boff);
             bf16x4 kt[4][2];                                    // K^T fragments (transposed reads) for dQ^T += K^T dS^T
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
-                a_read_tr_o<0>(kt[dt][0], tb[dt] + boff);
-                a_read_tr_o<2048>(kt[dt][1], tb[dt] + boff);
+                ds_read_tr_o<0>(kt[dt][0], tb[dt] + boff);
+                ds_read_tr_o<2048>(kt[dt][1], tb[dt] + boff);
             }
             a_wait_lds();
             float ds[2][4];
@@ -357,10 +335,10 @@ __global__ __launch_bounds__(64 * AWAVES) void battn_bwd_dq_kernel(const BAttn p
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
             ushort4 v;
-            v.x = abf(dq[dt][0]); v.y = abf(dq[dt][1]); v.z = abf(dq[dt][2]); v.w = abf(dq[dt][3]);
+            v.x = f2bf(dq[dt][0]); v.y = f2bf(dq[dt][1]); v.z = f2bf(dq[dt][2]); v.w = f2bf(dq[dt][3]);
             if (q < T) *reinterpret_cast<ushort4*>(op + 16 * dt) = v;
-            stored[dt][0] = q < T ? afl(v.x) : 0.f; stored[dt][1] = q < T ? afl(v.y) : 0.f;
-            stored[dt][2] = q < T ? afl(v.z) : 0.f; stored[dt][3] = q < T ? afl(v.w) : 0.f;
+            stored[dt][0] = q < T ? bf2f(v.x) : 0.f; stored[dt][1] = q < T ? bf2f(v.y) : 0.f;
+            stored[dt][2] = q < T ? bf2f(v.z) : 0.f; stored[dt][3] = q < T ? bf2f(v.w) : 0.f;
         }
         if (p.colpart) add_tile_colsum(stored, cst + wave * 64, l15, g);   // sums of the values as stored
     }
@@ -411,14 +389,14 @@ __global__ __launch_bounds__(64 * AWAVES) void battn_bwd_dkv_kernel(const BAttn 
         for (int j = 0; j < nblk; ++j) {                        // 32 queries per step
             const unsigned boff = (unsigned)j * 4096u;
             bf16x8 qf[2][2], df[2][2];
-            a_read128_o<0>(qf[0][0], qb0 + boff);
-            a_read128_o<0>(qf[0][1], qb1 + boff);
-            a_read128_o<2048>(qf[1][0], qb0 + boff);
-            a_read128_o<2048>(qf[1][1], qb1 + boff);
-            a_read128_o<AIMG>(df[0][0], qb0 + boff);
-            a_read128_o<AIMG>(df[0][1], qb1 + boff);
-            a_read128_o<AIMG + 2048>(df[1][0], qb0 + boff);
-            a_read128_o<AIMG + 2048>(df[1][1], qb1 + boff);
+            ds_read128_o<0>(qf[0][0], qb0 + boff);
+            ds_read128_o<0>(qf[0][1], qb1 + boff);
+            ds_read128_o<2048>(qf[1][0], qb0 + boff);
+            ds_read128_o<2048>(qf[1][1], qb1 + boff);
+            ds_read128_o<AIMG>(df[0][0], qb0 + boff);
+            ds_read128_o<AIMG>(df[0][1], qb1 + boff);
+            ds_read128_o<AIMG + 2048>(df[1][0], qb0 + boff);
+            ds_read128_o<AIMG + 2048>(df[1][1], qb1 + boff);
             a_wait_lds();
             float pr[2][4], ds[2][4];
 #pragma unroll
@@ -446,10 +424,10 @@ __global__ __launch_bounds__(64 * AWAVES) void battn_bwd_dkv_kernel(const BAttn 
                 bf16x4 qT[2][2], dT[2][2];
 #pragma unroll
                 for (int d2 = 0; d2 < 2; ++d2) {
-                    a_read_tr_o<0>(qT[d2][0], tb[2 * half + d2] + boff);
-                    a_read_tr_o<2048>(qT[d2][1], tb[2 * half + d2] + boff);
-                    a_read_tr_o<AIMG>(dT[d2][0], tb[2 * half + d2] + boff);
-                    a_read_tr_o<AIMG + 2048>(dT[d2][1], tb[2 * half + d2] + boff);
+                    ds_read_tr_o<0>(qT[d2][0], tb[2 * half + d2] + boff);
+                    ds_read_tr_o<2048>(qT[d2][1], tb[2 * half + d2] + boff);
+                    ds_read_tr_o<AIMG>(dT[d2][0], tb[2 * half + d2] + boff);
+                    ds_read_tr_o<AIMG + 2048>(dT[d2][1], tb[2 * half + d2] + boff);
                 }
                 a_wait_lds();
 #pragma unroll
@@ -469,19 +447,19 @@ __global__ __launch_bounds__(64 * AWAVES) void battn_bwd_dkv_kernel(const BAttn 
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
             ushort4 a;
-            a.x = abf(dk[dt][0]); a.y = abf(dk[dt][1]); a.z = abf(dk[dt][2]); a.w = abf(dk[dt][3]);
+            a.x = f2bf(dk[dt][0]); a.y = f2bf(dk[dt][1]); a.z = f2bf(dk[dt][2]); a.w = f2bf(dk[dt][3]);
             if (live) *reinterpret_cast<ushort4*>(op + E + 16 * dt) = a;
-            stored[dt][0] = live ? afl(a.x) : 0.f; stored[dt][1] = live ? afl(a.y) : 0.f;
-            stored[dt][2] = live ? afl(a.z) : 0.f; stored[dt][3] = live ? afl(a.w) : 0.f;
+            stored[dt][0] = live ? bf2f(a.x) : 0.f; stored[dt][1] = live ? bf2f(a.y) : 0.f;
+            stored[dt][2] = live ? bf2f(a.z) : 0.f; stored[dt][3] = live ? bf2f(a.w) : 0.f;
         }
         if (p.colpart) add_tile_colsum(stored, cst + wave * 64, l15, g);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
             ushort4 c;
-            c.x = abf(dv[dt][0]); c.y = abf(dv[dt][1]); c.z = abf(dv[dt][2]); c.w = abf(dv[dt][3]);
+            c.x = f2bf(dv[dt][0]); c.y = f2bf(dv[dt][1]); c.z = f2bf(dv[dt][2]); c.w = f2bf(dv[dt][3]);
             if (live) *reinterpret_cast<ushort4*>(op + 2 * E + 16 * dt) = c;
-            stored[dt][0] = live ? afl(c.x) : 0.f; stored[dt][1] = live ? afl(c.y) : 0.f;
-            stored[dt][2] = live ? afl(c.z) : 0.f; stored[dt][3] = live ? afl(c.w) : 0.f;
+            stored[dt][0] = live ? bf2f(c.x) : 0.f; stored[dt][1] = live ? bf2f(c.y) : 0.f;
+            stored[dt][2] = live ? bf2f(c.z) : 0.f; stored[dt][3] = live ? bf2f(c.w) : 0.f;
         }
         if (p.colpart) add_tile_colsum(stored, cst + AWAVES * 64 + wave * 64, l15, g);
     }
@@ -489,35 +467,6 @@ __global__ __launch_bounds__(64 * AWAVES) void battn_bwd_dkv_kernel(const BAttn 
         __syncthreads();
         publish_colsum(cst, p.colpart + (int64_t)b * 3 * E + E + h * AHD);
         publish_colsum(cst + AWAVES * 64, p.colpart + (int64_t)b * 3 * E + 2 * E + h * AHD);
-    }
-}
-
-// out[n] = sum over the batch of part[b][n]: 64 columns x 16 sample groups per workgroup (group rg sums samples rg, rg + 16, ...: eight
-// independent loads per wait), the group sums combined through LDS in a fixed order.  (One thread per column walked all 512 samples:
-// 64 dependent round trips on nine workgroups, 40 us per launch.)
-__global__ __launch_bounds__(1024) void battn_colsum_finish_kernel(const float* __restrict__ part, int nparts, int N, float* __restrict__ out) {
-    __shared__ float red[16][64];
-    const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const int n = blockIdx.x * 64 + cl;
-    float s = 0.f;
-    if (n < N) {
-        const int mine = (nparts - rg + 15) / 16;
-        for (int k0 = 0; k0 < mine; k0 += 8) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = part[(int64_t)(rg + 16 * min(k0 + j, mine - 1)) * N + n];
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (k0 + j < mine) s += v[j];
-        }
-    }
-    red[rg][cl] = s;
-    __syncthreads();
-    if (rg == 0 && n < N) {
-        float t = 0.f;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) t += red[g][cl];
-        out[n] = t;
     }
 }
 
@@ -535,7 +484,7 @@ using namespace msn;
 extern "C" int msn_attention_bf16_fwd(const void* qkv, int64_t ld, int B, int H, int T, float scale, void* out, int64_t ldo,
                                       float* lse, msn_stream_t stream) {
     if (int rc = check_battn("msn_attention_bf16_fwd", B, H, T, ld, ldo)) return rc;
-    MSN_REQUIRE(qkv && out && lse && (reinterpret_cast<uintptr_t>(qkv) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0,
+    MSN_REQUIRE(qkv && out && lse && aligned16(qkv) && (reinterpret_cast<uintptr_t>(out) & 7) == 0,
                 "msn_attention_bf16_fwd: null / misaligned pointer");
     BAttn a = {};
     a.qkv = static_cast<const u16*>(qkv); a.ld = ld; a.out = static_cast<u16*>(out); a.ldo = ldo; a.lse = lse;
@@ -552,8 +501,7 @@ extern "C" int msn_attention_bf16_bwd(const void* qkv, int64_t ld, const void* o
                                       float* colsum_out, float* colsum_ws, msn_stream_t stream) {
     if (int rc = check_battn("msn_attention_bf16_bwd", B, H, T, ld, ldo)) return rc;
     MSN_REQUIRE(qkv && out && dout && lse && dqkv && delta && ldd >= H * AHD && ldd % 8 == 0 &&
-                    (reinterpret_cast<uintptr_t>(qkv) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(dout) & 15) == 0 && (reinterpret_cast<uintptr_t>(dqkv) & 7) == 0,
+                    aligned16(qkv, out, dout) && (reinterpret_cast<uintptr_t>(dqkv) & 7) == 0,
                 "msn_attention_bf16_bwd: null / misaligned pointer");
     BAttn a = {};
     a.qkv = static_cast<const u16*>(qkv); a.ld = ld; a.out = const_cast<u16*>(static_cast<const u16*>(out)); a.ldo = ldo;
@@ -566,10 +514,6 @@ extern "C" int msn_attention_bf16_bwd(const void* qkv, int64_t ld, const void* o
     MSN_LAUNCH_CHECK();
     hipLaunchKernelGGL(battn_bwd_dkv_kernel, dim3((unsigned)(B * H)), dim3(64 * AWAVES), 0, st, a);
     MSN_LAUNCH_CHECK();
-    if (colsum_out) {
-        hipLaunchKernelGGL(battn_colsum_finish_kernel, dim3((unsigned)cdiv(3 * H * AHD, 64)), dim3(1024), 0, st, colsum_ws, B,
-                           3 * H * AHD, colsum_out);
-        MSN_LAUNCH_CHECK();
-    }
+    if (colsum_out) return colsum16_finish(colsum_ws, B, 3 * H * AHD, colsum_out, st);    // fixed-order sum over the samples
     return MSN_OK;
 }

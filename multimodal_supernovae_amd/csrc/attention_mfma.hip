@@ -26,7 +26,6 @@
 
 namespace msn {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr float kFill = -1e7f;  // ref transformer_utils.py:77
 
 // (struct MAttn: attention_args.h)
@@ -225,11 +224,6 @@ __device__ __forceinline__ float wave_dot(const float* a, const float* b, int la
 }
 constexpr int kTailScratch = 384;   // floats of LDS behind the images: 2 broadcast rows (64 each) + 2 weight vectors (128)
 
-__device__ __forceinline__ unsigned short bf16_rne_bits(float f) {
-    const __bf16 b = (__bf16)f;
-    return *reinterpret_cast<const unsigned short*>(&b);
-}
-
 // The output tile of one (sample, head) -- Tq rows x hd columns in LDS, row stride HD + 4 -- as planes in the blocked layout of
 // msn_plane_split: a thread takes 8 columns of one row (16 bytes of one plane image), consecutive threads consecutive 16-byte
 // chunks of ONE image, so a wave's store is a contiguous run of it (the form of the one-pass backward's dqkv output).  Rows of a
@@ -252,7 +246,7 @@ __device__ __forceinline__ void planes_from_tile(const MAttn& p, const float* ti
             unsigned w[4];
 #pragma unroll
             for (int x = 0; x < 4; ++x) {
-                const unsigned short lo = bf16_rne_bits(v[2 * x]), hi = bf16_rne_bits(v[2 * x + 1]);
+                const unsigned short lo = f2bf(v[2 * x]), hi = f2bf(v[2 * x + 1]);
                 v[2 * x] -= __uint_as_float((unsigned)lo << 16);          // exact
                 v[2 * x + 1] -= __uint_as_float((unsigned)hi << 16);
                 w[x] = lo | ((unsigned)hi << 16);
@@ -1136,7 +1130,7 @@ __global__ __launch_bounds__(512) void mattn_bwd_fused_kernel(const MAttn p, con
                     unsigned w[4];
 #pragma unroll
                     for (int x = 0; x < 4; ++x) {
-                        const unsigned short lo = bf16_rne_bits(v[2 * x]), hi = bf16_rne_bits(v[2 * x + 1]);
+                        const unsigned short lo = f2bf(v[2 * x]), hi = f2bf(v[2 * x + 1]);
                         v[2 * x] -= __uint_as_float((unsigned)lo << 16);          // exact
                         v[2 * x + 1] -= __uint_as_float((unsigned)hi << 16);
                         w[x] = lo | ((unsigned)hi << 16);
@@ -1487,7 +1481,7 @@ bool mattn_applicable(const MAttn& a, bool shared_q) {
         if (v % 4 != 0) return false;
     const void* ptrs[] = {a.q, a.k, a.v};
     for (const void* ptr : ptrs)
-        if (reinterpret_cast<uintptr_t>(ptr) & 15) return false;
+        if (!aligned16(ptr)) return false;
     return true;
 }
 
@@ -1549,7 +1543,7 @@ static size_t fused_lds(const MAttn& a, bool tail) {
 bool mattn_fused_applicable(const MAttn& a) {
     if (!mattn_applicable(a) || a.Tq != a.Tk || a.Tk > 128 || a.hd > 64 || a.hd % 4 != 0) return false;
     const int64_t al[] = {a.ldd, a.d_bs, a.ldo, a.o_bs};
-    bool ok = ((reinterpret_cast<uintptr_t>(a.dout) | reinterpret_cast<uintptr_t>(a.o)) & 15) == 0;
+    bool ok = aligned16(a.dout, a.o);
     for (int64_t v : al) ok = ok && (v % 4 == 0);
     return ok && fused_lds(a, use_tail(a)) <= 160 * 1024;
 }
@@ -1594,7 +1588,7 @@ int mattn_backward(const MAttn& a0, hipStream_t st) {
     const int TPk = (a.Tk + 15) / 16 * 16, TPq = (a.Tq + 15) / 16 * 16;
     int rc;
     const int64_t al[] = {a.ldd, a.d_bs, a.ldo, a.o_bs};
-    bool ok = ((reinterpret_cast<uintptr_t>(a.dout) | reinterpret_cast<uintptr_t>(a.o)) & 15) == 0;
+    bool ok = aligned16(a.dout, a.o);
     for (int64_t v : al) ok = ok && (v % 4 == 0);
     if (!ok) {
         set_error("attention backward: out / dout must be 16-byte aligned with strides %% 4 == 0");
@@ -1653,7 +1647,7 @@ extern "C" int msn_attention_fwd_planes(const float* qkv, int64_t ldqkv, const u
     MSN_REQUIRE(head_dim % 16 == 0 && head_dim <= 64, "msn_attention_fwd_planes: head width %d (16, 32, 48 or 64)", head_dim);
     const int e = H * head_dim;
     MSN_REQUIRE(ldqkv >= 3 * (int64_t)e && ldo >= e, "msn_attention_fwd_planes: row strides shorter than the rows");
-    MSN_REQUIRE((reinterpret_cast<uintptr_t>(out_planes) & 15) == 0, "msn_attention_fwd_planes: the plane matrix must be 16-byte aligned");
+    MSN_REQUIRE(aligned16(out_planes), "msn_attention_fwd_planes: the plane matrix must be 16-byte aligned");
     MAttn m = {};
     m.q = qkv; m.k = qkv + e; m.v = qkv + 2 * e; m.out = out;
     m.mask = key_mask; m.lse = lse;
@@ -1694,7 +1688,7 @@ extern "C" int msn_attention_bwd_planes(const float* qkv, int64_t ldqkv, const u
     MSN_REQUIRE(head_dim % 16 == 0 && head_dim <= 64, "msn_attention_bwd_planes: head width %d (16, 32, 48 or 64)", head_dim);
     const int e = H * head_dim;
     MSN_REQUIRE(ldqkv >= 3 * (int64_t)e && ldo >= e && ldd >= e, "msn_attention_bwd_planes: row strides shorter than the rows");
-    MSN_REQUIRE((reinterpret_cast<uintptr_t>(dqkv_planes) & 15) == 0, "msn_attention_bwd_planes: the plane matrix must be 16-byte aligned");
+    MSN_REQUIRE(aligned16(dqkv_planes), "msn_attention_bwd_planes: the plane matrix must be 16-byte aligned");
     MAttn m = {};
     m.q = qkv; m.k = qkv + e; m.v = qkv + 2 * e; m.o = out; m.dout = dout;
     m.mask = key_mask; m.lse = const_cast<float*>(lse);

@@ -42,39 +42,19 @@
 namespace msn {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 constexpr float kFillP = -1e7f;                 // ref transformer_utils.py:77
 constexpr float kLog2e = 1.4426950408889634f;
-constexpr int PB = 1024;                        // one plane image of a 32-row block: [32 rows][16 bf16]
-constexpr int BLK = 3 * PB;                     // a 32-row block: three planes
+constexpr int BLK = 3 * PBLK;                    // a 32-row block: three planes
 constexpr int CH = 256;                         // streamed rows per LDS chunk
 constexpr int NBK = CH / 32;
 constexpr int UMAX = 2;                         // staging: 16-byte pieces per thread and image in flight
 
-__device__ __forceinline__ float trunc16(float x) { return __uint_as_float(__float_as_uint(x) & 0xffff0000u); }
-// (high half of b) << 16 | (high half of a): two bf16 (truncated) in fragment order
-__device__ __forceinline__ unsigned hi_pack(float a, float b) {
-    return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
-}
-// a, b -> their three planes, packed pairwise; exact: x = x0 + x1 + x2 (each difference is exact in fp32)
-struct Pair3 {
-    unsigned p0, p1, p2;
-};
-// (Written on 2-vectors -- one v_pk_add_f32 per level and pair instead of two v_sub_f32, 9 instead of 11 instructions per pair --
-//  every kernel of this file got SLOWER by 3 - 5 %: r06 log, item 6.  A packed fp32 add is two issue cycles, and its operands
-//  want aligned register pairs.)
-__device__ __forceinline__ Pair3 split2(float a, float b) {
-    const float ra = a - trunc16(a), rb = b - trunc16(b);
-    const float sa = ra - trunc16(ra), sb = rb - trunc16(rb);
-    return Pair3{hi_pack(a, b), hi_pack(ra, rb), hi_pack(sa, sb)};
-}
 struct Planes8 {          // eight values of one lane as three fragments
     u32x4 p0, p1, p2;
 };
@@ -176,8 +156,8 @@ __device__ __forceinline__ HeadFrags head_frags_narrow(const float (&v)[8], int 
 // row fragments of the 16-row tile t of a block, columns 0 .. 7: a_small = [x0 | x1 | x0 | x2], a_big = [x0 | x1 | x0 | x0]
 __device__ __forceinline__ void row_frags_narrow(const unsigned char* blk, int t, int c, int g, bf16x8& a_small, bf16x8& a_big) {
     const unsigned char* p = blk + t * 512 + c * 32;
-    a_small = *reinterpret_cast<const bf16x8*>(p + (g == 1 ? 1 : g == 3 ? 2 : 0) * PB);
-    a_big = *reinterpret_cast<const bf16x8*>(p + (g == 1 ? PB : 0));
+    a_small = *reinterpret_cast<const bf16x8*>(p + (g == 1 ? 1 : g == 3 ? 2 : 0) * PBLK);
+    a_big = *reinterpret_cast<const bf16x8*>(p + (g == 1 ? PBLK : 0));
 }
 __device__ __forceinline__ f32x4 head_product_narrow(const bf16x8& a_small, const bf16x8& a_big, const HeadFrags& b) {
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
@@ -212,11 +192,11 @@ struct StagePair {
         const int off = (r >> 5) * BLK + (r & 31) * 32 + q * 8;
         const Pair3 xa = split2(x.x, x.y), xb = split2(x.z, x.w), ya = split2(y.x, y.y), yb = split2(y.z, y.w);
         *reinterpret_cast<u32x2*>(img0 + off) = u32x2{xa.p0, xb.p0};
-        *reinterpret_cast<u32x2*>(img0 + off + PB) = u32x2{xa.p1, xb.p1};
-        *reinterpret_cast<u32x2*>(img0 + off + 2 * PB) = u32x2{xa.p2, xb.p2};
+        *reinterpret_cast<u32x2*>(img0 + off + PBLK) = u32x2{xa.p1, xb.p1};
+        *reinterpret_cast<u32x2*>(img0 + off + 2 * PBLK) = u32x2{xa.p2, xb.p2};
         *reinterpret_cast<u32x2*>(img1 + off) = u32x2{ya.p0, yb.p0};
-        *reinterpret_cast<u32x2*>(img1 + off + PB) = u32x2{ya.p1, yb.p1};
-        *reinterpret_cast<u32x2*>(img1 + off + 2 * PB) = u32x2{ya.p2, yb.p2};
+        *reinterpret_cast<u32x2*>(img1 + off + PBLK) = u32x2{ya.p1, yb.p1};
+        *reinterpret_cast<u32x2*>(img1 + off + 2 * PBLK) = u32x2{ya.p2, yb.p2};
     }
     // (tid: the thread's index, handed in as an OPAQUE copy per chunk by the callers -- opaque_tid() -- so that the piece indices
     //  derived from it are recomputed per chunk instead of living across the block loop: they were what the allocator spilled)
@@ -244,13 +224,13 @@ __device__ __forceinline__ int opaque_tid() {
 // row fragments (A operand of S / dP) of the 16-row tile t of a block: a01 = [x0 | x1], a02 = [x0 | x2]
 __device__ __forceinline__ void row_frags(const unsigned char* blk, int t, int c, int g, bf16x8& a01, bf16x8& a02) {
     const unsigned char* p = blk + t * 512 + c * 32 + (g & 1) * 16;
-    a01 = *reinterpret_cast<const bf16x8*>(p + (g >> 1) * PB);
-    a02 = *reinterpret_cast<const bf16x8*>(p + (g >> 1) * 2 * PB);
+    a01 = *reinterpret_cast<const bf16x8*>(p + (g >> 1) * PBLK);
+    a02 = *reinterpret_cast<const bf16x8*>(p + (g >> 1) * 2 * PBLK);
 }
 // transposed fragment (A operand of the token products) of plane pl of a block: lane (c, g) gets column c of rows
 // 4 g .. 4 g + 3 (elements 0 - 3) and 16 + 4 g .. + 3 (elements 4 - 7) -- the k order in which the accumulators hold P / dS
 __device__ __forceinline__ bf16x8 tr_frag(const unsigned char* blk, int pl, int c, int g) {
-    const unsigned char* p = blk + pl * PB + (4 * g + (c >> 2)) * 32 + (c & 3) * 8;
+    const unsigned char* p = blk + pl * PBLK + (4 * g + (c >> 2)) * 32 + (c & 3) * 8;
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p));
     const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 16 * 32));
     const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
@@ -731,8 +711,8 @@ __global__ __launch_bounds__(512, 4) void pattn_bwd_fused_kernel(const MAttn p) 
             const Pair3 xa = split2(x.x, x.y), xb = split2(x.z, x.w);
             unsigned char* dst = Kimg + (r >> 5) * BLK + (r & 31) * 32 + q4 * 8;
             *reinterpret_cast<u32x2*>(dst) = u32x2{xa.p0, xb.p0};
-            *reinterpret_cast<u32x2*>(dst + PB) = u32x2{xa.p1, xb.p1};
-            *reinterpret_cast<u32x2*>(dst + 2 * PB) = u32x2{xa.p2, xb.p2};
+            *reinterpret_cast<u32x2*>(dst + PBLK) = u32x2{xa.p1, xb.p1};
+            *reinterpret_cast<u32x2*>(dst + 2 * PBLK) = u32x2{xa.p2, xb.p2};
         }
         f32x4 kbg = {0.f, 0.f, 0.f, 0.f}, ksm = kbg, vbg = kbg, vsm = kbg;
         const int special = __any(liv == 0.f ? 1 : 0);    // this wave owns a key that is not live: the form with the v_min
@@ -940,16 +920,15 @@ bool pattn_applicable(const MAttn& a) {
         if (v % 4 != 0) return false;
     const void* ptrs[] = {a.q, a.k, a.v};
     for (const void* ptr : ptrs)
-        if (reinterpret_cast<uintptr_t>(ptr) & 15) return false;
+        if (!aligned16(ptr)) return false;
     return true;
 }
 bool pattn_forward_aligned(const MAttn& a) {
-    return (reinterpret_cast<uintptr_t>(a.out) & 15) == 0 && a.ldo % 4 == 0 && a.o_bs % 4 == 0;
+    return aligned16(a.out) && a.ldo % 4 == 0 && a.o_bs % 4 == 0;
 }
 bool pattn_backward_aligned(const MAttn& a) {
     const int64_t al[] = {a.ldd, a.d_bs, a.ldo, a.o_bs, a.lddq, a.lddk, a.lddv, a.dq_bs, a.dk_bs, a.dv_bs};
-    bool ok = ((reinterpret_cast<uintptr_t>(a.dout) | reinterpret_cast<uintptr_t>(a.o) | reinterpret_cast<uintptr_t>(a.dq) |
-                reinterpret_cast<uintptr_t>(a.dk) | reinterpret_cast<uintptr_t>(a.dv)) & 15) == 0;
+    bool ok = aligned16(a.dout, a.o, a.dq, a.dk, a.dv);
     for (int64_t v : al) ok = ok && (v % 4 == 0);
     return ok;
 }

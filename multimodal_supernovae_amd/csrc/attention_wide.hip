@@ -27,7 +27,6 @@ namespace msn {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr float kFill = -1e7f;       // ref transformer_utils.py:77
 constexpr int kFT = 2;               // fixed 16-row tiles per workgroup
 constexpr int kDS = 4;               // head-dimension parts
@@ -432,7 +431,7 @@ bool wattn_applicable(const MAttn& a) {
         if (v % 4 != 0) return false;
     const void* ptrs[] = {a.q, a.k, a.v};
     for (const void* ptr : ptrs)
-        if (reinterpret_cast<uintptr_t>(ptr) & 15) return false;
+        if (!aligned16(ptr)) return false;
     return true;
 }
 
@@ -442,7 +441,7 @@ int wattn_forward(const MAttn& a, hipStream_t st) {
 
 int wattn_backward(const MAttn& a, hipStream_t st) {
     const int64_t al[] = {a.ldd, a.d_bs, a.ldo, a.o_bs};
-    bool ok = ((reinterpret_cast<uintptr_t>(a.dout) | reinterpret_cast<uintptr_t>(a.o)) & 15) == 0;
+    bool ok = aligned16(a.dout, a.o);
     for (int64_t v : al) ok = ok && (v % 4 == 0);
     if (!ok) {
         set_error("attention backward: out / dout must be 16-byte aligned with strides %% 4 == 0");

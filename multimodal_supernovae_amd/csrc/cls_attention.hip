@@ -16,7 +16,6 @@
 namespace msn {
 namespace {
 
-typedef unsigned short u16;
 constexpr int HD = 64;          // head width (eight lanes x eight columns)
 constexpr int MAXIT = 32;       // key groups of eight per wave: T <= 256
 
@@ -202,8 +201,6 @@ __global__ __launch_bounds__(256) void cls_attn_bwd_kernel(const ClsArgs p) {
     if (kg == 0) store8<float>(p.dq + (int64_t)b * p.lddq + h * HD + 8 * pt, acc);
 }
 
-bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
-
 }  // namespace
 }  // namespace msn
 
@@ -216,8 +213,7 @@ extern "C" int msn_cls_attention_fwd(const float* q, int64_t ldq, const void* kv
     MSN_REQUIRE(q && kv && out && probs && B > 0 && H > 0, "msn_cls_attention_fwd: empty operand");
     MSN_REQUIRE(msn_cls_attention_supported(T, head_dim), "msn_cls_attention_fwd: head_dim %d (must be 64), T = %d (1 .. 256)", head_dim, T);
     const int e = H * HD, es = kv_bf16 ? 2 : 4;
-    MSN_REQUIRE(ldq >= e && ldo >= e && ldkv >= 2 * e && ldq % 4 == 0 && ldo % 4 == 0 && (ldkv * es) % 16 == 0 && aligned16(q) &&
-                    aligned16(kv) && aligned16(out),
+    MSN_REQUIRE(ldq >= e && ldo >= e && ldkv >= 2 * e && ldq % 4 == 0 && ldo % 4 == 0 && (ldkv * es) % 16 == 0 && aligned16(q, kv, out),
                 "msn_cls_attention_fwd: rows must be 16-byte aligned (ldq %lld, ldkv %lld, ldo %lld)", (long long)ldq, (long long)ldkv,
                 (long long)ldo);
     ClsArgs a = {};
@@ -237,8 +233,7 @@ extern "C" int msn_cls_attention_bwd(const float* q, int64_t ldq, const void* kv
     MSN_REQUIRE(msn_cls_attention_supported(T, head_dim), "msn_cls_attention_bwd: head_dim %d (must be 64), T = %d (1 .. 256)", head_dim, T);
     const int e = H * HD, es = kv_bf16 ? 2 : 4;
     MSN_REQUIRE(ldq >= e && ldo >= e && ldd >= e && lddq >= e && ldkv >= 2 * e && lddkv >= 2 * e && ldq % 4 == 0 && ldo % 4 == 0 &&
-                    ldd % 4 == 0 && lddq % 4 == 0 && (ldkv * es) % 16 == 0 && (lddkv * es) % 16 == 0 && aligned16(q) && aligned16(kv) &&
-                    aligned16(out) && aligned16(dout) && aligned16(dq) && aligned16(dkv),
+                    ldd % 4 == 0 && lddq % 4 == 0 && (ldkv * es) % 16 == 0 && (lddkv * es) % 16 == 0 && aligned16(q, kv, out, dout, dq, dkv),
                 "msn_cls_attention_bwd: rows must be 16-byte aligned");
     ClsArgs a = {};
     a.q = q, a.ldq = ldq, a.kv = kv, a.ldkv = ldkv, a.B = B, a.H = H, a.T = T, a.scale = scale;

@@ -281,7 +281,7 @@ extern "C" int msn_im2col_tap(const float* x, int B, int H, int W, int C, int kh
     ConvGeom g;
     if (int rc = make_geom("msn_im2col_tap", B, H, W, C, kh, kw, sh, sw, ph, pw, &g)) return rc;
     MSN_REQUIRE(x && cols, "msn_im2col_tap: null pointer");
-    MSN_REQUIRE(C % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(cols)) & 15) == 0,
+    MSN_REQUIRE(C % 4 == 0 && aligned16(x, cols),
                 "msn_im2col_tap: needs C %% 4 == 0 and 16-byte aligned tensors");
     hipLaunchKernelGGL(im2col_tap_kernel, dim3(grid_for((int64_t)B * g.OH * g.OW * (C / 4) * kh * kw)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), x, g, cols);
@@ -293,7 +293,7 @@ extern "C" int msn_col2im_tap(const float* dcols, int B, int H, int W, int C, in
     ConvGeom g;
     if (int rc = make_geom("msn_col2im_tap", B, H, W, C, kh, kw, sh, sw, ph, pw, &g)) return rc;
     MSN_REQUIRE(dx && dcols, "msn_col2im_tap: null pointer");
-    MSN_REQUIRE(C % 4 == 0 && ((reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(dcols)) & 15) == 0,
+    MSN_REQUIRE(C % 4 == 0 && aligned16(dx, dcols),
                 "msn_col2im_tap: needs C %% 4 == 0 and 16-byte aligned tensors");
     hipLaunchKernelGGL(col2im_tap_kernel, dim3(grid_for((int64_t)B * H * W * (C / 4))), dim3(256), 0,
                        static_cast<hipStream_t>(stream), dcols, g, dx);
@@ -320,8 +320,7 @@ extern "C" int msn_maxpool2d_fwd(const float* x, int B, int H, int W, int C, int
     ConvGeom g;
     if (int rc = make_geom("msn_maxpool2d_fwd", B, H, W, C, k, k, s, s, p, p, &g)) return rc;
     MSN_REQUIRE(x && y && argmax, "msn_maxpool2d_fwd: null pointer");
-    const bool vec = C % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) |
-                                     reinterpret_cast<uintptr_t>(argmax)) & 15) == 0;
+    const bool vec = C % 4 == 0 && aligned16(x, y, argmax);
     if (vec)
         hipLaunchKernelGGL(maxpool_fwd4_kernel, dim3(grid_for((int64_t)B * g.OH * g.OW * (C / 4))), dim3(256), 0,
                            static_cast<hipStream_t>(stream), x, g, y, argmax);
@@ -336,8 +335,7 @@ extern "C" int msn_maxpool2d_bwd(const float* dy, const int* argmax, int B, int 
     ConvGeom g;
     if (int rc = make_geom("msn_maxpool2d_bwd", B, H, W, C, k, k, s, s, p, p, &g)) return rc;
     MSN_REQUIRE(dy && dx && argmax, "msn_maxpool2d_bwd: null pointer");
-    const bool vec = C % 4 == 0 && ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx) |
-                                     reinterpret_cast<uintptr_t>(argmax)) & 15) == 0;
+    const bool vec = C % 4 == 0 && aligned16(dy, dx, argmax);
     if (vec)
         hipLaunchKernelGGL(maxpool_bwd4_kernel, dim3(grid_for((int64_t)B * H * W * (C / 4))), dim3(256), 0,
                            static_cast<hipStream_t>(stream), dy, argmax, g, dx);

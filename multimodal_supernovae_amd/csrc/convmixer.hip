@@ -108,21 +108,11 @@ __global__ __launch_bounds__(256) void bn_sqdev_kernel(const float* __restrict__
 __device__ __forceinline__ float slab_sum16(const float* __restrict__ part, int64_t stride, int nblocks, int c, int C,
                                             float (*red)[64]) {
     const int cl = threadIdx.x & 63, g = threadIdx.x >> 6;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (c < C) {
-        int b = g;
-        for (; b + 48 < nblocks; b += 64) {
-            s0 += part[(int64_t)b * stride + c];
-            s1 += part[(int64_t)(b + 16) * stride + c];
-            s2 += part[(int64_t)(b + 32) * stride + c];
-            s3 += part[(int64_t)(b + 48) * stride + c];
-        }
-        for (; b < nblocks; b += 16) s0 += part[(int64_t)b * stride + c];
-    }
+    const float s = strided_sum4(c < C, part, stride, c, g, 16, nblocks);
     __syncthreads();
-    red[g][cl] = (s0 + s1) + (s2 + s3);
+    red[g][cl] = s;
     __syncthreads();
-    float t = 0.f;
+    float t = 0.f;                              // (sixteen groups added one after the other; gemm.hip's column sums: four, as a tree)
 #pragma unroll
     for (int k = 0; k < 16; ++k) t += red[k][cl];
     return t;

@@ -32,32 +32,18 @@
 namespace msn {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
-constexpr int PB = 1024;                        // one plane image of a block: [32 rows][16 bf16]
-constexpr int BLK = 3 * PB;                     // a 32 x 16 block: three planes
+constexpr int BLK = 3 * PBLK;                    // a 32 x 16 block: three planes
 constexpr int E = 32;                           // embedding width this file is built for
 constexpr int HID = 4 * E;                      // ref transformer_utils.py:124 (ff_hidden_mult = 4)
 constexpr int WBYTES = (HID / 32) * (E / 16) * BLK;      // a [HID][E] plane matrix: 24 KB
 constexpr int NCH = HID / 32;                   // hidden chunks of 32
 
-__device__ __forceinline__ float trunc16(float x) { return __uint_as_float(__float_as_uint(x) & 0xffff0000u); }
-__device__ __forceinline__ unsigned hi_pack(float a, float b) {
-    return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
-}
-struct Pair3 { unsigned p0, p1, p2; };
-// a, b -> their three planes, packed pairwise (truncation split: every residual is exact in fp32)
-__device__ __forceinline__ Pair3 split2(float a, float b) {
-    const float ra = a - trunc16(a), rb = b - trunc16(b);
-    const float sa = ra - trunc16(ra), sb = rb - trunc16(rb);
-    return Pair3{hi_pack(a, b), hi_pack(ra, rb), hi_pack(sa, sb)};
-}
 struct Planes8 { u32x4 p0, p1, p2; };           // eight values of one lane as three fragments
 __device__ __forceinline__ Planes8 split8(const float (&v)[8]) {
     Planes8 o;
@@ -87,7 +73,7 @@ __device__ __forceinline__ void plane_product(const bf16x8 (&a)[3], const bf16x8
 __device__ __forceinline__ void row_frags32(const unsigned char* mat, int rb, int t, int c, int g, bf16x8 (&f)[3]) {
     const unsigned char* p = mat + (rb * 2 + (g >> 1)) * BLK + (16 * t + c) * 32 + (g & 1) * 16;
 #pragma unroll
-    for (int pl = 0; pl < 3; ++pl) f[pl] = *reinterpret_cast<const bf16x8*>(p + pl * PB);
+    for (int pl = 0; pl < 3; ++pl) f[pl] = *reinterpret_cast<const bf16x8*>(p + pl * PBLK);
 }
 // Transposed fragments of ONE block (32 rows x 16 columns): lane (c, g) gets column c of rows 4 g .. + 3 (elements 0 - 3) and
 // 16 + 4 g .. + 3 (elements 4 - 7): k = the block's 32 rows, in the order in which accumulators hold two 16-row tiles
@@ -95,8 +81,8 @@ __device__ __forceinline__ void tr_frags(const unsigned char* blk, int c, int g,
     const unsigned char* p = blk + (4 * g + (c >> 2)) * 32 + (c & 3) * 8;
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl) {
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + pl * PB));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + pl * PB + 16 * 32));
+        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + pl * PBLK));
+        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + pl * PBLK + 16 * 32));
         const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
         f[pl] = __builtin_bit_cast(bf16x8, v);
     }
@@ -257,11 +243,11 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_kernel(const FfnArgs p) {
             const int off = (q >> 2) * BLK + r * 32 + (q & 3) * 8;
             const Pair3 da = split2(d.x, d.y), db = split2(d.z, d.w), xa = split2(x.x, x.y), xb = split2(x.z, x.w);
             *reinterpret_cast<u32x2*>(DZ + off) = u32x2{da.p0, db.p0};
-            *reinterpret_cast<u32x2*>(DZ + off + PB) = u32x2{da.p1, db.p1};
-            *reinterpret_cast<u32x2*>(DZ + off + 2 * PB) = u32x2{da.p2, db.p2};
+            *reinterpret_cast<u32x2*>(DZ + off + PBLK) = u32x2{da.p1, db.p1};
+            *reinterpret_cast<u32x2*>(DZ + off + 2 * PBLK) = u32x2{da.p2, db.p2};
             *reinterpret_cast<u32x2*>(XI + off) = u32x2{xa.p0, xb.p0};
-            *reinterpret_cast<u32x2*>(XI + off + PB) = u32x2{xa.p1, xb.p1};
-            *reinterpret_cast<u32x2*>(XI + off + 2 * PB) = u32x2{xa.p2, xb.p2};
+            *reinterpret_cast<u32x2*>(XI + off + PBLK) = u32x2{xa.p1, xb.p1};
+            *reinterpret_cast<u32x2*>(XI + off + 2 * PBLK) = u32x2{xa.p2, xb.p2};
         }
         request(it + gridDim.x);
         __syncthreads();
@@ -321,11 +307,11 @@ __global__ __launch_bounds__(512, 2) void ffn_bwd_kernel(const FfnArgs p) {
             for (int nt = 0; nt < 2; ++nt) {    // token 16 nt + c; hidden 4 g .. + 3 -> column block 0, 16 + 4 g .. + 3 -> column block 1
                 unsigned char* d = patch + (16 * nt + c) * 32 + 8 * g;
                 *reinterpret_cast<u32x2*>(d) = u32x2{v[nt].p0[0], v[nt].p0[1]};
-                *reinterpret_cast<u32x2*>(d + PB) = u32x2{v[nt].p1[0], v[nt].p1[1]};
-                *reinterpret_cast<u32x2*>(d + 2 * PB) = u32x2{v[nt].p2[0], v[nt].p2[1]};
+                *reinterpret_cast<u32x2*>(d + PBLK) = u32x2{v[nt].p1[0], v[nt].p1[1]};
+                *reinterpret_cast<u32x2*>(d + 2 * PBLK) = u32x2{v[nt].p2[0], v[nt].p2[1]};
                 *reinterpret_cast<u32x2*>(d + BLK) = u32x2{v[nt].p0[2], v[nt].p0[3]};
-                *reinterpret_cast<u32x2*>(d + BLK + PB) = u32x2{v[nt].p1[2], v[nt].p1[3]};
-                *reinterpret_cast<u32x2*>(d + BLK + 2 * PB) = u32x2{v[nt].p2[2], v[nt].p2[3]};
+                *reinterpret_cast<u32x2*>(d + BLK + PBLK) = u32x2{v[nt].p1[2], v[nt].p1[3]};
+                *reinterpret_cast<u32x2*>(d + BLK + 2 * PBLK) = u32x2{v[nt].p2[2], v[nt].p2[3]};
             }
         };
         auto wgrad = [&](const unsigned char* other, f32x4 (&accb)[2][2], f32x4 (&accs)[2][2]) {
@@ -455,8 +441,6 @@ int launch_lds(K kernel, int grid, size_t lds, hipStream_t st, const FfnArgs& a,
     return MSN_OK;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 }  // namespace msn
 
@@ -468,7 +452,7 @@ extern "C" int msn_ffn_fwd(const float* x, int64_t ldx, int64_t M, int emb, int 
                            const float* c1, const float* c2, float* z, int64_t ldz, msn_stream_t stream) {
     MSN_REQUIRE(msn_ffn_supported(M, emb, hidden), "msn_ffn_fwd: emb %d / hidden %d (built for %d / %d)", emb, hidden, E, HID);
     MSN_REQUIRE(x && w1_planes && w2t_planes && c1 && c2 && z, "msn_ffn_fwd: null pointer");
-    MSN_REQUIRE(aligned16(x) && aligned16(z) && aligned16(w1_planes) && aligned16(w2t_planes) && ldx % 4 == 0 && ldz % 4 == 0 &&
+    MSN_REQUIRE(aligned16(x, z, w1_planes, w2t_planes) && ldx % 4 == 0 && ldz % 4 == 0 &&
                     ldx >= E && ldz >= E, "msn_ffn_fwd: rows must be 16-byte aligned");
     FfnArgs a = {};
     a.x = x; a.ldx = ldx; a.w1p = static_cast<const unsigned char*>(w1_planes); a.w2tp = static_cast<const unsigned char*>(w2t_planes);
@@ -487,7 +471,7 @@ extern "C" int msn_ffn_bwd(const float* x, int64_t ldx, const float* dz, int64_t
                            float* dc1, float* dw2, float* dc2, void* ws, size_t ws_bytes, msn_stream_t stream) {
     MSN_REQUIRE(msn_ffn_supported(M, emb, hidden), "msn_ffn_bwd: emb %d / hidden %d (built for %d / %d)", emb, hidden, E, HID);
     MSN_REQUIRE(x && dz && w1_planes && w2t_planes && c1 && dx && dw1 && dc1 && dw2 && dc2, "msn_ffn_bwd: null pointer");
-    MSN_REQUIRE(aligned16(x) && aligned16(dz) && aligned16(dx) && aligned16(w1_planes) && aligned16(w2t_planes) && ldx % 4 == 0 &&
+    MSN_REQUIRE(aligned16(x, dz, dx, w1_planes, w2t_planes) && ldx % 4 == 0 &&
                     lddz % 4 == 0 && lddx % 4 == 0 && ldx >= E && lddz >= E && lddx >= E, "msn_ffn_bwd: rows must be 16-byte aligned");
     const size_t need = msn_ffn_bwd_workspace_bytes(M, emb, hidden);
     MSN_REQUIRE(ws && ws_bytes >= need && aligned16(ws), "msn_ffn_bwd: workspace %zu < %zu bytes", ws_bytes, need);

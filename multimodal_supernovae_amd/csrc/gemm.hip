@@ -443,20 +443,9 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
     __shared__ float red[CS_RG][CS_COLS];
     const int cl = threadIdx.x % CS_COLS, rg = threadIdx.x / CS_COLS;
     const int64_t n = (int64_t)blockIdx.y * CS_COLS + cl;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (n < N) {
-        const int64_t stride = (int64_t)gridDim.x * CS_RG;
-        int64_t r = (int64_t)blockIdx.x * CS_RG + rg;
-        for (; r + 3 * stride < M; r += 4 * stride) {
-            s0 += X[r * ldx + n];
-            s1 += X[(r + stride) * ldx + n];
-            s2 += X[(r + 2 * stride) * ldx + n];
-            s3 += X[(r + 3 * stride) * ldx + n];
-        }
-        for (; r < M; r += stride) s0 += X[r * ldx + n];
-    }
-    red[rg][cl] = (s0 + s1) + (s2 + s3);
+    red[rg][cl] = strided_sum4<int64_t>(n < N, X, ldx, n, (int64_t)blockIdx.x * CS_RG + rg, (int64_t)gridDim.x * CS_RG, M);
     __syncthreads();
+    // (the four row groups combine as a tree here and in colsum_final_kernel; the 16-group finishes add theirs one after the other)
     if (rg == 0 && n < N) part[(int64_t)blockIdx.x * N + n] = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
 }
 __global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restrict__ part, int64_t slabs, int64_t N,
@@ -464,18 +453,7 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restri
     __shared__ float red[CS_RG][CS_COLS];
     const int cl = threadIdx.x % CS_COLS, rg = threadIdx.x / CS_COLS;
     const int64_t n = (int64_t)blockIdx.x * CS_COLS + cl;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (n < N) {
-        int64_t k = rg;
-        for (; k + 3 * CS_RG < slabs; k += 4 * CS_RG) {   // four slabs in flight per thread
-            s0 += part[k * N + n];
-            s1 += part[(k + CS_RG) * N + n];
-            s2 += part[(k + 2 * CS_RG) * N + n];
-            s3 += part[(k + 3 * CS_RG) * N + n];
-        }
-        for (; k < slabs; k += CS_RG) s0 += part[k * N + n];
-    }
-    red[rg][cl] = (s0 + s1) + (s2 + s3);
+    red[rg][cl] = strided_sum4<int64_t>(n < N, part, N, n, rg, CS_RG, slabs);   // four slabs in flight per thread
     __syncthreads();
     if (rg == 0 && n < N) out[n] = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
 }
@@ -744,7 +722,7 @@ static int sgemm_impl(int opA, int opB, int64_t M, int64_t N, int64_t K, const f
         const int64_t a_ext0 = opA == MSN_OP_T ? M : K, b_ext0 = opB == MSN_OP_N ? N : K;
         const bool dma_pre = (g_gemm_variant != 0 || conv != 0) && K % BK == 0 && (lda % 4 == 0) && (ldb % 4 == 0) && (a_ext0 % 4 == 0) &&
                              (b_ext0 % 4 == 0) && a_ext0 >= 4 && b_ext0 >= 4 &&
-                             ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0;
+                             aligned16(A, B);
         if (!dma_pre && conv == 0 && bm != 128) bm = 128;
     }
     a.colsum = nullptr;
@@ -781,14 +759,14 @@ static int sgemm_impl(int opA, int opB, int64_t M, int64_t N, int64_t K, const f
     // bf16 matrix-core paths need 16-byte loads on the K-contiguous operands; otherwise stay on fp32
     bool bf16_ok = precision != MSN_PREC_F32;
     if (bf16_ok && opA == MSN_OP_N)
-        bf16_ok = (lda % 4 == 0) && (K % 4 == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0);
+        bf16_ok = (lda % 4 == 0) && (K % 4 == 0) && aligned16(A);
     if (bf16_ok && opB == MSN_OP_T)
-        bf16_ok = (ldb % 4 == 0) && (K % 4 == 0) && ((reinterpret_cast<uintptr_t>(B) & 15) == 0);
+        bf16_ok = (ldb % 4 == 0) && (K % 4 == 0) && aligned16(B);
     // LDS-DMA kernels: every operand 16-B aligned with ld % 4 == 0 and extents % 4 == 0, whole K-steps only
     const int64_t a_ext = opA == MSN_OP_T ? M : K, b_ext = opB == MSN_OP_N ? N : K;
     const bool dma_ok = (g_gemm_variant != 0 || conv != 0) && bn >= 32 && K % BK == 0 && kps % BK == 0 && (lda % 4 == 0) && (ldb % 4 == 0) &&
                         (a_ext % 4 == 0) && (b_ext % 4 == 0) && a_ext >= 4 && b_ext >= 4 &&
-                        ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0;
+                        aligned16(A, B);
     const bool fuse_colsum = colsum_out && !bf16_ok && dma_ok && opA == MSN_OP_T && opB == MSN_OP_N;
     if (fuse_colsum) {   // slabs of partial sums behind the product's own split-K slabs, or the result itself
         if (splits > 1) {
@@ -830,7 +808,7 @@ static int sgemm_impl(int opA, int opB, int64_t M, int64_t N, int64_t K, const f
     if (splits > 1) {
         const int64_t total = M * N;
         // 16-byte path: a group of 4 outputs never straddles a row (N % 4 == 0) and C rows stay 16-byte aligned
-        const bool v4 = N % 4 == 0 && ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0;
+        const bool v4 = N % 4 == 0 && ldc % 4 == 0 && aligned16(C);
         const int cs_blocks = fuse_colsum ? (int)cdiv(M, 64) : 0;   // the column-sum slabs ride in the same launch
         const bool deep = splits >= 64;   // many slabs: 16 thread groups share them
         const int blocks = (int)std::min<int64_t>(cdiv(total, v4 ? 256 : 64), 4096);

@@ -22,9 +22,6 @@
 
 namespace msn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int BBK = 32;   // K-step
 constexpr int BRS = 40;   // LDS row stride in bf16 elements
 

@@ -29,9 +29,6 @@
 
 namespace msn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) const void gptr_t;
@@ -43,11 +40,6 @@ constexpr int OPER_BYTES = BT * BKS * 2;      // one operand of one K-tile: 32 K
 constexpr int STAGE_BYTES = 2 * OPER_BYTES;   // 64 KB
 constexpr int EPI_B_NONE = 0, EPI_B_GELU = 1, EPI_B_GELU_BWD = 2, EPI_B_ADD = 3;
 
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((unsigned)v << 16); }
-__device__ __forceinline__ u16 f2bf(float f) {          // round to nearest even; NaN stays NaN (plain cast)
-    const __bf16 b = (__bf16)f;
-    return *reinterpret_cast<const u16*>(&b);
-}
 
 // GELU (erf form) and its derivative for bf16 outputs, without transcendentals: Phi(x) - 1/2 and gelu'(x) - 1/2 are odd
 // functions; on |x| <= 4 (clamped: Phi(4) = 1 - 3e-5) they are evaluated as odd polynomials in t = x / 4 of degree 15 / 17
@@ -97,10 +89,6 @@ struct BgemmArgs {
 // 16-byte slot in the 256-byte bank row = 8 (r & 1) + (c ^ swz(r)); even rows land on 8 distinct slots of the lower
 // half, odd rows on 8 distinct slots of the upper half -> conflict-free.
 __device__ __forceinline__ int swz(int r) { return (r >> 1) & 7; }
-
-__device__ __forceinline__ void ds_read128(bf16x8& dst, unsigned addr) {
-    asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr));
-}
 
 #ifndef MSN_BGEMM_STAGGER
 #define MSN_BGEMM_STAGGER 0
@@ -512,11 +500,6 @@ __global__ __launch_bounds__(512, 2) void bgemm_nt_kernel(const BgemmArgs p) {
 // is XORed with tsw(r) = (r & 3) | ((r >> 3) & 1) << 2, which is distinct over those eight rows -> conflict-free.
 __device__ __forceinline__ int tsw(int r) { return (r & 3) | (((r >> 3) & 1) << 2); }
 
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void ds_read_tr(bf16x4& dst, unsigned addr) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(dst) : "v"(addr));
-}
-
 __global__ __launch_bounds__(512, 2) void bgemm_tn_kernel(const BgemmArgs p) {
     __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * STAGE_BYTES];
     const int lane = threadIdx.x & 63;
@@ -675,23 +658,6 @@ __global__ __launch_bounds__(512, 2) void bgemm_tn_kernel(const BgemmArgs p) {
     }
 }
 
-// C[i] = sum_s slab[s][i] in split order (float4 per thread, eight independent loads per wait)
-__global__ void bgemm_slab_sum_kernel(const float* __restrict__ slabs, int splits, int64_t n4, int K4, int64_t ldc4,
-                                      float* __restrict__ C) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int k0 = 0; k0 < splits; k0 += 8) {
-            float4 v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = reinterpret_cast<const float4*>(slabs)[(int64_t)std::min(k0 + j, splits - 1) * n4 + i];
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (k0 + j < splits) { s.x += v[j].x; s.y += v[j].y; s.z += v[j].z; s.w += v[j].w; }
-        }
-        reinterpret_cast<float4*>(C)[(i / K4) * ldc4 + (i % K4)] = s;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------- casts, sums
 // y = bf16(x), 8 elements per thread
 __global__ void cast_bf16_kernel(const float* __restrict__ x, int64_t n8, u16* __restrict__ y) {
@@ -780,38 +746,6 @@ __global__ __launch_bounds__(256) void bcolsum_part_kernel(const u16* __restrict
         }
     }
 }
-// out[n] = sum_k part[k][n]: 64 columns x 16 row groups per workgroup (group rg sums the parts k = rg, rg + 16, ... eight independent
-// loads per wait), the sixteen group sums combined through LDS in a fixed order.  (Four groups of 256 threads took 30 us for the
-// 1 576 x 3 072 partials of a GELU' launch -- 50 dependent round trips per thread on 48 workgroups.)
-__global__ __launch_bounds__(1024) void bcolsum_finish_kernel(const float* __restrict__ part, int nparts, int N,
-                                                              float* __restrict__ out) {
-    __shared__ float red[16][64];
-    const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const int n = blockIdx.x * 64 + cl;
-    float s = 0.f;
-    if (n < N) {
-        const int mine = (nparts - rg + 15) / 16;               // parts this group owns
-        for (int k0 = 0; k0 < mine; k0 += 8) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = part[(int64_t)(rg + 16 * std::min(k0 + j, mine - 1)) * N + n];
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (k0 + j < mine) s += v[j];
-        }
-    }
-    red[rg][cl] = s;
-    __syncthreads();
-    if (rg == 0 && n < N) {
-        float t = 0.f;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) t += red[g][cl];
-        out[n] = t;
-    }
-}
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 static int tn_splits(int tiles, int64_t M) {
     // enough workgroups for the 256 CUs (one 128-KB workgroup per CU), each split a whole number of K-steps
     int s = std::max(1, 256 / tiles);
@@ -833,7 +767,7 @@ extern "C" int msn_bgemm_nt(int64_t M, int N, int K, const void* A, int64_t lda,
                             float* colsum_out, void* ws, size_t ws_bytes, msn_stream_t stream) {
     MSN_REQUIRE(M > 0 && N > 0 && K > 0 && A && B && C, "msn_bgemm_nt: empty operand");
     MSN_REQUIRE(K % BKS == 0 && N % 4 == 0, "msn_bgemm_nt: K = %d must be a multiple of 64 and N = %d of 4", K, N);
-    MSN_REQUIRE(lda >= K && ldb >= K && lda % 8 == 0 && ldb % 8 == 0 && aligned16(A) && aligned16(B),
+    MSN_REQUIRE(lda >= K && ldb >= K && lda % 8 == 0 && ldb % 8 == 0 && aligned16(A, B),
                 "msn_bgemm_nt: operand rows must be 16-byte aligned (lda %lld, ldb %lld)", (long long)lda, (long long)ldb);
     MSN_REQUIRE(ldc >= N && ldc % 4 == 0 && aligned16(C) && (!bias || aligned16(bias)), "msn_bgemm_nt: bad output / bias");
     // (the epilogue addresses a tile's 256 rows through one buffer descriptor and 32-bit offsets below 2^30)
@@ -872,9 +806,7 @@ extern "C" int msn_bgemm_nt(int64_t M, int N, int K, const void* A, int64_t lda,
     }
     MSN_LAUNCH_CHECK();
     if (colsum_out) {   // every (row slab, column) partial was written by exactly one wave: fixed-order sum over the slabs
-        hipLaunchKernelGGL(bcolsum_finish_kernel, dim3((unsigned)cdiv(N, 64)), dim3(1024), 0, st, a.colpart, 4 * a.tiles_m, N,
-                           colsum_out);
-        MSN_LAUNCH_CHECK();
+        if (int rc = colsum16_finish(a.colpart, 4 * a.tiles_m, N, colsum_out, st)) return rc;
     }
     return MSN_OK;
 }
@@ -889,7 +821,7 @@ extern "C" size_t msn_bgemm_tn_workspace_bytes(int64_t M, int N, int K) {
 extern "C" int msn_bgemm_tn(int64_t M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb, float* C,
                             int64_t ldc, void* ws, size_t ws_bytes, msn_stream_t stream) {
     MSN_REQUIRE(M > 0 && N > 0 && K > 0 && A && B && C, "msn_bgemm_tn: empty operand");
-    MSN_REQUIRE(N % 8 == 0 && K % 8 == 0 && lda >= N && ldb >= K && lda % 8 == 0 && ldb % 8 == 0 && aligned16(A) && aligned16(B),
+    MSN_REQUIRE(N % 8 == 0 && K % 8 == 0 && lda >= N && ldb >= K && lda % 8 == 0 && ldb % 8 == 0 && aligned16(A, B),
                 "msn_bgemm_tn: N, K and both leading dimensions must be multiples of 8, operands 16-byte aligned");
     MSN_REQUIRE(ldc >= K && ldc % 4 == 0 && aligned16(C), "msn_bgemm_tn: bad output");
     BgemmArgs a = {};
@@ -912,15 +844,13 @@ extern "C" int msn_bgemm_tn(int64_t M, int N, int K, const void* A, int64_t lda,
     MSN_LAUNCH_CHECK();
     if (a.splits > 1) {
         const int64_t n4 = (int64_t)N * K / 4;
-        hipLaunchKernelGGL(bgemm_slab_sum_kernel, dim3((unsigned)std::min<int64_t>(cdiv(n4, 256), 2048)), dim3(256), 0, st,
-                           a.slabs, a.splits, n4, K / 4, ldc / 4, C);
-        MSN_LAUNCH_CHECK();
+        if (int rc = slab_sum(a.slabs, a.splits, n4, K / 4, ldc / 4, C, st)) return rc;
     }
     return MSN_OK;
 }
 
 extern "C" int msn_cast_bf16(const float* x, int64_t n, void* y, msn_stream_t stream) {
-    MSN_REQUIRE(x && y && n > 0 && n % 8 == 0 && aligned16(x) && aligned16(y), "msn_cast_bf16: n must be a multiple of 8, 16-byte aligned");
+    MSN_REQUIRE(x && y && n > 0 && n % 8 == 0 && aligned16(x, y), "msn_cast_bf16: n must be a multiple of 8, 16-byte aligned");
     hipLaunchKernelGGL(cast_bf16_kernel, dim3((unsigned)std::min<int64_t>(cdiv(n / 8, 256), 4096)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), x, n / 8, static_cast<u16*>(y));
     MSN_LAUNCH_CHECK();
@@ -976,7 +906,5 @@ extern "C" int msn_bcolsum(const void* X, int64_t ldx, int64_t M, int N, float* 
     hipLaunchKernelGGL(bcolsum_part_kernel, dim3((unsigned)cdiv(N / 8, 32), (unsigned)parts), dim3(256), 0, st,
                        static_cast<const u16*>(X), ldx, M, N / 8, rows_per_block, part);
     MSN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bcolsum_finish_kernel, dim3((unsigned)cdiv(N, 64)), dim3(1024), 0, st, part, parts, N, out);
-    MSN_LAUNCH_CHECK();
-    return MSN_OK;
+    return colsum16_finish(part, parts, N, out, st);
 }

@@ -6,8 +6,6 @@
 
 namespace msn {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int BK = 32;
 constexpr int KPAD = 4;  // floats; keeps 16-B alignment and makes b128 fragment reads conflict-free
 
@@ -302,7 +300,7 @@ struct DmaTile {
             asm volatile("ds_read2_b32 %0, %1 offset1:%2" : "=v"(f.hi) : "v"(a + 8u * ROWS), "n"(ROWS));
         } else {
             const unsigned a = tile_addr + 4u * (row * DBK + 4 * ((2 * ko + h) ^ swz(row)));
-            asm volatile("ds_read_b128 %0, %1" : "=v"(f.v) : "v"(a));
+            ds_read128(f.v, a);
         }
     }
 };

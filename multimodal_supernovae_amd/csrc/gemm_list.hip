@@ -315,7 +315,7 @@ static bool list_takes(const msn_gemm_desc& d) {
     if (d.K % BK != 0 || d.lda % 4 != 0 || d.ldb % 4 != 0) return false;
     const int64_t a_ext = d.opA == MSN_OP_T ? d.M : d.K, b_ext = d.opB == MSN_OP_N ? d.N : d.K;
     if (a_ext % 4 != 0 || b_ext % 4 != 0 || a_ext < 4 || b_ext < 4) return false;
-    if (((reinterpret_cast<uintptr_t>(d.A) | reinterpret_cast<uintptr_t>(d.B)) & 15) != 0) return false;
+    if (!aligned16(d.A, d.B)) return false;
     if (d.lda < (d.opA == MSN_OP_N ? d.K : d.M) || d.ldb < (d.opB == MSN_OP_N ? d.N : d.K) || d.ldc < d.N) return false;
     if (d.epilogue < MSN_EPI_NONE || d.epilogue > MSN_EPI_ADD) return false;
     const bool needs_aux = d.epilogue == MSN_EPI_RELU_BWD || d.epilogue == MSN_EPI_GELU_BWD || d.epilogue == MSN_EPI_ADD;

@@ -260,8 +260,8 @@ static int launch_cfg(const GemmArgs& a, int opA, int opB, hipStream_t st) {
     // 16-byte operand loads need: base aligned, ld % 4 == 0, contiguous extent % 4 == 0 (K for a
     // K-contiguous operand, M / N for a K-major one)
     const int64_t a_ext = opA == MSN_OP_T ? a.M : a.K, b_ext = opB == MSN_OP_N ? a.N : a.K;
-    const bool vec = (a.lda % 4 == 0) && (a_ext % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.A) & 15) == 0) &&
-                     (a.ldb % 4 == 0) && (b_ext % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.B) & 15) == 0) &&
+    const bool vec = (a.lda % 4 == 0) && (a_ext % 4 == 0) && aligned16(a.A) &&
+                     (a.ldb % 4 == 0) && (b_ext % 4 == 0) && aligned16(a.B) &&
                      a_ext >= 4 && b_ext >= 4;
 #define MSN_GEMM_GO(AKM, BKM)                                                                               \
     {                                                                                                       \

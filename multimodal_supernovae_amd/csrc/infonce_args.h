@@ -11,8 +11,6 @@ constexpr int kNceNarrowMaxD = 256;   // widest embedding of the infonce.hip ker
 constexpr int kNceWideMaxD = 1024;    // infonce_wide.hip: 256 < D <= 1024, D a multiple of 32 (one 32x32 MFMA output block)
 constexpr int kNceWideGranule = 32;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int QT = 32;        // queries per workgroup
 constexpr int KT = 32;        // keys per tile
 constexpr int NW = 4;         // waves per workgroup

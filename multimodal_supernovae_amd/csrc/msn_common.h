@@ -35,12 +35,109 @@ void set_error(const char* fmt, ...);
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// Column sums from partial rows (pgemm.hip): part = [nparts][N] floats followed by COLSUM_SLICES x N floats of scratch; the
+// every pointer given sits on a 16-byte boundary (a null pointer does)
+template <class... P>
+static inline bool aligned16(const P*... p) { return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0; }
+
+// ---- fixed-order sums of partials shared across translation units (kernels in pgemm.hip) ------
+// Column sums from partial rows: part = [nparts][N] floats followed by COLSUM_SLICES x N floats of scratch; the
 // order of the additions is fixed (two passes over fixed slices), so the sums are reproducible.
 constexpr int COLSUM_SLICES = 32;
 int colsum_finish(float* part, int nparts, int N, float* out, hipStream_t st);
+// out[n] = sum_k part[k][n] in ONE pass: sixteen groups (group g owns the parts g, g + 16, ...), combined sequentially
+int colsum16_finish(const float* part, int nparts, int N, float* out, hipStream_t st);
+// C[i / K4][i % K4] = sum_s slabs[s][i], i < n4, in split order (float4 units; C rows ldc4 apart): the split-reduction GEMMs
+int slab_sum(const float* slabs, int splits, int64_t n4, int K4, int64_t ldc4, float* C, hipStream_t st);
 
 // ---- device helpers -------------------------------------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned short u16;
+
+__device__ __forceinline__ u16 f2bf(float f) {          // round to nearest even; NaN stays NaN (plain cast)
+    const __bf16 b = (__bf16)f;
+    return *reinterpret_cast<const u16*>(&b);
+}
+__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((unsigned)v << 16); }
+
+// The truncation split of the plane kernels: x = x0 + x1 + x2, each the high half of what the ones before left (exact in fp32).
+constexpr int PBLK = 1024;          // bytes of one plane image of one 32 x 16 block: [32 rows][16 bf16]
+__device__ __forceinline__ float trunc16(float x) { return __uint_as_float(__float_as_uint(x) & 0xffff0000u); }
+// (high half of b) << 16 | (high half of a): two bf16 (truncated) in fragment order
+__device__ __forceinline__ unsigned hi_pack(float a, float b) {
+    return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
+}
+// a, b -> their three planes, packed pairwise; exact: x = x0 + x1 + x2 (each difference is exact in fp32)
+struct Pair3 {
+    unsigned p0, p1, p2;
+};
+// (Written on 2-vectors -- one v_pk_add_f32 per level and pair instead of two v_sub_f32, 9 instead of 11 instructions per pair --
+//  every kernel of attention_planes.hip got SLOWER by 3 - 5 %: r06 log, item 6.  A packed fp32 add is two issue cycles, and its
+//  operands want aligned register pairs.)
+__device__ __forceinline__ Pair3 split2(float a, float b) {
+    const float ra = a - trunc16(a), rb = b - trunc16(b);
+    const float sa = ra - trunc16(ra), sb = rb - trunc16(rb);
+    return Pair3{hi_pack(a, b), hi_pack(ra, rb), hi_pack(sa, sb)};
+}
+
+// LDS reads issued from inline asm (invisible to hipcc's waitcnt pass: the kernel counts lgkmcnt by hand), plain and with an
+// immediate byte offset (added by the instruction, not by the vector ALU).  V = any 16-byte (8-byte: _tr) vector type.
+template <class V>
+__device__ __forceinline__ void ds_read128(V& dst, unsigned addr) {
+    asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr));
+}
+template <int OFF, class V>
+__device__ __forceinline__ void ds_read128_o(V& dst, unsigned addr) {
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
+}
+__device__ __forceinline__ void ds_read_tr(bf16x4& dst, unsigned addr) {
+    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(dst) : "v"(addr));
+}
+template <int OFF>
+__device__ __forceinline__ void ds_read_tr_o(bf16x4& dst, unsigned addr) {
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
+}
+
+// The two per-thread loops of the fixed-order finishing kernels: partial k of column `col` is p[k * ld + col]; a thread whose
+// column lies outside the matrix passes active = false and gets 0.  The caller combines the groups' results through LDS in its
+// own (fixed) order.  (ld and col keep the caller's integer types: they are widened inside the guarded loop, where the kernels
+// these loops came from widened them.)
+// Schedule A: the partials k = first, first + step, ... < end; four sums in flight `step` apart, combined (s0 + s1) + (s2 + s3).
+template <class I, class L, class C>
+__device__ __forceinline__ float strided_sum4(bool active, const float* p, L ld, C col, I first, I step, I end) {
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    if (active) {
+        I k = first;
+        for (; k + 3 * step < end; k += 4 * step) {
+            s0 += p[(int64_t)k * ld + col];
+            s1 += p[(int64_t)(k + step) * ld + col];
+            s2 += p[(int64_t)(k + 2 * step) * ld + col];
+            s3 += p[(int64_t)(k + 3 * step) * ld + col];
+        }
+        for (; k < end; k += step) s0 += p[(int64_t)k * ld + col];
+    }
+    return (s0 + s1) + (s2 + s3);
+}
+// Schedule B: group g of G owns the partials begin + g, begin + g + G, ... of the `count` partials from `begin` on; eight loads per
+// wait, added one after the other.
+template <class L, class C>
+__device__ __forceinline__ float strided_sum_seq8(bool active, const float* p, L ld, C col, int begin, int count, int g, int G) {
+    float s = 0.f;
+    if (active) {
+        const int mine = (count - g + (G - 1)) / G;              // partials this group owns
+        for (int k0 = 0; k0 < mine; k0 += 8) {
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = p[(int64_t)(begin + g + G * min(k0 + j, mine - 1)) * ld + col];
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (k0 + j < mine) s += v[j];
+        }
+    }
+    return s;
+}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -80,8 +80,9 @@ __global__ __launch_bounds__(256) void pgemm_tail_finish_kernel(const PgemmArgs 
     *reinterpret_cast<float4*>(static_cast<float*>(p.C) + m * p.ldc + n) = s;
 }
 
-// C[i] = sum_s slab[s][i] in split order (float4 per thread, eight independent loads per wait)
-__global__ void pgemm_slab_sum_kernel(const float* __restrict__ slabs, int splits, int64_t n4, int K4, int64_t ldc4,
+// Schedule C of the fixed-order sums: C[i] = sum_s slab[s][i] in split order (float4 per thread, eight independent loads per wait)
+// -- the split reductions of msn_pgemm_tn and msn_bgemm_tn (slab_sum, declared in msn_common.h)
+__global__ void slab_sum_kernel(const float* __restrict__ slabs, int splits, int64_t n4, int K4, int64_t ldc4,
                                       float* __restrict__ C) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -308,22 +309,29 @@ __global__ __launch_bounds__(256) void pcolsum_finish_kernel(const float* __rest
     const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
     const int n = blockIdx.x * 64 + cl;
     const int k_begin = blockIdx.y * parts_per_slice, k_end = min(nparts, k_begin + parts_per_slice);
-    float s = 0.f;
-    if (n < N && k_begin < k_end) {
-        const int cnt = k_end - k_begin;
-        const int mine = (cnt - rg + 3) / 4;
-        for (int k0 = 0; k0 < mine; k0 += 8) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = part[(int64_t)(k_begin + rg + 4 * std::min(k0 + j, mine - 1)) * N + n];
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (k0 + j < mine) s += v[j];
-        }
-    }
-    red[rg][cl] = s;
+    // (four groups over a slice, combined as a tree; colsum16_finish_kernel: sixteen groups over all parts, combined one after the other)
+    red[rg][cl] = strided_sum_seq8(n < N && k_begin < k_end, part, N, n, k_begin, k_end - k_begin, rg, 4);
     __syncthreads();
     if (rg == 0 && n < N) out[(int64_t)blockIdx.y * N + n] = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
+}
+// out[n] = sum_k part[k][n] in one pass: 64 columns x 16 row groups per workgroup (group rg sums the parts k = rg, rg + 16, ... eight
+// independent loads per wait), the sixteen group sums combined through LDS one after the other -- the column sums of msn_bgemm_nt and
+// msn_bcolsum (per 64-row slab) and of msn_attention_bf16_bwd (per sample).  (Four groups of 256 threads took 30 us for the
+// 1 576 x 3 072 partials of a GELU' launch -- 50 dependent round trips per thread on 48 workgroups; one thread per column walking
+// all 512 samples of the attention: 64 dependent round trips on nine workgroups, 40 us per launch.)
+__global__ __launch_bounds__(1024) void colsum16_finish_kernel(const float* __restrict__ part, int nparts, int N,
+                                                               float* __restrict__ out) {
+    __shared__ float red[16][64];
+    const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
+    const int n = blockIdx.x * 64 + cl;
+    red[rg][cl] = strided_sum_seq8(n < N, part, N, n, 0, nparts, rg, 16);
+    __syncthreads();
+    if (rg == 0 && n < N) {
+        float t = 0.f;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) t += red[g][cl];
+        out[n] = t;
+    }
 }
 
 // part: [nparts][N] followed by COLSUM_SLICES x N floats of scratch (declared in msn_common.h)
@@ -339,8 +347,17 @@ int colsum_finish(float* part, int nparts, int N, float* out, hipStream_t st) {
     }
     return hipGetLastError() == hipSuccess ? MSN_OK : MSN_ERR_HIP;
 }
-
-static bool aligned16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+int colsum16_finish(const float* part, int nparts, int N, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(colsum16_finish_kernel, dim3((unsigned)cdiv(N, 64)), dim3(1024), 0, st, part, nparts, N, out);
+    MSN_LAUNCH_CHECK();
+    return MSN_OK;
+}
+int slab_sum(const float* slabs, int splits, int64_t n4, int K4, int64_t ldc4, float* C, hipStream_t st) {
+    hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)std::min<int64_t>(cdiv(n4, 256), 2048)), dim3(256), 0, st, slabs, splits, n4, K4,
+                       ldc4, C);
+    MSN_LAUNCH_CHECK();
+    return MSN_OK;
+}
 
 }  // namespace msn
 
@@ -368,7 +385,7 @@ extern "C" int msn_plane_split(const float* x, int64_t ldx, int64_t R, int64_t C
                                float* colsum, void* ws, size_t ws_bytes, msn_stream_t stream) {
     MSN_REQUIRE(x && out && R > 0 && C > 0 && ldx >= C, "msn_plane_split: bad operand");
     MSN_REQUIRE(planes == 2 || planes == 3, "msn_plane_split: planes must be 2 or 3 (got %d)", planes);
-    MSN_REQUIRE(aligned16p(out), "msn_plane_split: the plane matrix must be 16-byte aligned");
+    MSN_REQUIRE(aligned16(out), "msn_plane_split: the plane matrix must be 16-byte aligned");
     MSN_REQUIRE(R < (1ll << 31) && C < (1ll << 31), "msn_plane_split: matrix too large");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (transposed) {
@@ -412,7 +429,7 @@ extern "C" int msn_plane_split_list(int n, const msn_split_item* items, int plan
         for (int k = 0; k < tb.n; ++k) {
             const msn_split_item& it = items[base + k];
             MSN_REQUIRE(it.x && it.out && it.R > 0 && it.C > 0 && it.ldx >= it.C, "msn_plane_split_list: bad operand in item %d", base + k);
-            MSN_REQUIRE(aligned16p(it.out), "msn_plane_split_list: the plane matrix of item %d must be 16-byte aligned", base + k);
+            MSN_REQUIRE(aligned16(it.out), "msn_plane_split_list: the plane matrix of item %d must be 16-byte aligned", base + k);
             MSN_REQUIRE(it.R < (1ll << 31) && it.C < (1ll << 31), "msn_plane_split_list: item %d too large", base + k);
             SplitEntry& e = tb.e[k];
             e.x = it.x, e.out = static_cast<unsigned char*>(it.out), e.ld = it.ldx, e.R = (int)it.R, e.C = (int)it.C;
@@ -433,7 +450,7 @@ extern "C" int msn_plane_split_list(int n, const msn_split_item* items, int plan
 extern "C" int msn_plane_split_f16(const float* x, int64_t ldx, int64_t R, int64_t C, int transposed, void* out, float* scale,
                                    int reuse_scale, float* colsum, void* ws, size_t ws_bytes, msn_stream_t stream) {
     MSN_REQUIRE(x && out && scale && R > 0 && C > 0 && ldx >= C, "msn_plane_split_f16: bad operand");
-    MSN_REQUIRE(aligned16p(out), "msn_plane_split_f16: the plane matrix must be 16-byte aligned");
+    MSN_REQUIRE(aligned16(out), "msn_plane_split_f16: the plane matrix must be 16-byte aligned");
     MSN_REQUIRE(R < (1ll << 31) && C < (1ll << 31), "msn_plane_split_f16: matrix too large");
     MSN_REQUIRE(!(transposed && colsum), "msn_plane_split_f16: column sums only for the untransposed form");
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -550,12 +567,12 @@ static int pgemm_nt_impl(int64_t M, int N, int K, int planes, const void* A, con
     MSN_REQUIRE(!f16 || (scaleB && planes == 2 && !c_planes), "msn_pgemm_nt_f16: two fp16 planes per operand, both scales, fp32 result");
     MSN_REQUIRE(planes == 2 || planes == 3, "msn_pgemm_nt: planes must be 2 or 3 (got %d)", planes);
     MSN_REQUIRE(N % 4 == 0 && (!c_planes || N % 16 == 0), "msn_pgemm_nt: N = %d must be a multiple of 4 (16 for a plane output)", N);
-    MSN_REQUIRE(aligned16p(A) && aligned16p(B) && aligned16p(C) && (!bias || aligned16p(bias)), "msn_pgemm_nt: operands must be 16-byte aligned");
+    MSN_REQUIRE(aligned16(A, B, C) && (!bias || aligned16(bias)), "msn_pgemm_nt: operands must be 16-byte aligned");
     MSN_REQUIRE(c_planes || (ldc >= N && ldc % 4 == 0), "msn_pgemm_nt: bad output row stride %lld", (long long)ldc);
     MSN_REQUIRE(epilogue >= MSN_EPI_NONE && epilogue <= MSN_EPI_ADD, "msn_pgemm_nt: unknown epilogue %d", epilogue);
     const bool needs_aux = epilogue == MSN_EPI_RELU_BWD || epilogue == MSN_EPI_GELU_BWD || epilogue == MSN_EPI_ADD;
     MSN_REQUIRE(!needs_aux || aux, "msn_pgemm_nt: epilogue %d needs an aux matrix", epilogue);
-    MSN_REQUIRE(!aux || (ldaux >= N && ldaux % 4 == 0 && aligned16p(aux)), "msn_pgemm_nt: bad aux matrix");
+    MSN_REQUIRE(!aux || (ldaux >= N && ldaux % 4 == 0 && aligned16(aux)), "msn_pgemm_nt: bad aux matrix");
     MSN_REQUIRE(M < (1ll << 31) * 32, "msn_pgemm_nt: too many rows");
     // the epilogue addresses C / aux through buffer descriptors per tile row with 32-bit lane offsets (pgemm_kernels.h)
     MSN_REQUIRE(N < (1 << 20) && (c_planes || ldc < (1 << 20)) && (!aux || ldaux < (1 << 20)), "msn_pgemm_nt: row strides must be below 2^20 elements");
@@ -585,7 +602,7 @@ static int pgemm_nt_impl(int64_t M, int N, int K, int planes, const void* A, con
     }
     a.scaleA = scaleA, a.scaleB = scaleB;
     const NtTail tail = nt_tail_plan(M, N, K, c_planes, epilogue, colsum_out != nullptr);
-    if (tail.segs && ws && ws_bytes >= msn_pgemm_nt_workspace_bytes(M, N, K, planes, c_planes, epilogue, 0) && aligned16p(ws)) {
+    if (tail.segs && ws && ws_bytes >= msn_pgemm_nt_workspace_bytes(M, N, K, planes, c_planes, epilogue, 0) && aligned16(ws)) {
         a.tail_full = tail.full; a.tail_segs = tail.segs; a.tail_steps = tail.steps;
         a.tail_slabs = static_cast<float*>(ws);
     }
@@ -595,7 +612,7 @@ static int pgemm_nt_impl(int64_t M, int N, int K, int planes, const void* A, con
     const bool colsum_after = colsum_out && a.chunk_steps > 0;
     if (colsum_out && !colsum_after) {
         const size_t need = msn_pgemm_nt_colsum_workspace_bytes(M, N);
-        MSN_REQUIRE(ws && ws_bytes >= need && aligned16p(ws), "msn_pgemm_nt: column-sum workspace %zu < %zu bytes", ws_bytes, need);
+        MSN_REQUIRE(ws && ws_bytes >= need && aligned16(ws), "msn_pgemm_nt: column-sum workspace %zu < %zu bytes", ws_bytes, need);
         a.colpart = static_cast<float*>(ws);
     }
     const int total = a.tiles_m * a.tiles_n;
@@ -684,7 +701,7 @@ static int pgemm_tn_impl(int64_t M, int N, int K, int planes, const void* A, con
     MSN_REQUIRE(M > 0 && N > 0 && K > 0 && A && B && C, "msn_pgemm_tn: empty operand");
     MSN_REQUIRE(!f16 || (scaleB && planes == 2), "msn_pgemm_tn_f16: two fp16 planes per operand, both scales");
     MSN_REQUIRE(planes == 2 || planes == 3, "msn_pgemm_tn: planes must be 2 or 3 (got %d)", planes);
-    MSN_REQUIRE(K % 4 == 0 && ldc >= K && ldc % 4 == 0 && aligned16p(C) && aligned16p(A) && aligned16p(B),
+    MSN_REQUIRE(K % 4 == 0 && ldc >= K && ldc % 4 == 0 && aligned16(C, A, B),
                 "msn_pgemm_tn: K and ldc must be multiples of 4, operands 16-byte aligned");
     MSN_REQUIRE(std::max(N, K) < (1 << 19), "msn_pgemm_tn: N and K must be below 2^19 (32-bit offsets inside a row block of planes)");
     const TnPlan t = tn_plan(M, N, K, planes);
@@ -696,7 +713,7 @@ static int pgemm_tn_impl(int64_t M, int N, int K, int planes, const void* A, con
     a.tiles_m = t.tiles_p; a.tiles_n = t.tiles_q;
     a.splits = t.splits; a.rb_per_split = t.rb_per_split;
     const size_t need = t.splits > 1 ? sizeof(float) * (size_t)t.splits * N * K : 0;
-    MSN_REQUIRE(need == 0 || (ws && ws_bytes >= need && aligned16p(ws)), "msn_pgemm_tn: workspace %zu < %zu bytes", ws_bytes, need);
+    MSN_REQUIRE(need == 0 || (ws && ws_bytes >= need && aligned16(ws)), "msn_pgemm_tn: workspace %zu < %zu bytes", ws_bytes, need);
     a.slabs = static_cast<float*>(ws);
     a.scaleA = scaleA, a.scaleB = scaleB;
     const int grid = t.tiles_p * t.tiles_q * t.splits;
@@ -713,9 +730,7 @@ static int pgemm_tn_impl(int64_t M, int N, int K, int planes, const void* A, con
     MSN_LAUNCH_CHECK();
     if (t.splits > 1) {
         const int64_t n4 = (int64_t)N * K / 4;
-        hipLaunchKernelGGL(pgemm_slab_sum_kernel, dim3((unsigned)std::min<int64_t>(cdiv(n4, 256), 2048)), dim3(256), 0, st,
-                           a.slabs, t.splits, n4, K / 4, ldc / 4, C);
-        MSN_LAUNCH_CHECK();
+        if (int rc = slab_sum(a.slabs, t.splits, n4, K / 4, ldc / 4, C, st)) return rc;
     }
     return MSN_OK;
 }

@@ -8,14 +8,9 @@
 
 namespace msn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16;
 typedef __attribute__((address_space(1))) const void gptr_t;
 typedef __attribute__((address_space(3))) void lptr_t;
 
@@ -26,7 +21,6 @@ typedef __attribute__((address_space(3))) void lptr_t;
 #ifndef MSN_PG_ST_AUX
 #define MSN_PG_ST_AUX 0
 #endif
-constexpr int PBLK = 1024;          // bytes of one plane image of one 32 x 16 block
 constexpr int BM = 256;             // tile rows
 
 struct PgemmArgs {
@@ -63,10 +57,6 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
-template <int OFF>
-__device__ __forceinline__ void ds_read128(bf16x8& dst, unsigned addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
 template <int N>
 __device__ __forceinline__ void wait_lgkm() {
     asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
@@ -89,12 +79,6 @@ __device__ __forceinline__ void wait_vm(int n) {        // n is wave-uniform
         default: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
     }
 }
-
-__device__ __forceinline__ u16 f2bf(float f) {          // round to nearest even; NaN stays NaN (plain cast)
-    const __bf16 b = (__bf16)f;
-    return *reinterpret_cast<const u16*>(&b);
-}
-__device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float((unsigned)v << 16); }
 
 template <int OFF>
 __device__ __forceinline__ void ds_write64_o(unsigned addr, uint2 v) {
@@ -338,7 +322,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) / 4) void pgemm_nt_kernel(c
 #endif
         static_for<0, MT>([&](auto i_) {
             constexpr int i = decltype(i_)::value;
-            ds_read128<(i * NP + pl) * PBLK>(dst[i], fragA + slot_off);
+            ds_read128_o<(i * NP + pl) * PBLK>(dst[i], fragA + slot_off);
         });
     };
     auto req_b = [&](bf16x8 (&dst)[NT], unsigned slot_off, auto pl_) {
@@ -350,7 +334,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) / 4) void pgemm_nt_kernel(c
 #endif
         static_for<0, NT>([&](auto j_) {
             constexpr int j = decltype(j_)::value;
-            ds_read128<(j * NP + pl) * PBLK>(dst[j], fragB + slot_off);
+            ds_read128_o<(j * NP + pl) * PBLK>(dst[j], fragB + slot_off);
         });
     };
     // D^T tile = B_frag . A_frag^T: lane gets row m = lane & 31 of the tile and columns n = 8 b + 4 (lane >> 5) + r
@@ -838,11 +822,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN) / 4) void pgemm_nt_kernel(c
 // 4-row x 16-column block, column-major, to a 16-lane group: lane 4 q + p of the group supplies the address of row q,
 // bytes 8 p .. 8 p + 7; lane i receives column i).  Banking is per 32 lanes = the two column blocks of a 32-wide MFMA tile:
 // they read the same row quad, which the swizzle puts into opposite 128-byte halves of the bank row -> conflict-free.
-template <int OFF>
-__device__ __forceinline__ void ds_read_tr_o(bf16x4& dst, unsigned addr) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
-
 template <int NP, int BQ, bool SWAP, bool DUAL, int WM = 2, int WN = 4, bool F16 = false, int FOLDN = 1>
 __global__ __launch_bounds__(512, 2) void pgemm_tn_kernel(const PgemmArgs p) {
     static_assert(WM * WN == 8, "eight waves");

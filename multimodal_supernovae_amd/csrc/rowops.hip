@@ -43,10 +43,6 @@ __device__ __forceinline__ void store_row(const float4 (&v)[NCH], float* __restr
     }
 }
 // the same row as bf16 (round to nearest even), 8 bytes per chunk -- operands of the bf16-resident GEMMs (gemm_bf16res.hip)
-__device__ __forceinline__ unsigned short f2bf_bits(float f) {
-    const __bf16 b = (__bf16)f;
-    return *reinterpret_cast<const unsigned short*>(&b);
-}
 template <int LPR>
 __device__ __forceinline__ void load_row_bf16(float4 (&v)[NCH], const unsigned short* __restrict__ p, int cols, int lr) {
 #pragma unroll
@@ -67,7 +63,7 @@ __device__ __forceinline__ void store_row_bf16(const float4 (&v)[NCH], unsigned 
         const int c = 4 * (lr + k * LPR);
         if (c < cols) {
             ushort4 o;
-            o.x = f2bf_bits(v[k].x); o.y = f2bf_bits(v[k].y); o.z = f2bf_bits(v[k].z); o.w = f2bf_bits(v[k].w);
+            o.x = f2bf(v[k].x); o.y = f2bf(v[k].y); o.z = f2bf(v[k].z); o.w = f2bf(v[k].w);
             *reinterpret_cast<ushort4*>(p + c) = o;
         }
     }
@@ -88,7 +84,7 @@ __device__ __forceinline__ void split4(const float4& v, uint2 (&o)[NP]) {
     for (int k = 0; k < NP; ++k) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            b[e] = f2bf_bits(r[e]);
+            b[e] = f2bf(r[e]);
             r[e] -= __uint_as_float((unsigned)b[e] << 16);       // exact
         }
         o[k].x = b[0] | ((unsigned)b[1] << 16);
@@ -437,21 +433,10 @@ __global__ __launch_bounds__(1024) void sum_slabs_kernel(const float* __restrict
     __shared__ float red[16][64];
     const int cl = threadIdx.x % 64, g = threadIdx.x / 64;
     const int i = blockIdx.x * 64 + cl;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (i < n) {
-        int b = g;
-        for (; b + 48 < nslabs; b += 64) {
-            s0 += part[(int64_t)b * n + i];
-            s1 += part[(int64_t)(b + 16) * n + i];
-            s2 += part[(int64_t)(b + 32) * n + i];
-            s3 += part[(int64_t)(b + 48) * n + i];
-        }
-        for (; b < nslabs; b += 16) s0 += part[(int64_t)b * n + i];
-    }
-    red[g][cl] = (s0 + s1) + (s2 + s3);
+    red[g][cl] = strided_sum4(i < n, part, n, i, g, 16, nslabs);
     __syncthreads();
     if (g == 0 && i < n) {
-        float t = 0.f;
+        float t = 0.f;                          // (sixteen groups added one after the other; gemm.hip's column sums: four, as a tree)
 #pragma unroll
         for (int k = 0; k < 16; ++k) t += red[k][cl];
         if (i < split) out0[i] = t;
@@ -875,7 +860,7 @@ static int check_rows(const char* who, int64_t rows, int cols, std::initializer_
                 64 * NCH * 4);
     for (int64_t ld : lds) MSN_REQUIRE(ld >= cols && ld % 4 == 0, "%s: leading dimension %lld", who, (long long)ld);
     for (const void* p : ptrs)
-        MSN_REQUIRE(p && (reinterpret_cast<uintptr_t>(p) & 15) == 0, "%s: null or unaligned pointer", who);
+        MSN_REQUIRE(p && aligned16(p), "%s: null or unaligned pointer", who);
     return MSN_OK;
 }
 
@@ -935,7 +920,7 @@ extern "C" int msn_layernorm_bwd(const float* dy, int64_t lddy, const float* x, 
                                  size_t ws_bytes, msn_stream_t stream) {
     if (int rc = check_rows("msn_layernorm_bwd", rows, cols, {lddy, ldx, lddx}, {dy, x, dx, gamma})) return rc;
     MSN_REQUIRE(mean && rstd && dgamma && dbeta, "msn_layernorm_bwd: null pointer");
-    MSN_REQUIRE(!add || (ldadd >= cols && ldadd % 4 == 0 && (reinterpret_cast<uintptr_t>(add) & 15) == 0),
+    MSN_REQUIRE(!add || (ldadd >= cols && ldadd % 4 == 0 && aligned16(add)),
                 "msn_layernorm_bwd: bad residual-gradient operand");
     const int lpr = pick_lpr(cols);
     const int grid = ln_bwd_grid(rows, lpr);
@@ -962,7 +947,7 @@ extern "C" int msn_layernorm_bwd_bf16(const float* dy, int64_t lddy, const float
     if (int rc = check_rows("msn_layernorm_bwd_bf16", rows, cols, {lddy, ldx, lddx}, {dy, x, dx, gamma})) return rc;
     MSN_REQUIRE(mean && rstd && dgamma && dbeta && dx_bf16 && (reinterpret_cast<uintptr_t>(dx_bf16) & 7) == 0,
                 "msn_layernorm_bwd_bf16: null pointer");
-    MSN_REQUIRE(!add || (ldadd >= cols && ldadd % 4 == 0 && (reinterpret_cast<uintptr_t>(add) & 15) == 0),
+    MSN_REQUIRE(!add || (ldadd >= cols && ldadd % 4 == 0 && aligned16(add)),
                 "msn_layernorm_bwd_bf16: bad residual-gradient operand");
     const int lpr = pick_lpr(cols);
     const int grid = ln_bwd_grid(rows, lpr);
@@ -1002,7 +987,7 @@ extern "C" int msn_layernorm_fwd_planes(const float* x, int64_t ldx, int64_t row
                                         float* mean, float* rstd, msn_stream_t stream) {
     if (int rc = check_rows("msn_layernorm_fwd_planes", rows, cols, {ldx}, {x, gamma, beta, y_planes})) return rc;
     MSN_REQUIRE(mean && rstd && (planes == 2 || planes == 3), "msn_layernorm_fwd_planes: bad argument");
-    MSN_REQUIRE(!y || (ldy >= cols && ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0), "msn_layernorm_fwd_planes: bad fp32 output");
+    MSN_REQUIRE(!y || (ldy >= cols && ldy % 4 == 0 && aligned16(y)), "msn_layernorm_fwd_planes: bad fp32 output");
     const int lpr = pick_lpr(cols);
     const RowGeom g{rows, cols, ldx};
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1039,7 +1024,7 @@ extern "C" int msn_layernorm_bwd_planes(const float* dy, int64_t lddy, const flo
                                         float* dbeta, float* dx_colsum, void* ws, size_t ws_bytes, msn_stream_t stream) {
     if (int rc = check_rows("msn_layernorm_bwd_planes", rows, cols, {lddy, ldx, lddx}, {dy, x, dx, gamma, dx_planes})) return rc;
     MSN_REQUIRE(mean && rstd && dgamma && dbeta && (planes == 2 || planes == 3), "msn_layernorm_bwd_planes: bad argument");
-    MSN_REQUIRE(!add || (ldadd >= cols && ldadd % 4 == 0 && (reinterpret_cast<uintptr_t>(add) & 15) == 0),
+    MSN_REQUIRE(!add || (ldadd >= cols && ldadd % 4 == 0 && aligned16(add)),
                 "msn_layernorm_bwd_planes: bad residual-gradient operand");
     const int lpr = pick_lpr(cols);
     const int grid = ln_bwd_grid(rows, lpr);
@@ -1199,7 +1184,7 @@ __global__ void add_rows_kernel(float* __restrict__ dst, int64_t ldd, const floa
 extern "C" int msn_add_rows(float* dst, int64_t ldd, const float* src, int64_t lds, int64_t rows, int cols,
                             msn_stream_t stream) {
     MSN_REQUIRE(dst && src && rows > 0 && cols > 0 && cols % 4 == 0 && ldd % 4 == 0 && lds % 4 == 0 && ldd >= cols &&
-                    lds >= cols && (reinterpret_cast<uintptr_t>(dst) & 15) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0,
+                    lds >= cols && aligned16(dst, src),
                 "msn_add_rows: bad arguments (cols and both leading dimensions must be multiples of 4, 16-byte aligned)");
     const int64_t total = rows * (cols / 4);
     hipLaunchKernelGGL(add_rows_kernel, dim3((unsigned)std::min<int64_t>(cdiv(total, 256), 4096)), dim3(256), 0,
@@ -1226,7 +1211,7 @@ extern "C" int msn_vit_tokens_bwd(const float* dtok, int64_t B, int T, int e, fl
 
 extern "C" int msn_series_features(const float* x, const float* t, const uint8_t* mask, int64_t rows, float inv_norm,
                                    float* feat, msn_stream_t stream) {
-    MSN_REQUIRE(x && t && mask && feat && rows > 0 && (reinterpret_cast<uintptr_t>(feat) & 15) == 0,
+    MSN_REQUIRE(x && t && mask && feat && rows > 0 && aligned16(feat),
                 "msn_series_features: bad arguments");
     hipLaunchKernelGGL(series_features_kernel, dim3((unsigned)std::min<int64_t>(cdiv(rows, 256), 4096)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), x, t, mask, rows, inv_norm, reinterpret_cast<float4*>(feat));
