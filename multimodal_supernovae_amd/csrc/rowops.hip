@@ -881,92 +881,8 @@ static int ln_bwd_grid(int64_t rows, int lpr) {
 
 using namespace msn;
 
-extern "C" int msn_layernorm_fwd(const float* x, int64_t ldx, int64_t rows, int cols, const float* gamma,
-                                 const float* beta, float eps, float* y, int64_t ldy, float* mean, float* rstd,
-                                 msn_stream_t stream) {
-    if (int rc = check_rows("msn_layernorm_fwd", rows, cols, {ldx, ldy}, {x, y, gamma, beta})) return rc;
-    MSN_REQUIRE(mean && rstd, "msn_layernorm_fwd: null statistics pointer");
-    const int lpr = pick_lpr(cols);
-    const RowGeom g{rows, cols, ldx};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    MSN_LPR_DISPATCH(ln_fwd_kernel, lpr, dim3(ln_grid(rows, lpr)), 0, st, x, ldx, g, gamma, beta, eps, y, ldy, mean, rstd,
-                     (unsigned short*)nullptr, PlaneOut{nullptr, 0, 0, 0})
-    MSN_LAUNCH_CHECK();
-    return MSN_OK;
-}
-
-extern "C" int msn_layernorm_fwd_bf16(const float* x, int64_t ldx, int64_t rows, int cols, const float* gamma,
-                                      const float* beta, float eps, void* y_bf16, int64_t ldy, float* mean, float* rstd,
-                                      msn_stream_t stream) {
-    if (int rc = check_rows("msn_layernorm_fwd_bf16", rows, cols, {ldx, ldy}, {x, gamma, beta})) return rc;
-    MSN_REQUIRE(mean && rstd && y_bf16 && (reinterpret_cast<uintptr_t>(y_bf16) & 7) == 0, "msn_layernorm_fwd_bf16: bad pointer");
-    const int lpr = pick_lpr(cols);
-    const RowGeom g{rows, cols, ldx};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    MSN_LPR_DISPATCH(ln_fwd_kernel, lpr, dim3(ln_grid(rows, lpr)), 0, st, x, ldx, g, gamma, beta, eps, (float*)nullptr, ldy,
-                     mean, rstd, static_cast<unsigned short*>(y_bf16), PlaneOut{nullptr, 0, 0, 0})
-    MSN_LAUNCH_CHECK();
-    return MSN_OK;
-}
-
-extern "C" size_t msn_layernorm_bwd_workspace_bytes(int64_t rows, int cols) {
-    if (rows <= 0 || cols <= 0) return 0;
-    return sizeof(float) * 2 * (size_t)cols * (size_t)ln_bwd_grid(rows, pick_lpr(cols));
-}
-
-extern "C" int msn_layernorm_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, int64_t rows, int cols,
-                                 const float* mean, const float* rstd, const float* gamma, const float* add,
-                                 int64_t ldadd, float* dx, int64_t lddx, float* dgamma, float* dbeta, void* ws,
-                                 size_t ws_bytes, msn_stream_t stream) {
-    if (int rc = check_rows("msn_layernorm_bwd", rows, cols, {lddy, ldx, lddx}, {dy, x, dx, gamma})) return rc;
-    MSN_REQUIRE(mean && rstd && dgamma && dbeta, "msn_layernorm_bwd: null pointer");
-    MSN_REQUIRE(!add || (ldadd >= cols && ldadd % 4 == 0 && aligned16(add)),
-                "msn_layernorm_bwd: bad residual-gradient operand");
-    const int lpr = pick_lpr(cols);
-    const int grid = ln_bwd_grid(rows, lpr);
-    MSN_REQUIRE(ws && ws_bytes >= sizeof(float) * 2 * (size_t)cols * grid, "msn_layernorm_bwd: workspace too small");
-    const RowGeom g{rows, cols, ldx};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float* part = static_cast<float*>(ws);
-    const size_t lds = sizeof(float) * 2 * (size_t)cols * (256 / lpr);
-    MSN_LPR_DISPATCH(ln_bwd_kernel, lpr, dim3(grid), lds, st, dy, lddy, x, ldx, g, mean, rstd, gamma, dx, lddx, part, add, ldadd,
-                     (unsigned short*)nullptr, 0, PlaneOut{nullptr, 0, 0, 0})
-    MSN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sum_slabs_kernel, dim3((unsigned)cdiv(2 * cols, 64)), dim3(1024), 0, st, part, grid, 2 * cols,
-                       dgamma, dbeta, cols);
-    MSN_LAUNCH_CHECK();
-    return MSN_OK;
-}
-
-// the same backward that ALSO writes a bf16 copy of dx (row stride lddx): the gradient is consumed twice, as the fp32
-// residual-stream gradient and as the bf16 operand of the next weight / input gradient product
-extern "C" int msn_layernorm_bwd_bf16(const float* dy, int64_t lddy, const float* x, int64_t ldx, int64_t rows, int cols,
-                                      const float* mean, const float* rstd, const float* gamma, const float* add,
-                                      int64_t ldadd, float* dx, int64_t lddx, void* dx_bf16, float* dgamma, float* dbeta,
-                                      float* dx_colsum, int dy_is_bf16, void* ws, size_t ws_bytes, msn_stream_t stream) {
-    if (int rc = check_rows("msn_layernorm_bwd_bf16", rows, cols, {lddy, ldx, lddx}, {dy, x, dx, gamma})) return rc;
-    MSN_REQUIRE(mean && rstd && dgamma && dbeta && dx_bf16 && (reinterpret_cast<uintptr_t>(dx_bf16) & 7) == 0,
-                "msn_layernorm_bwd_bf16: null pointer");
-    MSN_REQUIRE(!add || (ldadd >= cols && ldadd % 4 == 0 && aligned16(add)),
-                "msn_layernorm_bwd_bf16: bad residual-gradient operand");
-    const int lpr = pick_lpr(cols);
-    const int grid = ln_bwd_grid(rows, lpr);
-    const int nacc = dx_colsum ? 3 : 2;
-    MSN_REQUIRE(ws && ws_bytes >= sizeof(float) * nacc * (size_t)cols * grid, "msn_layernorm_bwd_bf16: workspace too small");
-    const RowGeom g{rows, cols, ldx};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float* part = static_cast<float*>(ws);
-    const size_t lds = sizeof(float) * nacc * (size_t)cols * (256 / lpr);
-    MSN_LPR_DISPATCH(ln_bwd_kernel, lpr, dim3(grid), lds, st, dy, lddy, x, ldx, g, mean, rstd, gamma, dx, lddx, part, add, ldadd,
-                     static_cast<unsigned short*>(dx_bf16), (dx_colsum ? 1 : 0) | (dy_is_bf16 ? 2 : 0), PlaneOut{nullptr, 0, 0, 0})
-    MSN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sum_slabs_kernel, dim3((unsigned)cdiv(nacc * cols, 64)), dim3(1024), 0, st, part, grid, nacc * cols,
-                       dgamma, dbeta, cols, dx_colsum);
-    MSN_LAUNCH_CHECK();
-    return MSN_OK;
-}
-
-// ---- LayerNorm writing bf16 PLANES (blocked layout of msn_plane_split): the operand of the plane GEMMs (pgemm.hip)
+// ---- LayerNorm in three arithmetic forms: fp32, a bf16 copy, bf16 PLANES (blocked layout of msn_plane_split: the operand of
+// the plane GEMMs, pgemm.hip).  The extern "C" entry points validate; launch_ln_fwd / launch_ln_bwd hold the one launch body.
 static int plane_tail_zero(void* planes_out, int64_t rows, int cols, int np, hipStream_t st) {
     // rows past `rows` in the last 32-row block are part of the plane matrix and must be zero
     if (rows % 32 == 0) return MSN_OK;
@@ -982,42 +898,151 @@ static int plane_tail_zero(void* planes_out, int64_t rows, int cols, int np, hip
 // Row-block kernels (ln_fwd_planes_kernel / ln_bwd_planes_kernel) from 32 768 rows on; below, the coarse grid of whole row blocks
 // loses to the row-at-a-time kernels (25.7 vs 25.9 us at 8 320 rows: r05 log, item 14).  Both write the same bytes.
 static constexpr int64_t kLnBlockRows = 32 * 1024;
+
+// Forward.  Each output is optional: y (fp32, row stride ldy), yb (bf16, row stride ldy), y_planes (`planes` planes).
+static int launch_ln_fwd(const float* x, int64_t ldx, int64_t rows, int cols, const float* gamma, const float* beta, float eps,
+                         float* y, int64_t ldy, unsigned short* yb, void* y_planes, int planes, float* mean, float* rstd,
+                         hipStream_t st) {
+    const int lpr = pick_lpr(cols);
+    PlaneOut po{nullptr, 0, 0, 0};
+    if (y_planes) {
+        const int cbn = 2 * (int)cdiv(cols, 32);
+        const size_t img = (size_t)cbn * planes * 1024;
+        // whole row blocks through LDS (two workgroups per CU); from 1024 row blocks on (4 per CU) -- below that the grid is too
+        // coarse: 520 blocks (16 640 rows) 18.4 us against the row kernel's 15.1, 2080 blocks 45.5 against 55.5
+        if (!y && !yb && lpr == 64 && img <= 78 * 1024 && rows >= kLnBlockRows) {
+            unsigned char* o = static_cast<unsigned char*>(y_planes);
+            const dim3 grid((unsigned)cdiv(rows, 32)), block(512);
+            if (planes == 3) {
+                if (img > 64 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(ln_fwd_planes_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)img);
+                hipLaunchKernelGGL(ln_fwd_planes_kernel<3>, grid, block, img, st, x, ldx, rows, cols, gamma, beta, eps, mean, rstd, o, cbn);
+            } else {
+                if (img > 64 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(ln_fwd_planes_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)img);
+                hipLaunchKernelGGL(ln_fwd_planes_kernel<2>, grid, block, img, st, x, ldx, rows, cols, gamma, beta, eps, mean, rstd, o, cbn);
+            }
+            MSN_LAUNCH_CHECK();
+            return MSN_OK;
+        }
+        if (int rc = plane_tail_zero(y_planes, rows, cols, planes, st)) return rc;
+        po = PlaneOut{static_cast<unsigned char*>(y_planes), planes, cbn, cols};
+    }
+    const RowGeom g{rows, cols, ldx};
+    MSN_LPR_DISPATCH(ln_fwd_kernel, lpr, dim3(ln_grid(rows, lpr)), 0, st, x, ldx, g, gamma, beta, eps, y, ldy, mean, rstd, yb, po)
+    MSN_LAUNCH_CHECK();
+    return MSN_OK;
+}
+
+extern "C" int msn_layernorm_fwd(const float* x, int64_t ldx, int64_t rows, int cols, const float* gamma,
+                                 const float* beta, float eps, float* y, int64_t ldy, float* mean, float* rstd,
+                                 msn_stream_t stream) {
+    if (int rc = check_rows("msn_layernorm_fwd", rows, cols, {ldx, ldy}, {x, y, gamma, beta})) return rc;
+    MSN_REQUIRE(mean && rstd, "msn_layernorm_fwd: null statistics pointer");
+    return launch_ln_fwd(x, ldx, rows, cols, gamma, beta, eps, y, ldy, nullptr, nullptr, 0, mean, rstd,
+                         static_cast<hipStream_t>(stream));
+}
+
+extern "C" int msn_layernorm_fwd_bf16(const float* x, int64_t ldx, int64_t rows, int cols, const float* gamma,
+                                      const float* beta, float eps, void* y_bf16, int64_t ldy, float* mean, float* rstd,
+                                      msn_stream_t stream) {
+    if (int rc = check_rows("msn_layernorm_fwd_bf16", rows, cols, {ldx, ldy}, {x, gamma, beta})) return rc;
+    MSN_REQUIRE(mean && rstd && y_bf16 && (reinterpret_cast<uintptr_t>(y_bf16) & 7) == 0, "msn_layernorm_fwd_bf16: bad pointer");
+    return launch_ln_fwd(x, ldx, rows, cols, gamma, beta, eps, nullptr, ldy, static_cast<unsigned short*>(y_bf16), nullptr, 0,
+                         mean, rstd, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int msn_layernorm_fwd_planes(const float* x, int64_t ldx, int64_t rows, int cols, const float* gamma,
                                         const float* beta, float eps, int planes, void* y_planes, float* y, int64_t ldy,
                                         float* mean, float* rstd, msn_stream_t stream) {
     if (int rc = check_rows("msn_layernorm_fwd_planes", rows, cols, {ldx}, {x, gamma, beta, y_planes})) return rc;
     MSN_REQUIRE(mean && rstd && (planes == 2 || planes == 3), "msn_layernorm_fwd_planes: bad argument");
     MSN_REQUIRE(!y || (ldy >= cols && ldy % 4 == 0 && aligned16(y)), "msn_layernorm_fwd_planes: bad fp32 output");
+    return launch_ln_fwd(x, ldx, rows, cols, gamma, beta, eps, y, ldy, nullptr, y_planes, planes, mean, rstd,
+                         static_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t msn_layernorm_bwd_workspace_bytes(int64_t rows, int cols) {
+    if (rows <= 0 || cols <= 0) return 0;
+    return sizeof(float) * 2 * (size_t)cols * (size_t)ln_bwd_grid(rows, pick_lpr(cols));
+}
+
+// Backward: dx (fp32) always; optionally ALSO a bf16 copy dxb (row stride lddx) or the planes of dx -- the gradient is consumed
+// twice, as the fp32 residual-stream gradient and as the operand of the next weight / input gradient products -- and
+// dx_colsum, the column sums of dx (a bias gradient): a third accumulator row in every workgroup's slab of partial sums
+// beside dgamma's and dbeta's (nacc 3 against 2).  `who` names the entry point in the workspace error.
+static int launch_ln_bwd(const char* who, const float* dy, int64_t lddy, const float* x, int64_t ldx, int64_t rows, int cols,
+                         const float* mean, const float* rstd, const float* gamma, const float* add, int64_t ldadd, float* dx,
+                         int64_t lddx, unsigned short* dxb, void* dx_planes, int planes, int dy_is_bf16, float* dgamma,
+                         float* dbeta, float* dx_colsum, void* ws, size_t ws_bytes, hipStream_t st) {
     const int lpr = pick_lpr(cols);
-    const RowGeom g{rows, cols, ldx};
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int grid = ln_bwd_grid(rows, lpr);
+    const int nacc = dx_colsum ? 3 : 2;
+    MSN_REQUIRE(ws && ws_bytes >= sizeof(float) * nacc * (size_t)cols * grid, "%s: workspace too small", who);
+    float* part = static_cast<float*>(ws);
     const int cbn = 2 * (int)cdiv(cols, 32);
     const size_t img = (size_t)cbn * planes * 1024;
-    // whole row blocks through LDS (two workgroups per CU); from 1024 row blocks on (4 per CU) -- below that the grid is too
-    // coarse: 520 blocks (16 640 rows) 18.4 us against the row kernel's 15.1, 2080 blocks 45.5 against 55.5
-    if (!y && lpr == 64 && img <= 78 * 1024 && rows >= kLnBlockRows) {
-        unsigned char* o = static_cast<unsigned char*>(y_planes);
-        const dim3 grid((unsigned)cdiv(rows, 32)), block(512);
-        if (planes == 3) {
-            if (img > 64 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(ln_fwd_planes_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)img);
-            hipLaunchKernelGGL(ln_fwd_planes_kernel<3>, grid, block, img, st, x, ldx, rows, cols, gamma, beta, eps, mean, rstd, o, cbn);
-        } else {
-            if (img > 64 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(ln_fwd_planes_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)img);
-            hipLaunchKernelGGL(ln_fwd_planes_kernel<2>, grid, block, img, st, x, ldx, rows, cols, gamma, beta, eps, mean, rstd, o, cbn);
-        }
-        MSN_LAUNCH_CHECK();
-        return MSN_OK;
+    int nslabs = grid;
+    if (dx_planes && lpr == 64 && img <= 78 * 1024 && rows >= kLnBlockRows) {
+        // whole row blocks through LDS (ln_bwd_planes_kernel): the same rule as the forward's
+        nslabs = (int)std::min<int64_t>(cdiv(rows, 32), std::min(grid, 512));       // <= grid: the workspace holds it
+        const int nc = (int)cdiv(cols, 256);
+        unsigned char* o = static_cast<unsigned char*>(dx_planes);
+#define MSN_LN_BWD_BLOCK(NP_, NC_)                                                                                               \
+    {                                                                                                                            \
+        if (img > 64 * 1024)                                                                                                     \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ln_bwd_planes_kernel<NP_, NC_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)img); \
+        hipLaunchKernelGGL((ln_bwd_planes_kernel<NP_, NC_>), dim3(nslabs), dim3(512), img, st, dy, lddy, x, ldx, rows, cols, mean, rstd, \
+                           gamma, dx, lddx, part, add, ldadd, dx_colsum ? 1 : 0, o, cbn);                                        \
     }
-    if (int rc = plane_tail_zero(y_planes, rows, cols, planes, st)) return rc;
-    const PlaneOut po{static_cast<unsigned char*>(y_planes), planes, 2 * (int)cdiv(cols, 32), cols};
-    MSN_LPR_DISPATCH(ln_fwd_kernel, lpr, dim3(ln_grid(rows, lpr)), 0, st, x, ldx, g, gamma, beta, eps, y, ldy, mean, rstd,
-                     (unsigned short*)nullptr, po)
+        if (planes == 3) {
+            if (nc == 1) MSN_LN_BWD_BLOCK(3, 1) else if (nc == 2) MSN_LN_BWD_BLOCK(3, 2) else if (nc == 3) MSN_LN_BWD_BLOCK(3, 3) else MSN_LN_BWD_BLOCK(3, 4)
+        } else {
+            if (nc == 1) MSN_LN_BWD_BLOCK(2, 1) else if (nc == 2) MSN_LN_BWD_BLOCK(2, 2) else if (nc == 3) MSN_LN_BWD_BLOCK(2, 3) else MSN_LN_BWD_BLOCK(2, 4)
+        }
+#undef MSN_LN_BWD_BLOCK
+    } else {
+        PlaneOut po{nullptr, 0, 0, 0};
+        if (dx_planes) {
+            if (int rc = plane_tail_zero(dx_planes, rows, cols, planes, st)) return rc;
+            po = PlaneOut{static_cast<unsigned char*>(dx_planes), planes, cbn, cols};
+        }
+        const RowGeom g{rows, cols, ldx};
+        const size_t lds = sizeof(float) * nacc * (size_t)cols * (256 / lpr);
+        MSN_LPR_DISPATCH(ln_bwd_kernel, lpr, dim3(grid), lds, st, dy, lddy, x, ldx, g, mean, rstd, gamma, dx, lddx, part, add, ldadd,
+                         dxb, (dx_colsum ? 1 : 0) | (dy_is_bf16 ? 2 : 0), po)
+    }
+    MSN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sum_slabs_kernel, dim3((unsigned)cdiv(nacc * cols, 64)), dim3(1024), 0, st, part, nslabs, nacc * cols,
+                       dgamma, dbeta, cols, dx_colsum);
     MSN_LAUNCH_CHECK();
     return MSN_OK;
 }
 
-// backward that ALSO writes the planes of dx: the gradient is consumed as the fp32 residual-stream gradient and as the plane
-// operand of the next weight / input gradient products; dx_colsum (nullable): column sums of dx (a bias gradient)
+extern "C" int msn_layernorm_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, int64_t rows, int cols,
+                                 const float* mean, const float* rstd, const float* gamma, const float* add,
+                                 int64_t ldadd, float* dx, int64_t lddx, float* dgamma, float* dbeta, void* ws,
+                                 size_t ws_bytes, msn_stream_t stream) {
+    if (int rc = check_rows("msn_layernorm_bwd", rows, cols, {lddy, ldx, lddx}, {dy, x, dx, gamma})) return rc;
+    MSN_REQUIRE(mean && rstd && dgamma && dbeta, "msn_layernorm_bwd: null pointer");
+    MSN_REQUIRE(!add || (ldadd >= cols && ldadd % 4 == 0 && aligned16(add)),
+                "msn_layernorm_bwd: bad residual-gradient operand");
+    return launch_ln_bwd("msn_layernorm_bwd", dy, lddy, x, ldx, rows, cols, mean, rstd, gamma, add, ldadd, dx, lddx, nullptr,
+                         nullptr, 0, 0, dgamma, dbeta, nullptr, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int msn_layernorm_bwd_bf16(const float* dy, int64_t lddy, const float* x, int64_t ldx, int64_t rows, int cols,
+                                      const float* mean, const float* rstd, const float* gamma, const float* add,
+                                      int64_t ldadd, float* dx, int64_t lddx, void* dx_bf16, float* dgamma, float* dbeta,
+                                      float* dx_colsum, int dy_is_bf16, void* ws, size_t ws_bytes, msn_stream_t stream) {
+    if (int rc = check_rows("msn_layernorm_bwd_bf16", rows, cols, {lddy, ldx, lddx}, {dy, x, dx, gamma})) return rc;
+    MSN_REQUIRE(mean && rstd && dgamma && dbeta && dx_bf16 && (reinterpret_cast<uintptr_t>(dx_bf16) & 7) == 0,
+                "msn_layernorm_bwd_bf16: null pointer");
+    MSN_REQUIRE(!add || (ldadd >= cols && ldadd % 4 == 0 && aligned16(add)),
+                "msn_layernorm_bwd_bf16: bad residual-gradient operand");
+    return launch_ln_bwd("msn_layernorm_bwd_bf16", dy, lddy, x, ldx, rows, cols, mean, rstd, gamma, add, ldadd, dx, lddx,
+                         static_cast<unsigned short*>(dx_bf16), nullptr, 0, dy_is_bf16, dgamma, dbeta, dx_colsum, ws, ws_bytes,
+                         static_cast<hipStream_t>(stream));
+}
+
 extern "C" int msn_layernorm_bwd_planes(const float* dy, int64_t lddy, const float* x, int64_t ldx, int64_t rows, int cols,
                                         const float* mean, const float* rstd, const float* gamma, const float* add,
                                         int64_t ldadd, float* dx, int64_t lddx, int planes, void* dx_planes, float* dgamma,
@@ -1026,50 +1051,8 @@ extern "C" int msn_layernorm_bwd_planes(const float* dy, int64_t lddy, const flo
     MSN_REQUIRE(mean && rstd && dgamma && dbeta && (planes == 2 || planes == 3), "msn_layernorm_bwd_planes: bad argument");
     MSN_REQUIRE(!add || (ldadd >= cols && ldadd % 4 == 0 && aligned16(add)),
                 "msn_layernorm_bwd_planes: bad residual-gradient operand");
-    const int lpr = pick_lpr(cols);
-    const int grid = ln_bwd_grid(rows, lpr);
-    const int nacc = dx_colsum ? 3 : 2;
-    MSN_REQUIRE(ws && ws_bytes >= sizeof(float) * nacc * (size_t)cols * grid, "msn_layernorm_bwd_planes: workspace too small");
-    const RowGeom g{rows, cols, ldx};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float* part = static_cast<float*>(ws);
-    {   // whole row blocks through LDS (ln_bwd_planes_kernel): the same rule as the forward's
-        const int cbn = 2 * (int)cdiv(cols, 32);
-        const size_t img = (size_t)cbn * planes * 1024;
-        if (lpr == 64 && img <= 78 * 1024 && rows >= kLnBlockRows) {
-            const int bgrid = (int)std::min<int64_t>(cdiv(rows, 32), std::min(grid, 512));       // <= grid: the workspace holds it
-            const int nc = (int)cdiv(cols, 256);
-            unsigned char* o = static_cast<unsigned char*>(dx_planes);
-#define MSN_LN_BWD_BLOCK(NP_, NC_)                                                                                               \
-    {                                                                                                                            \
-        if (img > 64 * 1024)                                                                                                     \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ln_bwd_planes_kernel<NP_, NC_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)img); \
-        hipLaunchKernelGGL((ln_bwd_planes_kernel<NP_, NC_>), dim3(bgrid), dim3(512), img, st, dy, lddy, x, ldx, rows, cols, mean, rstd, \
-                           gamma, dx, lddx, part, add, ldadd, dx_colsum ? 1 : 0, o, cbn);                                        \
-    }
-            if (planes == 3) {
-                if (nc == 1) MSN_LN_BWD_BLOCK(3, 1) else if (nc == 2) MSN_LN_BWD_BLOCK(3, 2) else if (nc == 3) MSN_LN_BWD_BLOCK(3, 3) else MSN_LN_BWD_BLOCK(3, 4)
-            } else {
-                if (nc == 1) MSN_LN_BWD_BLOCK(2, 1) else if (nc == 2) MSN_LN_BWD_BLOCK(2, 2) else if (nc == 3) MSN_LN_BWD_BLOCK(2, 3) else MSN_LN_BWD_BLOCK(2, 4)
-            }
-#undef MSN_LN_BWD_BLOCK
-            MSN_LAUNCH_CHECK();
-            hipLaunchKernelGGL(sum_slabs_kernel, dim3((unsigned)cdiv(nacc * cols, 64)), dim3(1024), 0, st, part, bgrid, nacc * cols,
-                               dgamma, dbeta, cols, dx_colsum);
-            MSN_LAUNCH_CHECK();
-            return MSN_OK;
-        }
-    }
-    if (int rc = plane_tail_zero(dx_planes, rows, cols, planes, st)) return rc;
-    const PlaneOut po{static_cast<unsigned char*>(dx_planes), planes, 2 * (int)cdiv(cols, 32), cols};
-    const size_t lds = sizeof(float) * nacc * (size_t)cols * (256 / lpr);
-    MSN_LPR_DISPATCH(ln_bwd_kernel, lpr, dim3(grid), lds, st, dy, lddy, x, ldx, g, mean, rstd, gamma, dx, lddx, part, add, ldadd,
-                     (unsigned short*)nullptr, dx_colsum ? 1 : 0, po)
-    MSN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sum_slabs_kernel, dim3((unsigned)cdiv(nacc * cols, 64)), dim3(1024), 0, st, part, grid, nacc * cols,
-                       dgamma, dbeta, cols, dx_colsum);
-    MSN_LAUNCH_CHECK();
-    return MSN_OK;
+    return launch_ln_bwd("msn_layernorm_bwd_planes", dy, lddy, x, ldx, rows, cols, mean, rstd, gamma, add, ldadd, dx, lddx, nullptr,
+                         dx_planes, planes, 0, dgamma, dbeta, dx_colsum, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int msn_l2norm_fwd(const float* x, int64_t ldx, int64_t rows, int cols, float* y, int64_t ldy,

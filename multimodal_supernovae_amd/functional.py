@@ -180,6 +180,22 @@ def l2_normalise(x):
 
 
 # ------------------------------------------------------------------------------ self-attention
+def _qkv_attention_fwd(qkv, B, T, e, mask_u8, heads, scale):
+    """Attention on the packed (B T, 3e) q | k | v matrix (column slices, no copies) -> (a2 (B T, e), lse)."""
+    q3 = qkv.view(B, T, 3 * e)
+    a, lse = ops.attention_fwd(q3[..., :e], q3[..., e:2 * e], q3[..., 2 * e:], mask_u8, heads, scale)
+    return a.view(B * T, e), lse
+
+
+def _qkv_attention_bwd(qkv, B, T, e, mask_u8, heads, scale, a2, lse, da):
+    """Its backward: da (B T, e) -> dqkv (B T, 3e) = dq | dk | dv, written through column slices."""
+    dqkv = torch.empty_like(qkv)
+    q3, d3 = qkv.view(B, T, 3 * e), dqkv.view(B, T, 3 * e)
+    ops.attention_bwd(q3[..., :e], q3[..., e:2 * e], q3[..., 2 * e:], mask_u8, heads, scale, a2.view(B, T, e), lse,
+                      da.view(B, T, e), d3[..., :e], d3[..., e:2 * e], d3[..., 2 * e:])
+    return dqkv
+
+
 def _attn_forward_raw(x2, B, T, wq, wk, wv, wu, bu, mask_u8, heads, scale, residual, wcat=None):
     """x2: (B*T, e).  Returns z = unify(attn) (+ residual) and what backward needs."""
     M, e = x2.shape
@@ -189,9 +205,7 @@ def _attn_forward_raw(x2, B, T, wq, wk, wv, wu, bu, mask_u8, heads, scale, resid
     if wcat is None:
         wcat = torch.cat([wq, wk, wv], 0)
     qkv = sgemm(x2, wcat, OP_N, OP_T)
-    q3 = qkv.view(B, T, 3 * e)
-    a, lse = ops.attention_fwd(q3[..., :e], q3[..., e:2 * e], q3[..., 2 * e:], mask_u8, heads, scale)
-    a2 = a.view(M, e)
+    a2, lse = _qkv_attention_fwd(qkv, B, T, e, mask_u8, heads, scale)
     if residual is not None:
         z = sgemm(a2, wu, OP_N, OP_T, bias=bu, epilogue=EPI_ADD, aux=residual)
     else:
@@ -205,10 +219,7 @@ def _attn_backward_raw(dz, x2, B, T, saved, wq, wk, wv, wu, mask_u8, heads, scal
     M, e = x2.shape
     dwu, dbu = ops.wgrad_bias(dz, a2)
     da = sgemm(dz, wu, OP_N, OP_N)
-    dqkv = torch.empty_like(qkv)
-    q3, d3 = qkv.view(B, T, 3 * e), dqkv.view(B, T, 3 * e)
-    ops.attention_bwd(q3[..., :e], q3[..., e:2 * e], q3[..., 2 * e:], mask_u8, heads, scale, a2.view(B, T, e), lse,
-                      da.view(B, T, e), d3[..., :e], d3[..., e:2 * e], d3[..., 2 * e:])
+    dqkv = _qkv_attention_bwd(qkv, B, T, e, mask_u8, heads, scale, a2, lse, da)
     dw = sgemm(dqkv, x2, OP_T, OP_N)                       # stacked (3e, e): rows = dWq | dWk | dWv
     if add_to is not None:
         dx = sgemm(dqkv, wcat, OP_N, OP_N, epilogue=EPI_ADD, aux=add_to)
@@ -551,9 +562,7 @@ class _PreNormBlock(torch.autograd.Function):
         scale = 1.0 / math.sqrt(e // heads)
         h1, m1, r1 = ops.layernorm_fwd(x2, g1, b1, eps)
         qkv = sgemm(h1, wqkv, OP_N, OP_T, bias=bqkv)
-        q3 = qkv.view(B, T, 3 * e)
-        a, lse = ops.attention_fwd(q3[..., :e], q3[..., e:2 * e], q3[..., 2 * e:], None, heads, scale)
-        a2 = a.view(B * T, e)
+        a2, lse = _qkv_attention_fwd(qkv, B, T, e, None, heads, scale)
         x1 = sgemm(a2, wo, OP_N, OP_T, bias=bo, epilogue=EPI_ADD, aux=x2)
         h2, m2, r2 = ops.layernorm_fwd(x1, g2, b2, eps)
         pre = torch.empty((B * T, w1.shape[0]), dtype=torch.float32, device=x.device)
@@ -585,10 +594,7 @@ class _PreNormBlock(torch.autograd.Function):
         else:
             dwo, dbo = ops.wgrad_bias(dx1, a2)
             da = sgemm(dx1, wo, OP_N, OP_N)
-        dqkv = torch.empty_like(qkv)
-        q3, d3 = qkv.view(B, T, 3 * e), dqkv.view(B, T, 3 * e)
-        ops.attention_bwd(q3[..., :e], q3[..., e:2 * e], q3[..., 2 * e:], None, heads, scale, a2.view(B, T, e), lse,
-                          da.view(B, T, e), d3[..., :e], d3[..., e:2 * e], d3[..., 2 * e:])
+        dqkv = _qkv_attention_bwd(qkv, B, T, e, None, heads, scale, a2, lse, da)
         if pair & 1:
             dh1, dwqkv, dbqkv = ops.dgrad_wgrad(dqkv, wqkv, h1)
         else:
@@ -631,13 +637,11 @@ class _PlaneVitTrunk(torch.autograd.Function):
             wqkvp, wop, w1p, w2p = wp[4 * i: 4 * i + 4]
             h1p, m1, r1 = ops.layernorm_fwd_planes(x2, g1, b1, eps, NPL)
             qkv = ops.pgemm_nt(h1p, wqkvp, bias=bqkv)
-            q3 = qkv.view(B, T, 3 * e)
             if ops.attention_fwd_planes_supported(T, e // heads):     # the output projection's operand from the attention kernel
-                a, lse, ap = ops.attention_fwd_planes(q3, heads, scale, NPL)
+                a, lse, ap = ops.attention_fwd_planes(qkv.view(B, T, 3 * e), heads, scale, NPL)
                 a2 = a.view(M, e)
             else:
-                a, lse = ops.attention_fwd(q3[..., :e], q3[..., e:2 * e], q3[..., 2 * e:], None, heads, scale)
-                a2 = a.view(M, e)
+                a2, lse = _qkv_attention_fwd(qkv, B, T, e, None, heads, scale)
                 ap = ops.plane_split(a2, NPL)
             x1 = ops.pgemm_nt(ap, wop, bias=bo, epilogue=EPI_ADD, aux=x2)
             h2p, m2, r2 = ops.layernorm_fwd_planes(x1, g2, b2, eps, NPL)
@@ -692,10 +696,7 @@ class _PlaneVitTrunk(torch.autograd.Function):
                 dqkvp, dbqkv = ops.attention_bwd_planes(qkv.view(B, T, 3 * e), heads, scale, a2.view(B, T, e), lse,
                                                         da.view(B, T, e), NPL)
             else:
-                dqkv = torch.empty_like(qkv)
-                q3, d3 = qkv.view(B, T, 3 * e), dqkv.view(B, T, 3 * e)
-                ops.attention_bwd(q3[..., :e], q3[..., e:2 * e], q3[..., 2 * e:], None, heads, scale, a2.view(B, T, e), lse,
-                                  da.view(B, T, e), d3[..., :e], d3[..., e:2 * e], d3[..., 2 * e:])
+                dqkv = _qkv_attention_bwd(qkv, B, T, e, None, heads, scale, a2, lse, da)
                 dqkvp, dbqkv = ops.plane_split(dqkv, NPL, want_colsum=True)
             dwqkv = ops.pgemm_tn(dqkvp, h1p)
             dh1 = ops.pgemm_nt(dqkvp, wqkvt)
@@ -742,6 +743,46 @@ def pre_norm_block(x, heads, p, eps=1e-6):
     return _PreNormBlock.apply(x, heads, eps, *p)
 
 
+# What the two last-block nodes below share: everything that touches the class rows only.  Each node keeps its own key | value
+# projection over every token, the two backward products of that projection and its attention kernel.
+def _cls_rows_forward(a2, xc, eps, wo, bo, g2, b2, w1, c1, w2, c2):
+    """From the attention rows a2 (B, e) and the class rows xc of the block's input: output projection + skip, LN2, MLP + skip."""
+    x1 = sgemm(a2, wo, OP_N, OP_T, bias=bo, epilogue=EPI_ADD, aux=xc)
+    h2, m2, r2 = ops.layernorm_fwd(x1, g2, b2, eps)
+    pre = torch.empty((a2.shape[0], w1.shape[0]), dtype=torch.float32, device=a2.device)
+    f = sgemm(h2, w1, OP_N, OP_T, bias=c1, epilogue=EPI_GELU, aux=pre)
+    out = sgemm(f, w2, OP_N, OP_T, bias=c2, epilogue=EPI_ADD, aux=x1)
+    return x1, m2, r2, h2, pre, f, out
+
+
+def _cls_rows_backward(d, wo, g2, w1, w2, a2, x1, m2, r2, h2, pre, f):
+    """Backward of _cls_rows_forward down to the attention rows: (dx1, da, (dwo, dbo, dg2, db2, dw1, dc1, dw2, dc2))."""
+    dw2, dc2 = ops.wgrad_bias(d, f)
+    dpre = sgemm(d, w2, OP_N, OP_N, epilogue=EPI_GELU_BWD, aux=pre)
+    dw1, dc1 = ops.wgrad_bias(dpre, h2)
+    dh2 = sgemm(dpre, w1, OP_N, OP_N)
+    dx1, dg2, db2 = ops.layernorm_bwd(dh2, x1, m2, r2, g2, add=d)         # + skip connection
+    dwo, dbo = ops.wgrad_bias(dx1, a2)
+    da = sgemm(dx1, wo, OP_N, OP_N)
+    return dx1, da, (dwo, dbo, dg2, db2, dw1, dc1, dw2, dc2)
+
+
+def _cls_rows_backward_ln1(B, T, e, dq2, h1c, kv_backward, wqkv, x2, m1, r1, g1, dx1):
+    """From the attention gradients up to the block's input.  dq2 (B, e) and the class rows h1c of LN1's output give the query
+    rows of dwqkv / dbqkv; kv_backward(dwqkv[e:], dbqkv[e:]) is the node's own pair of products over every token: it fills the
+    key | value rows and returns dh1 (B T, e) fp32.  -> (dx (B, T, e), dg1, db1, dwqkv, dbqkv)."""
+    dwqkv = torch.empty_like(wqkv)
+    dbqkv = torch.empty(3 * e, dtype=torch.float32, device=dq2.device)
+    ops.wgrad_bias(dq2, h1c, out=(dwqkv[:e], dbqkv[:e]))
+    dh1 = kv_backward(dwqkv[e:], dbqkv[e:])
+    dh1c = dh1.view(B, T, e)[:, 0, :]
+    sgemm(dq2, wqkv[:e], OP_N, OP_N, epilogue=EPI_ADD, aux=dh1c, out=dh1c)   # the query branch reaches class rows only
+    dx, dg1, db1 = ops.layernorm_bwd(dh1, x2, m1, r1, g1)
+    dx = dx.view(B, T, e)
+    ops.add_rows(dx[:, 0, :], dx1)                                        # skip connection of the class rows
+    return dx, dg1, db1, dwqkv, dbqkv
+
+
 @_remember_precision
 class _PreNormLastBlock(torch.autograd.Function):
     """The LAST block of the build-defined ViT, evaluated for the class token only.  The head reads token 0 of the last
@@ -767,11 +808,7 @@ class _PreNormLastBlock(torch.autograd.Function):
             kv3 = kv.view(B, T, 2 * e)
             a, lse = ops.attention_fwd(q.view(B, 1, e), kv3[..., :e], kv3[..., e:], None, heads, scale)
             a2 = a.view(B, e)
-        x1 = sgemm(a2, wo, OP_N, OP_T, bias=bo, epilogue=EPI_ADD, aux=x3[:, 0, :])
-        h2, m2, r2 = ops.layernorm_fwd(x1, g2, b2, eps)
-        pre = torch.empty((B, w1.shape[0]), dtype=torch.float32, device=x.device)
-        f = sgemm(h2, w1, OP_N, OP_T, bias=c1, epilogue=EPI_GELU, aux=pre)
-        out = sgemm(f, w2, OP_N, OP_T, bias=c2, epilogue=EPI_ADD, aux=x1)
+        x1, m2, r2, h2, pre, f, out = _cls_rows_forward(a2, x3[:, 0, :], eps, wo, bo, g2, b2, w1, c1, w2, c2)
         ctx.dims = (B, T, e, heads, scale, cls_kernels)
         ctx.save_for_backward(x2, g1, wqkv, wo, g2, w1, w2, m1, r1, h1, kv, q, a2, lse, x1, m2, r2, h2, pre, f)
         return out
@@ -781,13 +818,7 @@ class _PreNormLastBlock(torch.autograd.Function):
         B, T, e, heads, scale, cls_kernels = ctx.dims
         (x2, g1, wqkv, wo, g2, w1, w2, m1, r1, h1, kv, q, a2, lse, x1, m2, r2, h2, pre, f) = ctx.saved_tensors
         d = _c(dy)
-        dw2, dc2 = ops.wgrad_bias(d, f)
-        dpre = sgemm(d, w2, OP_N, OP_N, epilogue=EPI_GELU_BWD, aux=pre)
-        dw1, dc1 = ops.wgrad_bias(dpre, h2)
-        dh2 = sgemm(dpre, w1, OP_N, OP_N)
-        dx1, dg2, db2 = ops.layernorm_bwd(dh2, x1, m2, r2, g2, add=d)         # + skip connection
-        dwo, dbo = ops.wgrad_bias(dx1, a2)
-        da = sgemm(dx1, wo, OP_N, OP_N)
+        dx1, da, tail_grads = _cls_rows_backward(d, wo, g2, w1, w2, a2, x1, m2, r2, h2, pre, f)
         if cls_kernels:
             dq2, dkv = ops.cls_attention_bwd(q, kv, T, heads, scale, a2, lse, da)
         else:
@@ -797,17 +828,14 @@ class _PreNormLastBlock(torch.autograd.Function):
             ops.attention_bwd(q.view(B, 1, e), kv3[..., :e], kv3[..., e:], None, heads, scale, a2.view(B, 1, e), lse,
                               da.view(B, 1, e), dq, d3[..., :e], d3[..., e:])
             dq2 = dq.view(B, e)
-        h1c = h1.view(B, T, e)[:, 0, :]
-        dwqkv = torch.empty_like(wqkv)
-        dbqkv = torch.empty(3 * e, dtype=torch.float32, device=d.device)
-        ops.wgrad_bias(dq2, h1c, out=(dwqkv[:e], dbqkv[:e]))
-        ops.wgrad_bias(dkv, h1, out=(dwqkv[e:], dbqkv[e:]))
-        dh1 = sgemm(dkv, wqkv[e:], OP_N, OP_N)
-        dh1c = dh1.view(B, T, e)[:, 0, :]
-        sgemm(dq2, wqkv[:e], OP_N, OP_N, epilogue=EPI_ADD, aux=dh1c, out=dh1c)   # the query branch reaches class rows only
-        dx, dg1, db1 = ops.layernorm_bwd(dh1, x2, m1, r1, g1)
-        ops.add_rows(dx.view(B, T, e)[:, 0, :], dx1)                          # skip connection of the class rows
-        return (dx.view(B, T, e), None, None, dg1, db1, dwqkv, dbqkv, dwo, dbo, dg2, db2, dw1, dc1, dw2, dc2)
+
+        def kv_backward(dwkv, dbkv):
+            ops.wgrad_bias(dkv, h1, out=(dwkv, dbkv))
+            return sgemm(dkv, wqkv[e:], OP_N, OP_N)
+
+        dx, dg1, db1, dwqkv, dbqkv = _cls_rows_backward_ln1(B, T, e, dq2, h1.view(B, T, e)[:, 0, :], kv_backward, wqkv, x2, m1, r1,
+                                                            g1, dx1)
+        return (dx, None, None, dg1, db1, dwqkv, dbqkv, *tail_grads)
 
 
 class _Bf16LastBlock(torch.autograd.Function):
@@ -829,11 +857,7 @@ class _Bf16LastBlock(torch.autograd.Function):
         h1c = h1.view(B, T, e)[:, 0, :].float()                               # class rows
         q = sgemm(h1c, wqkv[:e], OP_N, OP_T, bias=bqkv[:e])                   # (B, e): the one query per sample
         a2, probs = ops.cls_attention_fwd(q, kv, T, heads, scale)
-        x1 = sgemm(a2, wo, OP_N, OP_T, bias=bo, epilogue=EPI_ADD, aux=x3[:, 0, :])
-        h2, m2, r2 = ops.layernorm_fwd(x1, g2, b2, eps)
-        pre = torch.empty((B, w1.shape[0]), dtype=torch.float32, device=x.device)
-        f = sgemm(h2, w1, OP_N, OP_T, bias=c1, epilogue=EPI_GELU, aux=pre)
-        out = sgemm(f, w2, OP_N, OP_T, bias=c2, epilogue=EPI_ADD, aux=x1)
+        x1, m2, r2, h2, pre, f, out = _cls_rows_forward(a2, x3[:, 0, :], eps, wo, bo, g2, b2, w1, c1, w2, c2)
         ctx.dims = (B, T, e, heads, scale)
         ctx.save_for_backward(x2, g1, wqkv, wo, g2, w1, w2, m1, r1, h1, kv, q, a2, probs, x1, m2, r2, h2, pre, f)
         return out
@@ -843,26 +867,17 @@ class _Bf16LastBlock(torch.autograd.Function):
         B, T, e, heads, scale = ctx.dims
         (x2, g1, wqkv, wo, g2, w1, w2, m1, r1, h1, kv, q, a2, probs, x1, m2, r2, h2, pre, f) = ctx.saved_tensors
         d = _c(dy)
-        dw2, dc2 = ops.wgrad_bias(d, f)
-        dpre = sgemm(d, w2, OP_N, OP_N, epilogue=EPI_GELU_BWD, aux=pre)
-        dw1, dc1 = ops.wgrad_bias(dpre, h2)
-        dh2 = sgemm(dpre, w1, OP_N, OP_N)
-        dx1, dg2, db2 = ops.layernorm_bwd(dh2, x1, m2, r2, g2, add=d)         # + skip connection
-        dwo, dbo = ops.wgrad_bias(dx1, a2)
-        da = sgemm(dx1, wo, OP_N, OP_N)
+        dx1, da, tail_grads = _cls_rows_backward(d, wo, g2, w1, w2, a2, x1, m2, r2, h2, pre, f)
         dq2, dkv = ops.cls_attention_bwd(q, kv, T, heads, scale, a2, probs, da)   # dkv: bf16, the operand of the two products below
-        h1c = h1.view(B, T, e)[:, 0, :].float()
-        dwqkv = torch.empty_like(wqkv)
-        dbqkv = torch.empty(3 * e, dtype=torch.float32, device=d.device)
-        ops.wgrad_bias(dq2, h1c, out=(dwqkv[:e], dbqkv[:e]))
-        dwqkv[e:].copy_(ops.bgemm_tn(dkv, h1))
-        dbqkv[e:].copy_(ops.bcolsum(dkv))
-        dh1 = ops.bgemm_nt(dkv, ops.cast_bf16_t(wqkv[e:]))                    # fp32: the class rows take the query branch below
-        dh1c = dh1.view(B, T, e)[:, 0, :]
-        sgemm(dq2, wqkv[:e], OP_N, OP_N, epilogue=EPI_ADD, aux=dh1c, out=dh1c)
-        dx, dg1, db1 = ops.layernorm_bwd(dh1, x2, m1, r1, g1)
-        ops.add_rows(dx.view(B, T, e)[:, 0, :], dx1)                          # skip connection of the class rows
-        return (dx.view(B, T, e), None, None, dg1, db1, dwqkv, dbqkv, dwo, dbo, dg2, db2, dw1, dc1, dw2, dc2)
+
+        def kv_backward(dwkv, dbkv):
+            dwkv.copy_(ops.bgemm_tn(dkv, h1))
+            dbkv.copy_(ops.bcolsum(dkv))
+            return ops.bgemm_nt(dkv, ops.cast_bf16_t(wqkv[e:]))               # fp32: the class rows take the query branch next
+
+        dx, dg1, db1, dwqkv, dbqkv = _cls_rows_backward_ln1(B, T, e, dq2, h1.view(B, T, e)[:, 0, :].float(), kv_backward, wqkv, x2,
+                                                            m1, r1, g1, dx1)
+        return (dx, None, None, dg1, db1, dwqkv, dbqkv, *tail_grads)
 
 
 def pre_norm_last_block(x, heads, p, eps=1e-6, bf16_resident=False):
@@ -909,9 +924,7 @@ class _Bf16VitTrunk(torch.autograd.Function):
                 a2 = empty
             else:
                 qkv = ops.bgemm_nt(h1, wqkv_b, bias=bqkv)                             # fp32: the fp32 attention kernels' input
-                q3 = qkv.view(B, T, 3 * e)
-                a, lse = ops.attention_fwd(q3[..., :e], q3[..., e:2 * e], q3[..., 2 * e:], None, heads, scale)
-                a2 = a.view(M, e)
+                a2, lse = _qkv_attention_fwd(qkv, B, T, e, None, heads, scale)
                 ab = ops.cast_bf16(a2)
             x1 = ops.bgemm_nt(ab, wo_b, bias=bo, epilogue=ops.BEPI_ADD, aux=x2)
             h2, m2, r2 = ops.layernorm_fwd_bf16(x1, g2, b2, eps)
@@ -956,10 +969,7 @@ class _Bf16VitTrunk(torch.autograd.Function):
                 dqkvb, dbqkv = ops.attention_bf16_bwd(qkv, ab, da, lse, B, T, heads, scale, want_colsum=True)
             else:
                 da = ops.bgemm_nt(dx1b, wo_t)
-                dqkv = torch.empty_like(qkv)
-                q3, d3 = qkv.view(B, T, 3 * e), dqkv.view(B, T, 3 * e)
-                ops.attention_bwd(q3[..., :e], q3[..., e:2 * e], q3[..., 2 * e:], None, heads, scale, a2.view(B, T, e), lse,
-                                  da.view(B, T, e), d3[..., :e], d3[..., e:2 * e], d3[..., 2 * e:])
+                dqkv = _qkv_attention_bwd(qkv, B, T, e, None, heads, scale, a2, lse, da)
                 dqkvb = ops.cast_bf16(dqkv)
                 dbqkv = colsum(dqkv)
             dwqkv = ops.bgemm_tn(dqkvb, h1)

@@ -1,6 +1,7 @@
 """Thin Python wrappers over the C-ABI (raw kernels, no autograd).  PyTorch is used only as the
 owner of device memory and of the current HIP stream; every FLOP happens in libmsn_hip.so."""
 import ctypes
+import os
 
 import torch
 
@@ -29,10 +30,13 @@ def plane_count(precision=None):
     """Planes per operand of the plane path under `precision` (default: the one in force), or 0 outside it."""
     p = GEMM_PRECISION if precision is None else precision
     return 3 if p == PREC_PLANES3 else 2 if p == PREC_PLANES2 else 0
-# Default "bf16x6": the wide products of the ViT towers run fp32-grade on the bf16 matrix cores from resident planes (the gate
-# for that default: tests/test_pgemm_gpu.py::test_fp32_grade_gate_* + every golden / oracle test at unchanged tolerances;
-# DESIGN.md section 4); every other product is the native fp32 MFMA kernel, exactly as under "f32".
-GEMM_PRECISION = _PREC_NAMES[__import__("os").environ.get("MSN_GEMM_PRECISION", "bf16x6").lower()]
+# Default "bf16x6": fp32-grade 3-plane arithmetic on the bf16 matrix cores for the wide products of the ViT towers (pgemm_*, from
+# resident planes) and for the fused feed-forward of the narrow towers (msn_ffn_*: functional._PostNormBlock takes it only when
+# plane_count() == 3).  The gate for that default: tests/test_pgemm_gpu.py::test_fp32_grade_gate_* + every golden / oracle test
+# at unchanged tolerances; DESIGN.md section 4.  Every other GEMM is the native fp32 MFMA kernel, exactly as under "f32".
+# Attention does not read this setting: long sequences of narrow heads run on 3 planes too (backward included) under every
+# precision, by msn_set_attention_planes.
+GEMM_PRECISION = _PREC_NAMES[os.environ.get("MSN_GEMM_PRECISION", "bf16x6").lower()]
 
 
 class gemm_precision:
@@ -52,7 +56,7 @@ class gemm_precision:
 
 
 def set_gemm_precision(name):
-    """Default inner-product precision of every GEMM issued from this process: "f32" | "bf16x3" | "bf16"."""
+    """Default inner-product precision of every GEMM issued from this process: "f32" | "bf16x3" | "bf16" | "bf16x6" | "bf16x3p"."""
     global GEMM_PRECISION
     GEMM_PRECISION = _PREC_NAMES[name]
 
@@ -77,13 +81,36 @@ OP_N, OP_T = 0, 1
 EPI_NONE, EPI_RELU, EPI_GELU, EPI_RELU_BWD, EPI_GELU_BWD, EPI_ADD = range(6)
 
 
-def _f32c(t, name):
+def _f32c(t, name, dtype=torch.float32):
+    """`t` if it is a GPU tensor of `dtype` (fp32 unless given: _bf16c), an error naming it otherwise."""
     if t.device.type != "cuda":
         _lib.require_gpu()
         raise _lib.MsnHipError(f"{name} must live on the GPU (got {t.device})")
-    if t.dtype != torch.float32:
-        raise _lib.MsnHipError(f"{name} must be float32 (got {t.dtype})")
+    if t.dtype != dtype:
+        raise _lib.MsnHipError(f"{name} must be {str(dtype).split('.')[-1]} (got {t.dtype})")
     return t
+
+
+class _span:
+    """`with _span(sink, tail):` around a launch that bench.py times.  `sink` is GEMM_PROFILE / ATTN_PROFILE / FFN_PROFILE as
+    read at the call: None = no instrumentation, no event is created; a list = one HIP event recorded on the current stream
+    before and one after, and (start_event, end_event, *tail) appended on a clean exit (nothing after an exception)."""
+    __slots__ = ("sink", "tail", "ev0")
+
+    def __init__(self, sink, tail):
+        self.sink, self.tail = sink, tail
+
+    def __enter__(self):
+        if self.sink is not None:
+            self.ev0 = torch.cuda.Event(enable_timing=True)
+            self.ev0.record()
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.sink is not None and exc_type is None:
+            ev1 = torch.cuda.Event(enable_timing=True)
+            ev1.record()
+            self.sink.append((self.ev0, ev1, *self.tail))
+        return False
 
 
 def _workspace(nbytes, device):
@@ -106,17 +133,11 @@ def sgemm(a, b, op_a=OP_N, op_b=OP_T, bias=None, epilogue=EPI_NONE, aux=None, ou
     if aux is not None:
         _f32c(aux, "aux")
         assert aux.stride(1) == 1
-    prof = GEMM_PROFILE
-    if prof is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(L.msn_sgemm(op_a, op_b, M, N, K, ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(c),
-                      c.stride(0) if c.numel() else max(N, 1), ptr(bias), epilogue, ptr(aux),
-                      aux.stride(0) if aux is not None else 0, _C_PRECISION[GEMM_PRECISION if precision is None else precision],
-                      ptr(ws), ws_bytes, stream_ptr()), "msn_sgemm")
-    if prof is not None:
-        ev1.record()
-        prof.append((ev0, ev1, 2.0 * M * N * K, (op_a, op_b, M, N, K, epilogue), aux is not None))
+    with _span(GEMM_PROFILE, (2.0 * M * N * K, (op_a, op_b, M, N, K, epilogue), aux is not None)):
+        check(L.msn_sgemm(op_a, op_b, M, N, K, ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(c),
+                          c.stride(0) if c.numel() else max(N, 1), ptr(bias), epilogue, ptr(aux),
+                          aux.stride(0) if aux is not None else 0, _C_PRECISION[GEMM_PRECISION if precision is None else precision],
+                          ptr(ws), ws_bytes, stream_ptr()), "msn_sgemm")
     return c
 
 
@@ -138,15 +159,10 @@ def wgrad_bias(dy, x, precision=None, out=None):
     L = lib()
     nb = L.msn_wgrad_bias_workspace_bytes(M, N, K)
     ws = _workspace(nb, dy.device)
-    prof = GEMM_PROFILE
-    if prof is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(L.msn_wgrad_bias(M, N, K, ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(dw), max(N, 1), ptr(db),
-                           _C_PRECISION[GEMM_PRECISION if precision is None else precision], ptr(ws), nb, stream_ptr()), "msn_wgrad_bias")
-    if prof is not None:
-        ev1.record()
-        prof.append((ev0, ev1, 2.0 * M * N * K, (OP_T, OP_N, M, N, K, EPI_NONE), False))
+    with _span(GEMM_PROFILE, (2.0 * M * N * K, (OP_T, OP_N, M, N, K, EPI_NONE), False)):
+        check(L.msn_wgrad_bias(M, N, K, ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(dw), max(N, 1), ptr(db),
+                               _C_PRECISION[GEMM_PRECISION if precision is None else precision], ptr(ws), nb, stream_ptr()),
+              "msn_wgrad_bias")
     return dw, db
 
 
@@ -173,26 +189,24 @@ def _gemm_desc(a, b, op_a, op_b, c, bias=None, epilogue=EPI_NONE, aux=None, cols
     return d
 
 
+def _list_profile_tail(descs, profile_key):
+    """GEMM_PROFILE entry of a work-list launch (sums over its descriptors: computed only while bench.py profiles)."""
+    flops = sum(2.0 * d.M * d.N * d.K for d in descs)
+    nbytes = sum(4.0 * (d.M * d.K + d.K * d.N + d.M * d.N * (2 if d.aux else 1)) for d in descs)
+    d0 = descs[0]
+    return flops, profile_key or (8, len(descs), d0.M, d0.N, d0.K, d0.epilogue), False, nbytes
+
+
 def sgemm_list(descs, precision=None, profile_key=None):
     """Up to three independent products (built by _gemm_desc) in one work-list launch (msn_sgemm_list)."""
-    import ctypes
     n = len(descs)
     arr = (_lib.GemmDesc * n)(*descs)
     L = lib()
     nb = L.msn_sgemm_list_workspace_bytes(n, ctypes.cast(arr, ctypes.c_void_p))
     ws = _workspace(nb, torch.device("cuda", torch.cuda.current_device()))
-    prof = GEMM_PROFILE
-    if prof is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(L.msn_sgemm_list(n, ctypes.cast(arr, ctypes.c_void_p), _C_PRECISION[GEMM_PRECISION if precision is None else precision],
-                           ptr(ws), nb, stream_ptr()), "msn_sgemm_list")
-    if prof is not None:
-        ev1.record()
-        flops = sum(2.0 * d.M * d.N * d.K for d in descs)
-        nbytes = sum(4.0 * (d.M * d.K + d.K * d.N + d.M * d.N * (2 if d.aux else 1)) for d in descs)
-        d0 = descs[0]
-        prof.append((ev0, ev1, flops, profile_key or (8, n, d0.M, d0.N, d0.K, d0.epilogue), False, nbytes))
+    with _span(GEMM_PROFILE, _list_profile_tail(descs, profile_key) if GEMM_PROFILE is not None else ()):
+        check(L.msn_sgemm_list(n, ctypes.cast(arr, ctypes.c_void_p), _C_PRECISION[GEMM_PRECISION if precision is None else precision],
+                               ptr(ws), nb, stream_ptr()), "msn_sgemm_list")
 
 
 def dgrad_wgrad(dy, w, x, epilogue=EPI_NONE, aux=None, want_bias=True, precision=None, want_dx=True):
@@ -238,30 +252,64 @@ def _rows2d(t):
     return t.view(-1, t.shape[-1])
 
 
-def layernorm_fwd(x, gamma, beta, eps=1e-5):
+def _layernorm_fwd(x, gamma, beta, eps, planes=None, bf16=False):
+    """The three forward forms: y fp32, y bf16 (bf16) or y as `planes` bf16 planes -> (y (rows, cols), mean, rstd)."""
     x2 = _rows2d(_f32c(x, "x"))
     rows, cols = x2.shape
-    y = torch.empty((rows, cols), dtype=torch.float32, device=x.device)
     mean = torch.empty(rows, dtype=torch.float32, device=x.device)
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-    check(lib().msn_layernorm_fwd(ptr(x2), x2.stride(0), rows, cols, ptr(gamma), ptr(beta), eps, ptr(y), cols,
-                                  ptr(mean), ptr(rstd), stream_ptr()), "msn_layernorm_fwd")
+    args = (ptr(x2), x2.stride(0), rows, cols, ptr(gamma), ptr(beta), eps)
+    if planes is not None:
+        y = Planes.empty(rows, cols, planes, x.device)
+        check(lib().msn_layernorm_fwd_planes(*args, planes, ptr(y.buf), None, 0, ptr(mean), ptr(rstd), stream_ptr()),
+              "msn_layernorm_fwd_planes")
+    else:
+        name = "msn_layernorm_fwd_bf16" if bf16 else "msn_layernorm_fwd"
+        y = torch.empty((rows, cols), dtype=torch.bfloat16 if bf16 else torch.float32, device=x.device)
+        check(getattr(lib(), name)(*args, ptr(y), cols, ptr(mean), ptr(rstd), stream_ptr()), name)
+    return y, mean, rstd
+
+
+def _layernorm_bwd(dy, x, mean, rstd, gamma, add, want_colsum=False, planes=None, bf16=False):
+    """The three backward forms: dx fp32 alone, or with a second copy of dx as bf16 (bf16; dy may be bf16 then) or as `planes`
+    bf16 planes, and with want_colsum the column sums of dx -> (dx (rows, cols), copy | None, dgamma, dbeta, colsum | None)."""
+    dy_b = bf16 and dy.dtype == torch.bfloat16
+    dy2, x2 = _rows2d(dy if dy_b else _f32c(dy, "dy")), _rows2d(x)
+    add2 = _rows2d(add) if add is not None else None
+    rows, cols = x2.shape
+    dev = x.device
+    dx = torch.empty((rows, cols), dtype=torch.float32, device=dev)
+    dg = torch.empty(cols, dtype=torch.float32, device=dev)
+    db = torch.empty(cols, dtype=torch.float32, device=dev)
+    cs = torch.empty(cols, dtype=torch.float32, device=dev) if want_colsum else None
+    L = lib()
+    nb = L.msn_layernorm_bwd_workspace_bytes(rows, cols)      # partial sums of dgamma and dbeta per workgroup: 2 accumulators
+    if planes is not None or bf16:
+        nb = nb * 3 // 2                                      # these forms may add the column sums of dx: 3 against 2
+    ws = _workspace(nb, dev)
+    args = (ptr(dy2), dy2.stride(0), ptr(x2), x2.stride(0), rows, cols, ptr(mean), ptr(rstd), ptr(gamma), ptr(add2),
+            add2.stride(0) if add2 is not None else 0, ptr(dx), cols)
+    if planes is not None:
+        copy = Planes.empty(rows, cols, planes, dev)
+        check(L.msn_layernorm_bwd_planes(*args, planes, ptr(copy.buf), ptr(dg), ptr(db), ptr(cs), ptr(ws), nb, stream_ptr()),
+              "msn_layernorm_bwd_planes")
+    elif bf16:
+        copy = torch.empty((rows, cols), dtype=torch.bfloat16, device=dev)
+        check(L.msn_layernorm_bwd_bf16(*args, ptr(copy), ptr(dg), ptr(db), ptr(cs), 1 if dy_b else 0, ptr(ws), nb, stream_ptr()),
+              "msn_layernorm_bwd_bf16")
+    else:
+        copy = None
+        check(L.msn_layernorm_bwd(*args, ptr(dg), ptr(db), ptr(ws), nb, stream_ptr()), "msn_layernorm_bwd")
+    return dx, copy, dg, db, cs
+
+
+def layernorm_fwd(x, gamma, beta, eps=1e-5):
+    y, mean, rstd = _layernorm_fwd(x, gamma, beta, eps)
     return y.view(x.shape), mean, rstd
 
 
 def layernorm_bwd(dy, x, mean, rstd, gamma, add=None):
-    dy2, x2 = _rows2d(_f32c(dy, "dy")), _rows2d(x)
-    add2 = _rows2d(add) if add is not None else None
-    rows, cols = x2.shape
-    dx = torch.empty((rows, cols), dtype=torch.float32, device=x.device)
-    dg = torch.empty(cols, dtype=torch.float32, device=x.device)
-    db = torch.empty(cols, dtype=torch.float32, device=x.device)
-    L = lib()
-    nb = L.msn_layernorm_bwd_workspace_bytes(rows, cols)
-    ws = _workspace(nb, x.device)
-    check(L.msn_layernorm_bwd(ptr(dy2), dy2.stride(0), ptr(x2), x2.stride(0), rows, cols, ptr(mean), ptr(rstd),
-                              ptr(gamma), ptr(add2), add2.stride(0) if add2 is not None else 0, ptr(dx), cols, ptr(dg),
-                              ptr(db), ptr(ws), nb, stream_ptr()), "msn_layernorm_bwd")
+    dx, _, dg, db, _ = _layernorm_bwd(dy, x, mean, rstd, gamma, add)
     return dx.view(x.shape), dg, db
 
 
@@ -395,16 +443,10 @@ def attention_fwd(q, k, v, mask_u8, heads, scale, q_shared=False):
         qbs = 0
     ldk, kbs = _bt(k)
     ldv, vbs = _bt(v)
-    prof = ATTN_PROFILE
-    if prof is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(lib().msn_attention_fwd(ptr(_f32c(q, "q")), ldq, qbs, ptr(k), ldk, kbs, ptr(v), ldv, vbs, ptr(mask_u8),
-                                  B, heads, Tq, Tk, hd, scale, ptr(out), E, Tq * E, ptr(lse), stream_ptr()),
-          "msn_attention_fwd")
-    if prof is not None:
-        ev1.record()
-        prof.append((ev0, ev1, 4.0 * B * heads * Tq * Tk * hd, (B, heads, Tq, Tk, hd), "fwd"))
+    with _span(ATTN_PROFILE, (4.0 * B * heads * Tq * Tk * hd, (B, heads, Tq, Tk, hd), "fwd")):
+        check(lib().msn_attention_fwd(ptr(_f32c(q, "q")), ldq, qbs, ptr(k), ldk, kbs, ptr(v), ldv, vbs, ptr(mask_u8),
+                                      B, heads, Tq, Tk, hd, scale, ptr(out), E, Tq * E, ptr(lse), stream_ptr()),
+              "msn_attention_fwd")
     return out, lse
 
 
@@ -431,17 +473,11 @@ def attention_bwd(q, k, v, mask_u8, heads, scale, out, lse, dout, dq, dk, dv, q_
     lq, bq = _bt(dq)
     lk, bk = _bt(dk)
     lv, bv = _bt(dv)
-    prof = ATTN_PROFILE
-    if prof is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(lib().msn_attention_bwd(ptr(q), ldq, qbs, ptr(k), ldk, kbs, ptr(v), ldv, vbs, ptr(mask_u8), B, heads, Tq,
-                                  Tk, hd, scale, ptr(out), E, Tq * E, ptr(lse), ptr(_f32c(dout, "dout")), ldd, dbs,
-                                  ptr(delta), ptr(dq), lq, bq, ptr(dk), lk, bk, ptr(dv), lv, bv, stream_ptr()),
-          "msn_attention_bwd")
-    if prof is not None:
-        ev1.record()
-        prof.append((ev0, ev1, 10.0 * B * heads * Tq * Tk * hd, (B, heads, Tq, Tk, hd), "bwd"))
+    with _span(ATTN_PROFILE, (10.0 * B * heads * Tq * Tk * hd, (B, heads, Tq, Tk, hd), "bwd")):
+        check(lib().msn_attention_bwd(ptr(q), ldq, qbs, ptr(k), ldk, kbs, ptr(v), ldv, vbs, ptr(mask_u8), B, heads, Tq,
+                                      Tk, hd, scale, ptr(out), E, Tq * E, ptr(lse), ptr(_f32c(dout, "dout")), ldd, dbs,
+                                      ptr(delta), ptr(dq), lq, bq, ptr(dk), lk, bk, ptr(dv), lv, bv, stream_ptr()),
+              "msn_attention_bwd")
     return dq, dk, dv
 
 
@@ -646,25 +682,10 @@ def conv2d_implicit_ok(B, H, W, C, co, kh, kw, sh, sw, ph, pw):
     return bool(lib().msn_conv2d_implicit_ok(B, H, W, C, co, kh, kw, sh, sw, ph, pw))
 
 
-class _conv_profile:
-    """GEMM_PROFILE entry for an implicit-GEMM convolution launch (bench.py's roofline step): M x N x K of the product the kernel
+def _conv_profile(code, M, N, K, nbytes, epilogue=0):
+    """GEMM_PROFILE span of an implicit-GEMM convolution launch (bench.py's roofline step): M x N x K of the product the kernel
     multiplies, and the bytes it must move -- image, weights, result; NOT the column matrix, which is never written."""
-
-    def __init__(self, code, M, N, K, nbytes, epilogue=0):
-        self.key, self.flops, self.nbytes = (code, 0, int(M), int(N), int(K), int(epilogue)), 2.0 * M * N * K, float(nbytes)
-        self.prof = GEMM_PROFILE
-
-    def __enter__(self):
-        if self.prof is not None:
-            self.ev0, self.ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            self.ev0.record()
-        return self
-
-    def __exit__(self, *exc):
-        if self.prof is not None and exc[0] is None:
-            self.ev1.record()
-            self.prof.append((self.ev0, self.ev1, self.flops, self.key, False, self.nbytes))
-        return False
+    return _span(GEMM_PROFILE, (2.0 * M * N * K, (code, 0, int(M), int(N), int(K), int(epilogue)), False, float(nbytes)))
 
 
 def _conv_ws(geom, device):
@@ -681,8 +702,7 @@ def conv2d_fwd(x, w_tap, kh, kw, sh, sw, ph, pw, bias=None, relu=False):
     Mo, K = y.shape[0], kh * kw * C
     with _conv_profile(20, Mo, co, K, 4.0 * (x.numel() + co * K + Mo * co), EPI_RELU if relu else EPI_NONE):
         check(lib().msn_conv2d_fwd(ptr(_f32c(x, "x")), B, H, W, C, ptr(_f32c(w_tap, "w_tap")), co, kh, kw, sh, sw, ph, pw,
-                                   ptr(bias) if bias is not None else None, EPI_RELU if relu else EPI_NONE, ptr(y),
-                                   ptr(ws) if ws is not None else None, nb, stream_ptr()), "msn_conv2d_fwd")
+                                   ptr(bias), EPI_RELU if relu else EPI_NONE, ptr(y), ptr(ws), nb, stream_ptr()), "msn_conv2d_fwd")
     return y
 
 
@@ -695,7 +715,7 @@ def conv2d_dgrad(dy, w_tco, shape, kh, kw, ph, pw):
     Mi, K = B * H * W, kh * kw * co
     with _conv_profile(21, Mi, C, K, 4.0 * (dy.numel() + K * C + Mi * C)):
         check(lib().msn_conv2d_dgrad(ptr(_f32c(dy, "dy")), B, H, W, C, ptr(_f32c(w_tco, "w_tco")), co, kh, kw, ph, pw, ptr(dx),
-                                     ptr(ws) if ws is not None else None, nb, stream_ptr()), "msn_conv2d_dgrad")
+                                     ptr(ws), nb, stream_ptr()), "msn_conv2d_dgrad")
     return dx
 
 
@@ -709,8 +729,7 @@ def conv2d_wgrad(dy, x, kh, kw, sh, sw, ph, pw, want_bias=False):
     Mo, K = dy.shape[0], kh * kw * C
     with _conv_profile(22, co, K, Mo, 4.0 * (dy.numel() + x.numel() + co * K)):
         check(lib().msn_conv2d_wgrad(ptr(_f32c(dy, "dy")), ptr(_f32c(x, "x")), B, H, W, C, co, kh, kw, sh, sw, ph, pw, ptr(dw),
-                                     ptr(db) if db is not None else None, ptr(ws) if ws is not None else None, nb, stream_ptr()),
-              "msn_conv2d_wgrad")
+                                     ptr(db), ptr(ws), nb, stream_ptr()), "msn_conv2d_wgrad")
     return dw, db
 
 
@@ -798,12 +817,7 @@ BEPI_NONE, BEPI_GELU, BEPI_GELU_BWD, BEPI_ADD = range(4)
 
 
 def _bf16c(t, name):
-    if t.device.type != "cuda":
-        _lib.require_gpu()
-        raise _lib.MsnHipError(f"{name} must live on the GPU (got {t.device})")
-    if t.dtype != torch.bfloat16:
-        raise _lib.MsnHipError(f"{name} must be bfloat16 (got {t.dtype})")
-    return t
+    return _f32c(t, name, torch.bfloat16)
 
 
 def bgemm_supported(M, N, K):
@@ -826,16 +840,10 @@ def bgemm_nt(a, w, bias=None, epilogue=BEPI_NONE, aux=None, out_bf16=False, want
         cs = torch.empty(N, dtype=torch.float32, device=a.device)
         nb = lib().msn_bgemm_nt_colsum_workspace_bytes(M, N)
         ws = _workspace(nb, a.device)
-    prof = GEMM_PROFILE
-    if prof is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(lib().msn_bgemm_nt(M, N, K, ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(c), N, 1 if out_bf16 else 0, ptr(bias),
-                             epilogue, ptr(aux), aux.stride(0) if aux is not None else 0, ptr(cs), ptr(ws), nb, stream_ptr()),
-          "msn_bgemm_nt")
-    if prof is not None:
-        ev1.record()
-        prof.append((ev0, ev1, 2.0 * M * N * K, (OP_N, OP_T, M, N, K, 100 + epilogue), aux is not None))
+    with _span(GEMM_PROFILE, (2.0 * M * N * K, (OP_N, OP_T, M, N, K, 100 + epilogue), aux is not None)):
+        check(lib().msn_bgemm_nt(M, N, K, ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(c), N, 1 if out_bf16 else 0, ptr(bias),
+                                 epilogue, ptr(aux), aux.stride(0) if aux is not None else 0, ptr(cs), ptr(ws), nb, stream_ptr()),
+              "msn_bgemm_nt")
     out = (c, aux) if epilogue == BEPI_GELU else (c,)
     if want_colsum:
         out = out + (cs,)
@@ -852,14 +860,8 @@ def bgemm_tn(dy, x):
     L = lib()
     nb = L.msn_bgemm_tn_workspace_bytes(M, N, K)
     ws = _workspace(nb, dy.device) if nb else None
-    prof = GEMM_PROFILE
-    if prof is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(L.msn_bgemm_tn(M, N, K, ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(c), K, ptr(ws), nb, stream_ptr()), "msn_bgemm_tn")
-    if prof is not None:
-        ev1.record()
-        prof.append((ev0, ev1, 2.0 * M * N * K, (OP_T, OP_N, N, K, M, 100), False))
+    with _span(GEMM_PROFILE, (2.0 * M * N * K, (OP_T, OP_N, N, K, M, 100), False)):
+        check(L.msn_bgemm_tn(M, N, K, ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(c), K, ptr(ws), nb, stream_ptr()), "msn_bgemm_tn")
     return c
 
 
@@ -918,35 +920,14 @@ def bcolsum(x):
 
 def layernorm_fwd_bf16(x, gamma, beta, eps=1e-5):
     """LayerNorm whose output is written as bf16 (the next product's operand); returns (y_bf16, mean, rstd)."""
-    x2 = _rows2d(_f32c(x, "x"))
-    rows, cols = x2.shape
-    y = torch.empty((rows, cols), dtype=torch.bfloat16, device=x.device)
-    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-    check(lib().msn_layernorm_fwd_bf16(ptr(x2), x2.stride(0), rows, cols, ptr(gamma), ptr(beta), eps, ptr(y), cols,
-                                       ptr(mean), ptr(rstd), stream_ptr()), "msn_layernorm_fwd_bf16")
-    return y, mean, rstd
+    return _layernorm_fwd(x, gamma, beta, eps, bf16=True)
 
 
 def layernorm_bwd_bf16(dy, x, mean, rstd, gamma, add=None, want_colsum=False):
     """LayerNorm backward returning (dx fp32, dx bf16 copy, dgamma, dbeta[, column sums of dx]).  dy: fp32, or bf16 as the
     input-gradient product of the bf16-resident trunk writes it."""
-    dy_b = dy.dtype == torch.bfloat16
-    dy2, x2 = _rows2d(dy if dy_b else _f32c(dy, "dy")), _rows2d(x)
-    add2 = _rows2d(add) if add is not None else None
-    rows, cols = x2.shape
-    dx = torch.empty((rows, cols), dtype=torch.float32, device=x.device)
-    dxb = torch.empty((rows, cols), dtype=torch.bfloat16, device=x.device)
-    dg = torch.empty(cols, dtype=torch.float32, device=x.device)
-    db = torch.empty(cols, dtype=torch.float32, device=x.device)
-    cs = torch.empty(cols, dtype=torch.float32, device=x.device) if want_colsum else None
-    L = lib()
-    nb = L.msn_layernorm_bwd_workspace_bytes(rows, cols) * 3 // 2
-    ws = _workspace(nb, x.device)
-    check(L.msn_layernorm_bwd_bf16(ptr(dy2), dy2.stride(0), ptr(x2), x2.stride(0), rows, cols, ptr(mean), ptr(rstd),
-                                   ptr(gamma), ptr(add2), add2.stride(0) if add2 is not None else 0, ptr(dx), cols, ptr(dxb),
-                                   ptr(dg), ptr(db), ptr(cs), 1 if dy_b else 0, ptr(ws), nb, stream_ptr()), "msn_layernorm_bwd_bf16")
-    return (dx, dxb, dg, db, cs) if want_colsum else (dx, dxb, dg, db)
+    out = _layernorm_bwd(dy, x, mean, rstd, gamma, add, want_colsum, bf16=True)
+    return out if want_colsum else out[:4]
 
 
 def attention_bf16_supported(T, head_dim):
@@ -983,8 +964,8 @@ def attention_bf16_bwd(qkv, out, dout, lse, B, T, heads, scale, want_colsum=Fals
 
 # ------------------------------------------------ fp32-grade products from resident bf16 planes (csrc/pgemm.hip)
 PLANES = 3          # planes per operand when a caller does not say: 3 = fp32 grade (6 products), 2 = 3 products
-if __import__("os").environ.get("MSN_ATTN_PLANES"):        # 0: long narrow-head attention on the exact-fp32 matrix-core kernels; 3 / 5: backward forms (A/B runs)
-    check(lib().msn_set_attention_planes(int(__import__("os").environ["MSN_ATTN_PLANES"])))
+if os.environ.get("MSN_ATTN_PLANES"):        # 0: long narrow-head attention on the exact-fp32 matrix-core kernels; 3 / 5: backward forms (A/B runs)
+    check(lib().msn_set_attention_planes(int(os.environ["MSN_ATTN_PLANES"])))
 
 
 F16_PLANES = 16     # `planes` code of the fp16 form: TWO fp16 planes + a power-of-two scale per matrix (msn_plane_split_f16)
@@ -1060,15 +1041,9 @@ def ffn_fwd(x, w1p, w2tp, c1, c2):
     _f32c(x, "x")
     M, e = x.shape
     z = torch.empty((M, e), dtype=torch.float32, device=x.device)
-    prof = FFN_PROFILE
-    if prof is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(lib().msn_ffn_fwd(ptr(x), x.stride(0), M, e, c1.numel(), ptr(w1p.buf), ptr(w2tp.buf), ptr(_f32c(c1, "c1")), ptr(_f32c(c2, "c2")),
-                            ptr(z), e, stream_ptr()), "msn_ffn_fwd")
-    if prof is not None:
-        ev1.record()
-        prof.append((ev0, ev1, 4.0 * M * e * c1.numel(), "fwd"))
+    with _span(FFN_PROFILE, (4.0 * M * e * c1.numel(), "fwd")):
+        check(lib().msn_ffn_fwd(ptr(x), x.stride(0), M, e, c1.numel(), ptr(w1p.buf), ptr(w2tp.buf), ptr(_f32c(c1, "c1")),
+                                ptr(_f32c(c2, "c2")), ptr(z), e, stream_ptr()), "msn_ffn_fwd")
     return z
 
 
@@ -1084,15 +1059,9 @@ def ffn_bwd(x, dz, w1p, w2tp, c1):
     dc2 = torch.empty(e, dtype=torch.float32, device=x.device)
     nb = lib().msn_ffn_bwd_workspace_bytes(M, e, hid)
     ws = _workspace(nb, x.device)
-    prof = FFN_PROFILE
-    if prof is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(lib().msn_ffn_bwd(ptr(x), x.stride(0), ptr(dz), dz.stride(0), M, e, hid, ptr(w1p.buf), ptr(w2tp.buf), ptr(_f32c(c1, "c1")),
-                            ptr(dx), e, ptr(dw1), ptr(dc1), ptr(dw2), ptr(dc2), ptr(ws), nb, stream_ptr()), "msn_ffn_bwd")
-    if prof is not None:
-        ev1.record()
-        prof.append((ev0, ev1, 8.0 * M * e * hid, "bwd"))       # the four products of an unfused backward (the recomputation is not counted)
+    with _span(FFN_PROFILE, (8.0 * M * e * hid, "bwd")):      # the four products of an unfused backward (the recomputation is not counted)
+        check(lib().msn_ffn_bwd(ptr(x), x.stride(0), ptr(dz), dz.stride(0), M, e, hid, ptr(w1p.buf), ptr(w2tp.buf), ptr(_f32c(c1, "c1")),
+                                ptr(dx), e, ptr(dw1), ptr(dc1), ptr(dw2), ptr(dc2), ptr(ws), nb, stream_ptr()), "msn_ffn_bwd")
     return dx, dw1, dc1, dw2, dc2
 
 
@@ -1130,18 +1099,10 @@ def attention_fwd_planes(qkv, heads, scale, planes=None, mask_u8=None):
     lse = torch.empty((B, heads, T, 2), dtype=torch.float32, device=qkv.device)
     op = Planes.empty(B * T, E, planes, qkv.device)
     hd = E // heads
-    prof = ATTN_PROFILE
-    if prof is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(lib().msn_attention_fwd_planes(ptr(qkv), qkv.stride(1), ptr(mask_u8), B, heads, T, hd, scale, ptr(out), E, ptr(lse), planes,
-                                         ptr(op.buf), stream_ptr()), "msn_attention_fwd_planes")
-    if prof is not None:
-        ev1.record()
-        prof.append((ev0, ev1, 4.0 * B * heads * T * T * hd, (B, heads, T, T, hd), "fwd"))
+    with _span(ATTN_PROFILE, (4.0 * B * heads * T * T * hd, (B, heads, T, T, hd), "fwd")):
+        check(lib().msn_attention_fwd_planes(ptr(qkv), qkv.stride(1), ptr(mask_u8), B, heads, T, hd, scale, ptr(out), E, ptr(lse),
+                                             planes, ptr(op.buf), stream_ptr()), "msn_attention_fwd_planes")
     return out, lse, op
-
-
 
 
 def cls_attention_supported(T, head_dim):
@@ -1242,26 +1203,20 @@ def pgemm_nt(a, w, bias=None, epilogue=EPI_NONE, aux=None, out_planes=False, wan
     cs = torch.empty(N, dtype=torch.float32, device=dev) if want_colsum else None
     nb = lib().msn_pgemm_nt_workspace_bytes(M, N, K, a.planes, 1 if out_planes else 0, epilogue, 1 if want_colsum else 0)
     ws = _workspace(nb, dev) if nb else None
-    prof = GEMM_PROFILE
-    if prof is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    if a.scale is not None:
-        assert w.scale is not None and not out_planes, "fp16 planes: both operands, fp32 result"
-        check(lib().msn_pgemm_nt_f16(M, N, K, ptr(a.buf), ptr(a.scale), ptr(w.buf), ptr(w.scale), ptr(c), N, ptr(bias), epilogue,
-                                     ptr(aux), aux.stride(0) if aux is not None else 0, ptr(cs), ptr(ws), nb, stream_ptr()),
-              "msn_pgemm_nt_f16")
-    else:
-        check(lib().msn_pgemm_nt(M, N, K, a.planes, ptr(a.buf), ptr(w.buf), ptr(c.buf if out_planes else c), N,
-                                 1 if out_planes else 0, ptr(bias), epilogue, ptr(aux), aux.stride(0) if aux is not None else 0,
-                                 ptr(cs), ptr(ws), nb, stream_ptr()), "msn_pgemm_nt")
-    if prof is not None:
-        ev1.record()
-        # bytes this launch MUST move in the formats it is given: plane operands are 2 bytes x planes per element (6 for the
-        # fp32-grade form), the result fp32 or planes, the aux matrix (gelu' written / read, residual read) fp32
-        pb = 2.0 * a.planes
-        nbytes = pb * (M * K + N * K) + (pb if out_planes else 4.0) * M * N + (4.0 * M * N if aux is not None else 0.0)
-        prof.append((ev0, ev1, 2.0 * M * N * K, (OP_N, OP_T, M, N, K, 200 + epilogue), aux is not None, nbytes))
+    # bytes this launch MUST move in the formats it is given: plane operands are 2 bytes x planes per element (6 for the
+    # fp32-grade form), the result fp32 or planes, the aux matrix (gelu' written / read, residual read) fp32
+    pb = 2.0 * a.planes
+    nbytes = pb * (M * K + N * K) + (pb if out_planes else 4.0) * M * N + (4.0 * M * N if aux is not None else 0.0)
+    with _span(GEMM_PROFILE, (2.0 * M * N * K, (OP_N, OP_T, M, N, K, 200 + epilogue), aux is not None, nbytes)):
+        if a.scale is not None:
+            assert w.scale is not None and not out_planes, "fp16 planes: both operands, fp32 result"
+            check(lib().msn_pgemm_nt_f16(M, N, K, ptr(a.buf), ptr(a.scale), ptr(w.buf), ptr(w.scale), ptr(c), N, ptr(bias), epilogue,
+                                         ptr(aux), aux.stride(0) if aux is not None else 0, ptr(cs), ptr(ws), nb, stream_ptr()),
+                  "msn_pgemm_nt_f16")
+        else:
+            check(lib().msn_pgemm_nt(M, N, K, a.planes, ptr(a.buf), ptr(w.buf), ptr(c.buf if out_planes else c), N,
+                                     1 if out_planes else 0, ptr(bias), epilogue, ptr(aux), aux.stride(0) if aux is not None else 0,
+                                     ptr(cs), ptr(ws), nb, stream_ptr()), "msn_pgemm_nt")
     out = (c, aux) if ret_aux else (c,)
     if want_colsum:
         out = out + (cs,)
@@ -1277,51 +1232,26 @@ def pgemm_tn(dy, x):
     L = lib()
     nb = L.msn_pgemm_tn_workspace_bytes(M, N, K, dy.planes)
     ws = _workspace(nb, dev) if nb else None
-    prof = GEMM_PROFILE
-    if prof is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    if dy.scale is not None:
-        assert x.scale is not None
-        check(L.msn_pgemm_tn_f16(M, N, K, ptr(dy.buf), ptr(dy.scale), ptr(x.buf), ptr(x.scale), ptr(c), K, ptr(ws), nb, stream_ptr()),
-              "msn_pgemm_tn_f16")
-    else:
-        check(L.msn_pgemm_tn(M, N, K, dy.planes, ptr(dy.buf), ptr(x.buf), ptr(c), K, ptr(ws), nb, stream_ptr()), "msn_pgemm_tn")
-    if prof is not None:
-        ev1.record()
-        prof.append((ev0, ev1, 2.0 * M * N * K, (OP_T, OP_N, N, K, M, 200), False, 2.0 * dy.planes * (M * N + M * K) + 4.0 * N * K))
+    nbytes = 2.0 * dy.planes * (M * N + M * K) + 4.0 * N * K
+    with _span(GEMM_PROFILE, (2.0 * M * N * K, (OP_T, OP_N, N, K, M, 200), False, nbytes)):
+        if dy.scale is not None:
+            assert x.scale is not None
+            check(L.msn_pgemm_tn_f16(M, N, K, ptr(dy.buf), ptr(dy.scale), ptr(x.buf), ptr(x.scale), ptr(c), K, ptr(ws), nb, stream_ptr()),
+                  "msn_pgemm_tn_f16")
+        else:
+            check(L.msn_pgemm_tn(M, N, K, dy.planes, ptr(dy.buf), ptr(x.buf), ptr(c), K, ptr(ws), nb, stream_ptr()), "msn_pgemm_tn")
     return c
 
 
 def layernorm_fwd_planes(x, gamma, beta, eps, planes):
     """LayerNorm whose output goes straight to bf16 planes (the next product's operand); returns (Planes, mean, rstd)."""
-    x2 = _rows2d(_f32c(x, "x"))
-    rows, cols = x2.shape
-    y = Planes.empty(rows, cols, planes, x.device)
-    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-    check(lib().msn_layernorm_fwd_planes(ptr(x2), x2.stride(0), rows, cols, ptr(gamma), ptr(beta), eps, planes, ptr(y.buf), None, 0,
-                                         ptr(mean), ptr(rstd), stream_ptr()), "msn_layernorm_fwd_planes")
-    return y, mean, rstd
+    return _layernorm_fwd(x, gamma, beta, eps, planes=planes)
 
 
 def layernorm_bwd_planes(dy, x, mean, rstd, gamma, planes, add=None, want_colsum=False):
     """LayerNorm backward returning (dx fp32, dx Planes, dgamma, dbeta[, column sums of dx])."""
-    dy2, x2 = _rows2d(_f32c(dy, "dy")), _rows2d(x)
-    add2 = _rows2d(add) if add is not None else None
-    rows, cols = x2.shape
-    dx = torch.empty((rows, cols), dtype=torch.float32, device=x.device)
-    dxp = Planes.empty(rows, cols, planes, x.device)
-    dg = torch.empty(cols, dtype=torch.float32, device=x.device)
-    db = torch.empty(cols, dtype=torch.float32, device=x.device)
-    cs = torch.empty(cols, dtype=torch.float32, device=x.device) if want_colsum else None
-    L = lib()
-    nb = L.msn_layernorm_bwd_workspace_bytes(rows, cols) * 3 // 2
-    ws = _workspace(nb, x.device)
-    check(L.msn_layernorm_bwd_planes(ptr(dy2), dy2.stride(0), ptr(x2), x2.stride(0), rows, cols, ptr(mean), ptr(rstd), ptr(gamma),
-                                     ptr(add2), add2.stride(0) if add2 is not None else 0, ptr(dx), cols, planes, ptr(dxp.buf),
-                                     ptr(dg), ptr(db), ptr(cs), ptr(ws), nb, stream_ptr()), "msn_layernorm_bwd_planes")
-    return (dx, dxp, dg, db, cs) if want_colsum else (dx, dxp, dg, db)
+    out = _layernorm_bwd(dy, x, mean, rstd, gamma, add, want_colsum, planes=planes)
+    return out if want_colsum else out[:4]
 
 
 def set_pgemm_tail_split(enabled):
