@@ -23,6 +23,18 @@ class RAdam(torch.optim.Optimizer):
             raise ValueError("invalid RAdam hyper-parameters")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
 
+    def load_state_dict(self, state_dict):
+        """torch.optim.Optimizer.load_state_dict on a DEEP COPY of `state_dict` (torch's `.to()` of a tensor that already has
+        the parameter's device and dtype returns that very tensor, so the live state of another optimizer would be shared and
+        stepped twice), then every `step` as a Python int: torch.optim.RAdam stores tensor(7.), a Lightning checkpoint
+        loaded with map_location="cuda" a CUDA tensor, and `_step_captured` / `graph_prepare` read int(step) -- on a CUDA
+        tensor a synchronisation inside a stream capture."""
+        import copy
+        super().load_state_dict(copy.deepcopy(state_dict))
+        for st in self.state.values():
+            if "step" in st:
+                st["step"] = int(st["step"])
+
     def _init_state(self):
         """Moment buffers of every parameter that has a gradient and no state yet, as views of ONE zeroed buffer per
         device (one fill launch instead of two per parameter; the step's launch reads them through the pointer table)."""

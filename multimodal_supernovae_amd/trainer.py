@@ -8,11 +8,15 @@ sequence as Lightning's automatic optimisation --
 -- with the 9-tuple batch moved to the GPU (None / empty placeholders pass through), epoch means
 of train_loss / val_loss, (multi-process) SUM all-reduce of the gradients before the step, and
 pl.Trainer's gradient clipping (gradient_clip_val / gradient_clip_algorithm) between the all-reduce and the step.
-Checkpointing, early stopping and W&B logging of the reference harness are out of scope.
+Callbacks (checkpoint.ModelCheckpoint, checkpoint.EarlyStopping) run once per epoch where Lightning saves: after
+validation -- after the training epoch without a validation loader -- and after the scheduler step;
+`fit(..., ckpt_path=...)` resumes a run from a checkpoint file (checkpoint.py says what resumes exactly).
+W&B logging of the reference harness is out of scope.
 """
 import torch
 import torch.distributed as dist
 
+from . import checkpoint as C
 from . import distributed as D
 from . import markers
 from . import optim
@@ -117,7 +121,7 @@ def _backward_seed(loss):
 
 class Trainer:
     def __init__(self, max_epochs=1, device=None, group=None, log_fn=None, sync_batchnorm=False, graphed_steps=False,
-                 gradient_clip_val=None, gradient_clip_algorithm=None):
+                 gradient_clip_val=None, gradient_clip_algorithm=None, callbacks=None):
         # pl.Trainer(gradient_clip_val=..., gradient_clip_algorithm=...): clip the all-reduced gradients before the step
         self.clip = _clip_config(gradient_clip_val, gradient_clip_algorithm)
         self.gradient_clip_val, self.gradient_clip_algorithm = gradient_clip_val, gradient_clip_algorithm
@@ -130,9 +134,83 @@ class Trainer:
         self.history = {"train_loss": [], "val_loss": []}
         self.step_losses = []
         self.global_step = 0
+        # as Lightning: checkpoint callbacks run last, so the file holds the state the other callbacks reached this epoch
+        callbacks = list(callbacks or [])
+        self.callbacks = ([c for c in callbacks if not isinstance(c, C.ModelCheckpoint)]
+                          + [c for c in callbacks if isinstance(c, C.ModelCheckpoint)])
+        self.current_epoch = 0
+        self.should_stop = False
+        self.model = self.optimizer = self.scheduler = self.graphed_step = None
 
-    def fit(self, model, train_dataloaders, val_dataloaders=None):
+    # ---- what callbacks see ----------------------------------------------------------------------------------------
+    @property
+    def is_global_zero(self):
+        return not (dist.is_available() and dist.is_initialized()) or dist.get_rank(self.group) == 0
+
+    def barrier(self):
+        if D.world_size(self.group) > 1:
+            dist.barrier(self.group)
+
+    def monitored(self, name):
+        """The value a callback monitors, as a float: the batch-weighted epoch mean of Trainer.history for train_loss /
+        val_loss (model.logged holds the last batch's), model.logged[name] for any other name (AUC_val, f1_val, ...).
+        With several ranks every rank gets rank 0's value: a rank that stopped or saved on a value of its own would
+        leave the others in a collective."""
+        if name in self.history:
+            value = self.history[name][-1] if self.history[name] else None
+        else:
+            value = getattr(self.model, "logged", {}).get(name)
+        value = None if value is None else float(value)
+        if D.world_size(self.group) > 1:
+            box = [value]
+            src = dist.get_global_rank(self.group, 0) if self.group is not None else 0
+            dist.broadcast_object_list(box, src=src, group=self.group)
+            value = box[0]
+        if value is None:
+            raise RuntimeError(f"monitored value {name!r} has not been logged this run (history: {sorted(self.history)}; "
+                               f"model.logged: {sorted(getattr(self.model, 'logged', {}))})")
+        return value
+
+    def save_checkpoint(self, path):
+        """The state of the run (model, optimizer, scheduler, callbacks, history, RNG) as a Lightning-layout file
+        (checkpoint.save_checkpoint); with several ranks every rank calls it and rank 0 writes."""
+        if self.model is None:
+            raise RuntimeError("Trainer.save_checkpoint: nothing to save before fit() has started")
+        extra = {"epoch": self.current_epoch, "global_step": self.global_step,
+                 "callbacks": {cb.state_key: cb.state_dict() for cb in self.callbacks},
+                 "history": {k: list(v) for k, v in self.history.items()}}
+        return C.save_checkpoint(path, self.model, self.optimizer, self.scheduler, extra, group=self.group, device=self.device)
+
+    def _resume(self, ckpt, model, optimizer, scheduler):
+        """optimizer -> scheduler -> callbacks -> history -> global_step -> RNG (the model is loaded before); returns the epoch
+        to go on with."""
+        if ckpt["optimizer_states"]:
+            C.load_optimizer_state(optimizer, ckpt["optimizer_states"][0])
+        if scheduler is not None and ckpt["lr_schedulers"]:
+            scheduler.load_state_dict(ckpt["lr_schedulers"][0])
+        for cb in self.callbacks:
+            if cb.state_key in ckpt["callbacks"]:
+                cb.load_state_dict(ckpt["callbacks"][cb.state_key])
+            cb.on_resume(self)
+        msn = ckpt.get("msn") or {}
+        if "history" in msn:
+            self.history = {k: list(v) for k, v in msn["history"].items()}
+            for k in ("train_loss", "val_loss"):
+                self.history.setdefault(k, [])
+        self.global_step = ckpt["global_step"]
+        self.current_epoch = max(ckpt["epoch"], 0)
+        C.restore_rng(ckpt, device=self.device, group=self.group)
+        return ckpt["epoch"] + 1
+
+    def fit(self, model, train_dataloaders, val_dataloaders=None, ckpt_path=None):
+        """`ckpt_path`: a checkpoint file of this package or of Lightning (or the dict checkpoint.load_checkpoint returned
+        for one) to resume from: training continues at the saved epoch + 1 up to `max_epochs` epochs in total."""
         model.to(self.device)
+        self.should_stop = False
+        ckpt = None
+        if ckpt_path is not None:
+            ckpt = ckpt_path if isinstance(ckpt_path, dict) else C.load_checkpoint(ckpt_path, map_location="cpu")
+            model.load_state_dict(ckpt["state_dict"], strict=True)
         D.broadcast_module(model, group=self.group)
         D.enable_sync_batchnorm(self.group, enabled=self.sync_batchnorm and D.world_size(self.group) > 1)
         optim_config = model.configure_optimizers()
@@ -144,10 +222,16 @@ class Trainer:
         if world > 1:
             _check_sharded_loader(train_dataloaders, self.group, "train_dataloaders")
         scheduler = self._scheduler_of(optim_config)
+        self.model, self.scheduler = model, scheduler
+        first_epoch = self._resume(ckpt, model, optimizer, scheduler) if ckpt is not None else 0
         graphed = GraphedTrainStep(model.train(), optimizer, reducer=reducer, group=self.group,
                                    gradient_clip_val=self.gradient_clip_val,
                                    gradient_clip_algorithm=self.gradient_clip_algorithm) if self.graphed_steps else None
-        for epoch in range(self.max_epochs):
+        self.graphed_step = graphed
+        for epoch in range(first_epoch, self.max_epochs):
+            if self.should_stop:
+                break
+            self.current_epoch = epoch
             model.train()
             _hook(model, "on_train_epoch_start")
             losses, rows = [], []
@@ -179,8 +263,24 @@ class Trainer:
                 self._validate(model, val_dataloaders, world)
             if self.log_fn:
                 self.log_fn(epoch, {k: v[-1] for k, v in self.history.items() if v})
+            for cb in self.callbacks:
+                cb.on_epoch_end(self)
         reducer.remove()
         return self
+
+    def validate(self, model, val_dataloaders, ckpt_path=None):
+        """pl.Trainer.validate: one validation epoch of `model` (with the weights of `ckpt_path`, if given) outside a fit.
+        Returns {"val_loss": the batch-weighted epoch mean}; what the model's hooks log (AUC_val, f1_val, ...) is in
+        model.logged.  Trainer.history is left as it is."""
+        model.to(self.device)
+        if ckpt_path is not None:
+            ckpt = ckpt_path if isinstance(ckpt_path, dict) else C.load_checkpoint(ckpt_path, map_location="cpu")
+            model.load_state_dict(ckpt["state_dict"], strict=True)
+        self.model = model
+        kept = list(self.history["val_loss"])
+        self._validate(model, val_dataloaders, D.world_size(self.group))
+        new, self.history["val_loss"] = self.history["val_loss"][len(kept):], kept
+        return {"val_loss": new[0] if new else None}
 
     @staticmethod
     def _scheduler_of(cfg):
