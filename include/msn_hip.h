@@ -611,6 +611,18 @@ int msn_grad_norm(const void* table, int n_tensors, int64_t max_numel, float nor
 int msn_grad_scale(const void* table, int n_tensors, int64_t max_numel, const float* coef, msn_stream_t stream);
 int msn_grad_clamp(const void* table, int n_tensors, int64_t max_numel, float clip_value, msn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Gradient accumulation over micro-batches, pl.Trainer(accumulate_grad_batches=k): one launch per micro-batch for the whole
+ * model in place of autograd's one add per parameter.
+ * table: DEVICE array of n_tensors (1 .. 65535) records of four 64-bit words {dst*, acc*, g*, numel} (fp32);
+ * max_numel >= every numel of the table.  Per element dst = g (store: the first micro-batch of a window) or dst = acc + g
+ * (add: one fp32 add, bitwise defined; NaN / inf as the add has them).  dst may be acc, g, or a third buffer.  A record whose
+ * acc is NULL is stored in either mode; a store with dst == g moves nothing.
+ * add: 0 = store, 1 = add.  add_dev: NULL, or a DEVICE int that overrides `add` (non-zero = add) -- a step recorded once in
+ * a HIP graph is replayed at every position of a window, and the word is rewritten on the replaying stream between replays. */
+int msn_grad_accumulate(const void* table, int n_tensors, int64_t max_numel, int add, const int* add_dev,
+                        msn_stream_t stream);
+
 /* Channels-last convolution plumbing for the build-defined ResNet-18 / 1-D CNN encoders (not in the
  * reference): cols[(b,oh,ow)][(c,u,v)] = x[b, oh*sh+u-ph, ow*sw+v-pw, c] (0 outside), column order equal to
  * the flattening of a (C_out, C_in, kh, kw) weight, so conv = msn_sgemm(cols, W) ; col2im is its adjoint

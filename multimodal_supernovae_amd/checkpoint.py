@@ -27,6 +27,11 @@ What resumes exactly (`Trainer.fit(ckpt_path=...)`, tests/test_checkpoint_gpu.py
   * graph-replayed steps with dropout > 0 draw a new seed base at the new capture: the masks after a resume are not those
     of the uninterrupted run -- the same distribution, not the same bits.
 
+Gradient accumulation (`Trainer(accumulate_grad_batches=k)`): checkpoints are written at epoch ends, where the last batch has
+always closed its window and the optimizer has stepped, so NO accumulator state goes into the file; `global_step` counts
+optimizer steps, and a resumed run with the same k is bitwise the uninterrupted one (tests/test_grad_accum_gpu.py).
+Mid-epoch checkpoints -- which would have to carry an open window's partial sums -- are not built.
+
 Several ranks: `save_checkpoint` is a collective (every rank calls it; the RNG states are gathered with
 `all_gather_object`), rank 0 alone writes, and a barrier follows.  On resume rank r takes entry r of the saved RNG
 states; if the world size differs from the saved one the RNG is left as it is, with a warning, and all else loads.

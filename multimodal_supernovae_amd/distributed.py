@@ -184,6 +184,9 @@ class GradientReducer:
     `backward()` and `optimizer.step()` -- reduces buckets that never filled (parameters without a gradient
     this step contribute zeros) and waits for all transfers.  Single-process: every method is a no-op.
     Every rank must build it over the same parameter list.
+    Gradient accumulation: inside `no_sync()` nothing is exchanged; with `accumulator` set (optim.GradAccumulator) the gather of
+    the micro-batch that closes a window writes accumulator + gradient into the bucket's slices, so each bucket's all-reduce
+    still starts under that backward, when its last gradient arrives.
     """
 
     def __init__(self, params, group=None, bucket_bytes=32 << 20, force=False, overlap=True):
@@ -193,6 +196,8 @@ class GradientReducer:
         self.buckets = []
         self._where = {}
         self._handles = []
+        self._sync = True                 # False inside no_sync(): gradients are accumulated locally, nothing is exchanged
+        self.accumulator = None           # optim.GradAccumulator: a bucket's gather is then the last add of the window
         if self.world == 1 and not (force and dist.is_available() and dist.is_initialized()):
             return                                   # force: run the machinery on a one-rank group (RCCL smoke test)
         params = [p for p in params if p.requires_grad]
@@ -221,7 +226,32 @@ class GradientReducer:
                 if overlap:
                     self._handles.append(p.register_post_accumulate_grad_hook(self._on_grad))
 
+    def no_sync(self):
+        """Context manager, as DistributedDataParallel.no_sync(): backward passes (and finish()) inside it issue no gradient
+        collective -- the non-boundary micro-batches of an accumulation window (Trainer(accumulate_grad_batches=k)).  The
+        exchanges of the global-negatives loss are not the reducer's and still run."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def ctx():
+            before, self._sync = self._sync, False
+            try:
+                yield self
+            finally:
+                self._sync = before
+        return ctx()
+
+    def _fill(self, b, have):
+        """The bucket's gradients into its flat buffer: one multi-tensor copy, or with an accumulation window open the
+        window's last add written straight into the slices (views = accumulator + gradient; csrc/grad_accum.hip)."""
+        if self.accumulator is not None and self.accumulator.window_open:
+            self.accumulator.flush_into(b["params"], b["views"])
+        elif have:
+            torch._foreach_copy_([v for v, _ in have], [g for _, g in have])
+
     def _on_grad(self, p):
+        if not self._sync:
+            return
         b = self.buckets[self._where[p]]
         if p.grad is not None and p.grad.is_cuda:
             # towers run on their own streams (models_multimodal.forward): the gradient exists on the stream this hook
@@ -267,8 +297,8 @@ class GradientReducer:
         have = [(v, p.grad) for v, p in zip(b["views"], b["params"]) if p.grad is not None]
         if len(have) < len(b["params"]):
             b["flat"].zero_()
+        self._fill(b, have)
         if have:
-            torch._foreach_copy_([v for v, _ in have], [g for _, g in have])
             if b["flat"].is_cuda:
                 # the old .grad tensors are dropped below; one produced on another tower's side stream must not be
                 # handed back to that stream's allocator pool while THIS stream's copy out of it is still queued
@@ -283,7 +313,7 @@ class GradientReducer:
             p.grad = v
 
     def finish(self):
-        if not self.buckets:
+        if not self.buckets or not self._sync:
             return
         if not self.overlap:
             # deferred form: gather every bucket, then all the all-reduces as ONE exchange (one break of a recorded step)

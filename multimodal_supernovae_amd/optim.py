@@ -7,6 +7,9 @@ constructor, `param_groups`, `state` keys (`step`, `exp_avg`, `exp_avg_sq`), `ze
 
 clip_grad_norm_ / clip_grad_value_ restate torch.nn.utils' functions of the same names on the GPU (multi-tensor HIP
 launches, csrc/grad_clip.hip): the gradient clipping pl.Trainer(gradient_clip_val=...) applies before the step.
+
+grad_accumulate_ / GradAccumulator add the gradients of the micro-batches of pl.Trainer(accumulate_grad_batches=k) with one
+multi-tensor HIP launch per micro-batch (csrc/grad_accum.hip) in place of autograd's one add per parameter.
 """
 import ctypes
 import math
@@ -223,17 +226,54 @@ class RAdam(torch.optim.Optimizer):
 # the table in pinned host memory (two buffers used alternately, as RAdam._staging); under stream capture the table comes
 # from a pinned buffer reserved BEFORE the capture (clip_graph_prepare), is filled at capture time and copied by a copy
 # node of the graph, and the clip coefficient stays on the device -- nothing is written by the host between replays.
-_CLIP_STAGING = [[None, None], [None, None]]
-_CLIP_SLOT = [0]
-_CLIP_RESERVED = []          # pinned tables reserved for captures to come
-_CLIP_CAPTURED = []          # pinned tables read by copy nodes of recorded graphs: kept alive with the process
+class _PinnedTables:
+    """Descriptor tables of a multi-tensor launch on their way to the device (`words` 64-bit words per record).  Eager: two
+    pinned buffers used alternately, one rewritten only after the copy that last read it has completed (its event).  Under
+    stream capture: a pinned buffer reserved BEFORE the capture (reserve), filled at capture time and copied by a copy node
+    of the graph; it is kept alive with the process and never rewritten."""
+
+    def __init__(self, words, what, prepare):
+        self.words, self.what, self.prepare = words, what, prepare
+        self.staging, self.slot = [[None, None], [None, None]], 0
+        self.reserved, self.captured = [], []
+
+    def reserve(self, n_records):
+        self.reserved.append(torch.empty(self.words * max(n_records, 1), dtype=torch.int64).pin_memory())
+
+    def upload(self, words, dev):
+        """The device copy of `words`; the host buffer it is copied from is never rewritten while a copy that reads it may
+        still be pending."""
+        if torch.cuda.is_current_stream_capturing():
+            fit = [i for i, t in enumerate(self.reserved) if t.numel() >= len(words)]
+            if not fit:
+                raise _lib.MsnHipError(f"{self.what} under stream capture needs optim.{self.prepare}(parameters) before the "
+                                       "capture begins (the descriptor table must be pinned in advance)")
+            host = self.reserved.pop(fit[0])
+            self.captured.append(host)
+            host[:len(words)].copy_(torch.tensor(words, dtype=torch.int64))
+            return host[:len(words)].to(dev, non_blocking=True)           # a copy node of the graph (static content)
+        self.slot ^= 1
+        slot = self.staging[self.slot]
+        if slot[1] is not None:
+            slot[1].synchronize()
+        if slot[0] is None or slot[0].numel() < len(words):
+            slot[0] = torch.empty(max(len(words), 1024), dtype=torch.int64).pin_memory()
+        slot[0][:len(words)] = torch.tensor(words, dtype=torch.int64)
+        table = slot[0][:len(words)].to(dev, non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record()
+        return table
+
+
+_CLIP_TABLES = _PinnedTables(2, "gradient clipping", "clip_graph_prepare")
+_ACCUM_TABLES = _PinnedTables(4, "gradient accumulation", "accum_graph_prepare")
 
 
 def clip_graph_prepare(parameters):
     """Call BEFORE a stream capture that will clip the gradients of `parameters` (eager): reserves the pinned descriptor
     table that the capture fills and its graph copies at every replay.  One reservation per clip call recorded."""
     params = [parameters] if torch.is_tensor(parameters) else list(parameters)
-    _CLIP_RESERVED.append(torch.empty(max(2 * len(params), 2), dtype=torch.int64).pin_memory())
+    _CLIP_TABLES.reserve(len(params))
 
 
 def _clip_grads(parameters, what):
@@ -252,33 +292,11 @@ def _clip_grads(parameters, what):
 
 
 def _clip_table(grads):
-    """(device table, max_numel) of the gradients; the host buffer it is copied from is never rewritten while a copy that
-    reads it may still be pending."""
+    """(device table, max_numel) of the gradients."""
     words = []
     for g in grads:
         words += [g.data_ptr(), g.numel()]
-    max_n = max(g.numel() for g in grads)
-    dev = grads[0].device
-    if torch.cuda.is_current_stream_capturing():
-        fit = [i for i, t in enumerate(_CLIP_RESERVED) if t.numel() >= len(words)]
-        if not fit:
-            raise _lib.MsnHipError("gradient clipping under stream capture needs optim.clip_graph_prepare(parameters) "
-                                   "before the capture begins (the descriptor table must be pinned in advance)")
-        host = _CLIP_RESERVED.pop(fit[0])
-        _CLIP_CAPTURED.append(host)
-        host[:len(words)].copy_(torch.tensor(words, dtype=torch.int64))
-        return host[:len(words)].to(dev, non_blocking=True), max_n        # a copy node of the graph (static content)
-    _CLIP_SLOT[0] ^= 1
-    slot = _CLIP_STAGING[_CLIP_SLOT[0]]
-    if slot[1] is not None:
-        slot[1].synchronize()
-    if slot[0] is None or slot[0].numel() < len(words):
-        slot[0] = torch.empty(max(len(words), 1024), dtype=torch.int64).pin_memory()
-    slot[0][:len(words)] = torch.tensor(words, dtype=torch.int64)
-    table = slot[0][:len(words)].to(dev, non_blocking=True)
-    slot[1] = torch.cuda.Event()
-    slot[1].record()
-    return table, max_n
+    return _CLIP_TABLES.upload(words, grads[0].device), max(g.numel() for g in grads)
 
 
 @torch.no_grad()
@@ -328,3 +346,161 @@ def clip_grad_value_(parameters, clip_value, foreach=None):
     table, max_n = _clip_table(grads)
     check(lib().msn_grad_clamp(ptr(table), len(grads), max_n, clip_value, stream_ptr()), "msn_grad_clamp")
     return None
+
+
+# ---- gradient accumulation (pl.Trainer(accumulate_grad_batches=k)) -------------------------------------------------------
+# One multi-tensor launch per micro-batch through a device table {dst*, acc*, g*, numel} per gradient (csrc/grad_accum.hip)
+# in place of autograd's AccumulateGrad (one stock add per parameter).  The table travels as the clipping tables do
+# (_PinnedTables): staged in pinned memory when eager, reserved before a capture (accum_graph_prepare).
+def accum_graph_prepare(parameters):
+    """Call BEFORE a stream capture that will accumulate the gradients of `parameters` (eager): reserves the pinned
+    descriptor table the capture fills.  One reservation per accumulate call recorded."""
+    params = [parameters] if torch.is_tensor(parameters) else list(parameters)
+    _ACCUM_TABLES.reserve(len(params))
+
+
+@torch.no_grad()
+def grad_accumulate_(dsts, accs, grads, add=True, add_dev=None):
+    """dst = acc + g (add) or dst = g (store) for every triple, in ONE launch; fp32, bit for bit torch's add.  accs[i] None:
+    that tensor is stored whatever `add` says.  dst may be acc, g or a third buffer.  `add_dev`: a device int32 tensor whose
+    first word overrides `add` when the launch runs (non-zero = add) -- for a step recorded once and replayed at every position
+    of an accumulation window."""
+    dsts, accs, grads = list(dsts), list(accs), list(grads)
+    if not (len(dsts) == len(accs) == len(grads)):
+        raise ValueError("grad_accumulate_: dsts, accs and grads must have one entry per tensor")
+    if not grads:
+        return
+    for d, a, g in zip(dsts, accs, grads):
+        for t in (d, g) if a is None else (d, a, g):
+            if t.device.type != "cuda":
+                _lib.require_gpu()
+                raise _lib.MsnHipError("grad_accumulate_: gradients must live on the GPU (there is no CPU path)")
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise _lib.MsnHipError(f"grad_accumulate_: contiguous float32 tensors only (got {t.dtype}, "
+                                       f"contiguous={t.is_contiguous()})")
+            if t.numel() != g.numel():
+                raise _lib.MsnHipError("grad_accumulate_: dst, acc and g of a tensor must have the same number of elements")
+    if len({g.device for g in grads}) != 1:
+        raise _lib.MsnHipError("grad_accumulate_: all gradients must live on one GPU")
+    words = []
+    for d, a, g in zip(dsts, accs, grads):
+        words += [d.data_ptr(), 0 if a is None else a.data_ptr(), g.data_ptr(), g.numel()]
+    max_n = max(g.numel() for g in grads)
+    table = _ACCUM_TABLES.upload(words, grads[0].device)
+    check(lib().msn_grad_accumulate(ptr(table), len(grads), max_n, 1 if add else 0, ptr(add_dev), stream_ptr()),
+          "msn_grad_accumulate")
+
+
+class GradAccumulator:
+    """The accumulation buffers of one optimizer's parameters (4 bytes per trainable parameter, views of ONE flat buffer with
+    16-byte aligned slices, allocated at the first micro-batch that needs them) and the state of the window: which parameters
+    hold a partial sum.  Usage per micro-batch, with p.grad set to None before backward so that autograd never adds:
+
+        backward(); acc.accumulate(boundary)         # boundary: the micro-batch after which the optimizer steps
+
+    Not at a boundary: acc = g for a parameter's first gradient of the window, acc += g afterwards.  At a boundary the same,
+    and p.grad is pointed at the accumulator (the sum of the window); a window of one micro-batch leaves p.grad as it is and
+    launches nothing.  A parameter without a gradient in a micro-batch contributes nothing."""
+
+    def __init__(self, params):
+        self.params = [p for p in params if p.requires_grad]
+        self.flat, self.acc = None, {}
+        self.have = set()                 # parameters whose accumulator holds a partial sum of the open window
+        self.selector = None              # device int32 word: the store / add selector of a recorded step
+
+    @property
+    def window_open(self):
+        return bool(self.have)
+
+    def _buffers(self):
+        if self.flat is None and self.params:
+            n = sum((p.numel() + 3) // 4 * 4 for p in self.params)
+            self.flat = torch.empty(n, dtype=torch.float32, device=self.params[0].device)
+            off = 0
+            for p in self.params:
+                self.acc[p] = self.flat[off:off + p.numel()].view(p.shape)
+                off += (p.numel() + 3) // 4 * 4
+        return self.acc
+
+    def _check(self, p):
+        if p.device.type != "cuda":
+            _lib.require_gpu()
+            raise _lib.MsnHipError("gradient accumulation: parameters must live on the GPU (there is no CPU path)")
+        if p.dtype != torch.float32:
+            raise _lib.MsnHipError(f"gradient accumulation: float32 parameters only (got {p.dtype})")
+
+    @torch.no_grad()
+    def accumulate(self, boundary):
+        with_grad = [p for p in self.params if p.grad is not None]
+        if boundary and not self.have:
+            return                                        # a window of one: p.grad is the sum already
+        for p in with_grad:
+            self._check(p)
+        acc = self._buffers()
+        if with_grad:
+            cur = torch.cuda.current_stream(with_grad[0].device)
+            for p in with_grad:                           # a gradient of a tower's side stream is freed before the next backward
+                p.grad.record_stream(cur)
+            grad_accumulate_([acc[p] for p in with_grad], [acc[p] if p in self.have else None for p in with_grad],
+                             [p.grad for p in with_grad], add=True)
+            self.have.update(with_grad)
+        if boundary:
+            self.point_grads()
+            self.have.clear()
+
+    @torch.no_grad()
+    def record(self):
+        """Under stream capture: the launch of one micro-batch with the store / add selector read from the device word, over
+        the parameters that have a gradient now; their .grad is pointed at the accumulators, which is what the clipping and
+        the optimizer recorded behind it read.  Nothing executes while recording, so the window's state is left alone.
+        Returns the parameters recorded."""
+        with_grad = [p for p in self.params if p.grad is not None]
+        for p in with_grad:
+            self._check(p)
+        acc = self._buffers()
+        if with_grad:
+            grad_accumulate_([acc[p] for p in with_grad], [acc[p] for p in with_grad], [p.grad for p in with_grad],
+                             add=True, add_dev=self.selector)
+        for p in with_grad:
+            p.grad = acc[p]
+        return with_grad
+
+    def point_grads(self):
+        """p.grad = the accumulator, for every parameter that holds a sum."""
+        for p in self.have:
+            p.grad = self.acc[p]
+
+    @torch.no_grad()
+    def flush_into(self, params, views):
+        """The last add of a window written into a third buffer: views[i] = acc + p.grad for the parameters given (a gradient
+        bucket's slices); a parameter without a gradient in this micro-batch hands over its partial sum as it is, one
+        without either is left alone.  The parameters leave the window."""
+        todo = []                                         # (dst, acc | None, g)
+        for p, v in zip(params, views):
+            if p.grad is not None:
+                self._check(p)
+                todo.append((v, self.acc[p] if p in self.have else None, p.grad))
+            elif p in self.have:
+                todo.append((v, None, self.acc[p]))       # no gradient now: the partial sum itself, stored
+        if todo:
+            grad_accumulate_([d for d, _, _ in todo], [a for _, a, _ in todo], [g for _, _, g in todo], add=True)
+        self.have.difference_update(params)
+
+    def graph_prepare(self):
+        """Call BEFORE the capture (eager): the buffers, the selector word with its two pinned constants, the pinned table."""
+        self._buffers()
+        dev = self.params[0].device
+        self.selector = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._consts = [torch.tensor([0], dtype=torch.int32).pin_memory(), torch.tensor([1], dtype=torch.int32).pin_memory()]
+        accum_graph_prepare(self.params)
+
+    def graph_pre_replay(self):
+        """Enqueued on the replaying stream BEFORE a replay (ordered against the previous replay's read and this one's): the
+        selector says whether the window is open.  The pinned constants are never rewritten."""
+        self.selector.copy_(self._consts[1 if self.have else 0], non_blocking=True)
+
+    def graph_post_replay(self, recorded, boundary):
+        if boundary:
+            self.have.clear()
+        else:
+            self.have.update(recorded)

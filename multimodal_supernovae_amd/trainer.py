@@ -108,6 +108,37 @@ def _clip_gradients(optimizer, clip):
         optim.clip_grad_value_(_clip_params(optimizer), val)
 
 
+def _accumulate_config(accumulate_grad_batches):
+    """pl.Trainer's accumulate_grad_batches -> k: an int >= 1 (1 = every batch is an optimizer step)."""
+    k = accumulate_grad_batches
+    if isinstance(k, dict):
+        raise ValueError("accumulate_grad_batches: Lightning's dict form (and GradientAccumulationScheduler) is out of scope "
+                         "here; pass one int >= 1")
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"accumulate_grad_batches must be an int >= 1 (got {accumulate_grad_batches!r})")
+    return k
+
+
+def _closes_window(position, k, last):
+    """Lightning's rule: the optimizer steps after micro-batch `position` (0-based, counted from the start of the epoch)
+    when (position + 1) % k == 0, and after the last batch of the epoch."""
+    return (position + 1) % k == 0 or bool(last)
+
+
+def _with_last(loader):
+    """(batch_idx, batch, is the last of the epoch) by looking one batch ahead: the loader may have no len()."""
+    it = iter(loader)
+    try:
+        cur = next(it)
+    except StopIteration:
+        return
+    idx = 0
+    for nxt in it:
+        yield idx, cur, False
+        cur, idx = nxt, idx + 1
+    yield idx, cur, True
+
+
 _SEEDS = {}
 
 
@@ -119,9 +150,31 @@ def _backward_seed(loss):
     return _SEEDS[key]
 
 
+def _accumulate_seed(loss, k):
+    """d (loss / k) / d loss = 1 / k as a cached device tensor beside _backward_seed: the fp32 quotient 1 / k that the
+    backward of `loss / k` forms, made once on the device."""
+    key = (loss.device, loss.dtype, tuple(loss.shape), k)
+    if key not in _SEEDS:
+        _SEEDS[key] = torch.ones(loss.shape, dtype=loss.dtype, device=loss.device) / k
+    return _SEEDS[key]
+
+
 class Trainer:
+    """pl.Trainer's arguments as far as the reference's scripts and their users rely on them.
+
+    accumulate_grad_batches=k (an int >= 1, Lightning 2.x's meaning): backward runs on loss / k, the gradients of k
+    consecutive batches are added in batch order, and the optimizer steps when (batch_idx + 1) % k == 0 and on the last
+    batch of the epoch (a shorter last window still divides by k; windows restart every epoch).  At a boundary: last add ->
+    gradient all-reduce -> clipping -> optimizer.step(); on the other micro-batches nothing is exchanged but the loss's own
+    embeddings.  global_step counts optimizer steps; step_losses, history and model.logged keep the undivided loss of
+    every micro-batch.  The adds are one multi-tensor launch per micro-batch (optim.GradAccumulator), never autograd's.
+    With the contrastive losses the negatives of a pair are those of ITS micro-batch: k micro-batches of B pairs are not a
+    batch of k B pairs (Lightning behaves the same way); for losses that are a mean over rows (ClipMLP, masked
+    pretraining) they are, up to the order of the sums.  k = 1 is the plain path: no buffer, no launch."""
+
     def __init__(self, max_epochs=1, device=None, group=None, log_fn=None, sync_batchnorm=False, graphed_steps=False,
-                 gradient_clip_val=None, gradient_clip_algorithm=None, callbacks=None):
+                 gradient_clip_val=None, gradient_clip_algorithm=None, callbacks=None, accumulate_grad_batches=1):
+        self.accumulate_grad_batches = _accumulate_config(accumulate_grad_batches)
         # pl.Trainer(gradient_clip_val=..., gradient_clip_algorithm=...): clip the all-reduced gradients before the step
         self.clip = _clip_config(gradient_clip_val, gradient_clip_algorithm)
         self.gradient_clip_val, self.gradient_clip_algorithm = gradient_clip_val, gradient_clip_algorithm
@@ -140,7 +193,7 @@ class Trainer:
                           + [c for c in callbacks if isinstance(c, C.ModelCheckpoint)])
         self.current_epoch = 0
         self.should_stop = False
-        self.model = self.optimizer = self.scheduler = self.graphed_step = None
+        self.model = self.optimizer = self.scheduler = self.graphed_step = self.reducer = self.accumulator = None
 
     # ---- what callbacks see ----------------------------------------------------------------------------------------
     @property
@@ -218,6 +271,7 @@ class Trainer:
         self.optimizer = optimizer
         # bucket all-reduces run under backward; a graph-replayed step reduces every bucket after backward (deferred form)
         reducer = D.GradientReducer(model.parameters(), group=self.group, overlap=not self.graphed_steps)
+        self.reducer = reducer
         world = D.world_size(self.group)
         if world > 1:
             _check_sharded_loader(train_dataloaders, self.group, "train_dataloaders")
@@ -226,8 +280,15 @@ class Trainer:
         first_epoch = self._resume(ckpt, model, optimizer, scheduler) if ckpt is not None else 0
         graphed = GraphedTrainStep(model.train(), optimizer, reducer=reducer, group=self.group,
                                    gradient_clip_val=self.gradient_clip_val,
-                                   gradient_clip_algorithm=self.gradient_clip_algorithm) if self.graphed_steps else None
+                                   gradient_clip_algorithm=self.gradient_clip_algorithm,
+                                   accumulate_grad_batches=self.accumulate_grad_batches) if self.graphed_steps else None
         self.graphed_step = graphed
+        k = self.accumulate_grad_batches
+        accum = None
+        if k > 1 and graphed is None:
+            accum = optim.GradAccumulator(_clip_params(optimizer))
+            reducer.accumulator = accum
+        self.accumulator = accum
         for epoch in range(first_epoch, self.max_epochs):
             if self.should_stop:
                 break
@@ -235,24 +296,27 @@ class Trainer:
             model.train()
             _hook(model, "on_train_epoch_start")
             losses, rows = [], []
-            for batch_idx, batch in enumerate(train_dataloaders):
-                batch = _to_device(batch, self.device)
-                rows.append(_batch_rows(batch))
-                if graphed is not None:
-                    losses.append(graphed(batch, batch_idx).detach().clone())   # the graph's loss tensor is overwritten by the next replay
+            if k > 1:
+                self._accumulating_epoch(model, optimizer, reducer, accum, graphed, train_dataloaders, losses, rows)
+            else:
+                for batch_idx, batch in enumerate(train_dataloaders):
+                    batch = _to_device(batch, self.device)
+                    rows.append(_batch_rows(batch))
+                    if graphed is not None:
+                        losses.append(graphed(batch, batch_idx).detach().clone())   # the graph's loss tensor is overwritten by the next replay
+                        self.global_step += 1
+                        continue
+                    optimizer.zero_grad(set_to_none=True)
+                    with markers.range("forward + loss"):
+                        loss = model.training_step(batch, batch_idx)
+                    with markers.range("backward"):
+                        loss.backward(_backward_seed(loss))
+                    reducer.finish()
+                    _clip_gradients(optimizer, self.clip)
+                    with markers.range("optimiser (RAdam)"):
+                        optimizer.step()
+                    losses.append(loss.detach())
                     self.global_step += 1
-                    continue
-                optimizer.zero_grad(set_to_none=True)
-                with markers.range("forward + loss"):
-                    loss = model.training_step(batch, batch_idx)
-                with markers.range("backward"):
-                    loss.backward(_backward_seed(loss))
-                reducer.finish()
-                _clip_gradients(optimizer, self.clip)
-                with markers.range("optimiser (RAdam)"):
-                    optimizer.step()
-                losses.append(loss.detach())
-                self.global_step += 1
             _hook(model, "on_train_epoch_end")
             self.step_losses += losses
             if losses:
@@ -267,6 +331,49 @@ class Trainer:
                 cb.on_epoch_end(self)
         reducer.remove()
         return self
+
+    def _accumulating_epoch(self, model, optimizer, reducer, accum, graphed, loader, losses, rows):
+        """The batches of one epoch with accumulate_grad_batches > 1: the window's rule lives in _closes_window, and
+        global_step advances when a micro-batch stepped the optimizer (the graphed step says whether its call did)."""
+        k = self.accumulate_grad_batches
+        for batch_idx, batch, last in _with_last(loader):
+            batch = _to_device(batch, self.device)
+            rows.append(_batch_rows(batch))
+            if graphed is not None:
+                losses.append(graphed(batch, batch_idx, last_batch=last).detach().clone())
+                stepped = graphed.stepped
+            else:
+                stepped = _closes_window(batch_idx, k, last)
+                losses.append(self._micro_batch(model, optimizer, reducer, accum, batch, batch_idx, stepped))
+            self.global_step += int(stepped)
+
+    def _micro_batch(self, model, optimizer, reducer, accum, batch, batch_idx, boundary):
+        """One micro-batch of an accumulation window (accumulate_grad_batches > 1), eager: backward on loss / k into fresh
+        gradients, then ONE launch adds them to the window's sum; at a boundary the all-reduce, the clipping and the step."""
+        k = self.accumulate_grad_batches
+        optimizer.zero_grad(set_to_none=True)             # autograd never adds: every backward writes fresh gradients
+        overlapped = bool(reducer.buckets) and reducer.overlap
+        with markers.range("forward + loss"):
+            loss = model.training_step(batch, batch_idx)
+        if not boundary:
+            with reducer.no_sync(), markers.range("backward"):
+                loss.backward(_accumulate_seed(loss, k))
+            with markers.range("gradient accumulation"):
+                accum.accumulate(False)
+            return loss.detach()
+        with markers.range("backward"):
+            loss.backward(_accumulate_seed(loss, k))
+        if overlapped:
+            reducer.finish()           # every bucket's gather was the window's last add, issued under backward (or here)
+            accum.have.clear()
+        else:
+            with markers.range("gradient accumulation"):
+                accum.accumulate(True)
+            reducer.finish()
+        _clip_gradients(optimizer, self.clip)
+        with markers.range("optimiser (RAdam)"):
+            optimizer.step()
+        return loss.detach()
 
     def validate(self, model, val_dataloaders, ckpt_path=None):
         """pl.Trainer.validate: one validation epoch of `model` (with the weights of `ckpt_path`, if given) outside a fit.
@@ -326,11 +433,14 @@ class _RecordedStep:
     """A training step recorded as HIP-graph SEGMENTS separated by host-driven exchanges.  While it records it is installed
     as distributed.SEGMENTED_CAPTURE: every collective issued through distributed.py closes the segment under capture,
     is remembered (not run: see exchange) and opens the next segment.  All segments allocate from ONE private pool, so a tensor produced in one segment and consumed in a
-    later one keeps its address.  replay() = segment, exchange, segment, ... in the recorded order."""
+    later one keeps its address.  replay() = segment, exchange, segment, ... in the recorded order.
+    With gradient accumulation the items behind mark_boundary() (gradient all-reduce, clipping, RAdam) run only in a replay
+    that closes a window: replay(boundary=False) stops in front of them."""
 
     def __init__(self, device):
         self.device = device
         self.items = []                 # ("graph", CUDAGraph) | ("call", fn)
+        self.boundary_from = None       # index of the first item that runs at a window's boundary only (None: all run always)
         self.pool = torch.cuda.graph_pool_handle()
         self.cur = None
 
@@ -353,6 +463,13 @@ class _RecordedStep:
         self.items.append(("call", fn))
         self.begin()
 
+    def mark_boundary(self):
+        """Everything recorded from here on belongs to the optimizer step: close the segment of the micro-batch."""
+        self.cur.capture_end()
+        self.items.append(("graph", self.cur))
+        self.boundary_from = len(self.items)
+        self.begin()
+
     def end(self):
         self.cur.capture_end()
         self.items.append(("graph", self.cur))
@@ -369,8 +486,9 @@ class _RecordedStep:
         self.cur = None
         self.items = []
 
-    def replay(self):
-        for kind, x in self.items:
+    def replay(self, boundary=True):
+        items = self.items if boundary or self.boundary_from is None else self.items[:self.boundary_from]
+        for kind, x in items:
             if kind == "graph":
                 x.replay()
             else:
@@ -388,6 +506,13 @@ class _RecordedStep:
 class GraphedTrainStep:
     """One training step (zero_grad -> training_step -> backward -> gradient all-reduce -> [gradient clipping] -> RAdam)
     recorded as HIP graphs and replayed.
+
+    accumulate_grad_batches=k > 1 (Trainer's meaning): the towers are still recorded ONCE, as [forward, backward, one
+    accumulate launch | gradient all-reduce, clipping, RAdam]; a call replays the first part, and the second part too when it
+    closes a window -- every k-th call, and a call with last_batch=True, after which the count restarts.  The accumulate launch
+    reads store / add from a device word written on the replaying stream in front of each replay.
+    The reducer must be the deferred form (overlap=False, refused otherwise at construction): a hook-driven one would gather
+    the last micro-batch's gradients alone and start their all-reduce before the window's sum is formed.
 
     The reference's own batch sizes (32 ... 256) -- and the 128 ... 256 rows a rank keeps when the global batch of 1024 is
     spread over 4 or 8 GPUs -- leave the GPU waiting for the host: a Maven step issues ~1300 launches and takes ~10 ms of
@@ -411,7 +536,8 @@ class GraphedTrainStep:
     """
 
     def __init__(self, model, optimizer, warmup=3, concurrent_towers=None, reducer=None, group=None, gradient_clip_val=None,
-                 gradient_clip_algorithm=None):
+                 gradient_clip_algorithm=None, accumulate_grad_batches=1):
+        self.k = _accumulate_config(accumulate_grad_batches)
         self.clip = _clip_config(gradient_clip_val, gradient_clip_algorithm)    # as Trainer's: None = no clipping
         self.concurrent_towers = concurrent_towers      # None: as the model is set (towers fork / join inside the graph)
         self.group = group
@@ -424,6 +550,29 @@ class GraphedTrainStep:
         self.reducer = reducer
         self.model, self.optimizer, self.warmup = model, optimizer, int(warmup)
         self.calls, self.graph, self.static, self.loss = 0, None, None, None
+        # accumulate_grad_batches > 1: the window's buffers (shared by eager calls and replays), the position in the window
+        self.accum = optim.GradAccumulator(_clip_params(optimizer)) if self.k > 1 and optimizer is not None else None
+        self._micro, self._recorded, self._eager_steps = 0, [], 0
+        self.stepped = True               # whether the last call stepped the optimizer (always, without accumulation)
+
+    def _eager_micro(self, batch, batch_idx, boundary):
+        """One micro-batch of an accumulation window, eager (warm-up calls, batches of another shape): into the same buffers
+        as the replays."""
+        self.optimizer.zero_grad(set_to_none=True)
+        loss = self.model.training_step(batch, batch_idx)
+        if boundary or self.reducer is None:
+            loss.backward(_accumulate_seed(loss, self.k))
+        else:
+            with self.reducer.no_sync():
+                loss.backward(_accumulate_seed(loss, self.k))
+        self.accum.accumulate(boundary)
+        if boundary:
+            if self.reducer is not None:
+                self.reducer.finish()
+            _clip_gradients(self.optimizer, self.clip)
+            self.optimizer.step()
+            self._eager_steps += 1
+        return loss
 
     def _eager(self, batch, batch_idx=0):
         self.optimizer.zero_grad(set_to_none=True)
@@ -449,6 +598,8 @@ class GraphedTrainStep:
         self.optimizer.graph_prepare()        # device copies of the hyper-parameters and the step count (eager)
         if self.clip is not None:
             optim.clip_graph_prepare(_clip_params(self.optimizer))    # the clip's pinned descriptor table (eager)
+        if self.accum is not None:
+            self.accum.graph_prepare()        # the selector word and the accumulate launch's pinned table (eager)
         import gc
         gc.collect()                          # no autograd graph of an earlier step (bound to other streams) may survive
         device = self.static_device()
@@ -475,7 +626,12 @@ class GraphedTrainStep:
                 rec.begin()
                 ops.graph_seed_advance()
                 self.loss = model.training_step(self.static, 0)
-                self.loss.backward()
+                if self.accum is None:
+                    self.loss.backward()
+                else:
+                    self.loss.backward(_accumulate_seed(self.loss, self.k))
+                    self._recorded = self.accum.record()      # store / add by the device word; .grad = the window's sums
+                    rec.mark_boundary()                       # behind it: what runs only when a window closes
                 if self.reducer is not None:
                     self.reducer.finish()         # several ranks: the clip below runs in the last segment, after the exchange
                 _clip_gradients(self.optimizer, self.clip)
@@ -501,12 +657,54 @@ class GraphedTrainStep:
             self.static, self.loss = None, None
             raise failure
         self.graph = rec
+        self._final_grads = [(p, p.grad) for p in self._recorded]     # the accumulators, or the reducer's bucket slices
+        self._recorded_set = set(self._recorded)
 
     def static_device(self):
         return next(t.device for t in self.static if torch.is_tensor(t))
 
-    def __call__(self, batch, batch_idx=0):
+    def _call_accumulating(self, batch, batch_idx, last_batch):
+        """__call__ with accumulate_grad_batches > 1: `boundary` = this micro-batch closes its window."""
+        boundary = self.stepped = _closes_window(self._micro, self.k, last_batch)
+        self._micro = 0 if last_batch else self._micro + 1
+        if self.graph is None:
+            # the recording needs RAdam's moment buffers: at least one eager OPTIMIZER step, not only `warmup` calls
+            if self.calls <= self.warmup or self._eager_steps == 0:
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    loss = self._eager_micro(batch, batch_idx, boundary)
+                torch.cuda.current_stream().wait_stream(side)
+                return loss
+            self._capture(batch)
+        same = len(batch) == len(self.static) and all(
+            (torch.is_tensor(d) and torch.is_tensor(s_) and d.shape == s_.shape) or (d is None and s_ is None)
+            for d, s_ in zip(self.static, batch))
+        # the recorded launch applies ONE store / add word to every recorded parameter: an open window whose partial sums are
+        # not exactly theirs (an eager micro-batch of another shape gave other parameters a gradient) goes on eagerly
+        if not same or (self.accum.have and self.accum.have != self._recorded_set):
+            loss = self._eager_micro(batch, batch_idx, boundary)
+            if boundary:
+                self.optimizer.graph_note_eager_step()
+            return loss
+        for dst, src in zip(self.static, batch):
+            if torch.is_tensor(dst):
+                dst.copy_(src, non_blocking=True)
+        self.accum.graph_pre_replay()
+        if boundary:
+            self.optimizer.graph_pre_replay()     # RAdam's device step count advances once per optimizer step
+        self.graph.replay(boundary)
+        self.accum.graph_post_replay(self._recorded, boundary)
+        if boundary:
+            for p, g in self._final_grads:        # after the step p.grad holds the accumulated (clipped) gradient
+                p.grad = g
+        return self.loss
+
+    def __call__(self, batch, batch_idx=0, last_batch=False):
+        """`last_batch`: this is the last batch of the epoch -- with accumulate_grad_batches > 1 it closes its window."""
         self.calls += 1
+        if self.accum is not None:
+            return self._call_accumulating(batch, batch_idx, last_batch)
         if self.graph is None:
             if self.calls <= self.warmup:
                 side = torch.cuda.Stream()
