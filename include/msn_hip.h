@@ -623,6 +623,25 @@ int msn_grad_clamp(const void* table, int n_tensors, int64_t max_numel, float cl
 int msn_grad_accumulate(const void* table, int n_tensors, int64_t max_numel, int add, const int* add_dev,
                         msn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Weight averaging over training (Lightning's WeightAveraging / StochasticWeightAveraging, torch's AveragedModel): one launch
+ * per optimizer step for every averaged tensor.
+ * table: DEVICE array of n_tensors (1 .. 65535) records of three 64-bit words {avg*, p*, numel} (fp32);
+ * max_numel >= every numel of the table.  state: two DEVICE 64-bit words {n_averaged, active}.
+ *   active == 0: the launch changes nothing, neither the averages nor n_averaged;
+ *   n_averaged == 0: avg = p, a copy of the bits;
+ *   otherwise d = p - avg, avg = fmaf(w, d, avg), one rounding each, with
+ *     MSN_AVG_EMA  w = weight = (float)(1.0 - decay), rounded once by the caller; 0 <= weight <= 1;
+ *     MSN_AVG_SWA  w = (float)(1.0 / (double)(n_averaged + 1)), formed on the device (weight is ignored);
+ *   then n_averaged += 1 (when active), by a one-thread kernel behind the main one on `stream`.
+ *   MSN_AVG_SWAP  avg and p exchange their bits (twice is the identity); state may be NULL and is left alone.
+ * `active` is meant to be rewritten on the replaying stream between the replays of a step recorded in a HIP graph. */
+#define MSN_AVG_EMA 0
+#define MSN_AVG_SWA 1
+#define MSN_AVG_SWAP 2
+int msn_weight_average(const void* table, int n_tensors, int64_t max_numel, int mode, float weight, long long* state,
+                       msn_stream_t stream);
+
 /* Channels-last convolution plumbing for the build-defined ResNet-18 / 1-D CNN encoders (not in the
  * reference): cols[(b,oh,ow)][(c,u,v)] = x[b, oh*sh+u-ph, ow*sw+v-pw, c] (0 outside), column order equal to
  * the flattening of a (C_out, C_in, kh, kw) weight, so conv = msn_sgemm(cols, W) ; col2im is its adjoint

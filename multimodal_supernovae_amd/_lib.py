@@ -161,6 +161,7 @@ SIGNATURES = {
     "msn_grad_scale": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_ptr]),
     "msn_grad_clamp": (c_int, [c_ptr, c_int, c_i64, c_f32, c_ptr]),
     "msn_grad_accumulate": (c_int, [c_ptr, c_int, c_i64, c_int, c_ptr, c_ptr]),
+    "msn_weight_average": (c_int, [c_ptr, c_int, c_i64, c_int, c_f32, c_ptr, c_ptr]),
     "msn_set_attention_path": (c_int, [c_int]),
     "msn_set_attention_fused": (c_int, [c_int]),
     "msn_set_attention_planes": (c_int, [c_int]),

@@ -3,6 +3,7 @@
     save_checkpoint(path, model, optimizer=None, scheduler=None, extra=None)     load_checkpoint(path, map_location="cpu")
     ModelCheckpoint(dirpath, filename=None, monitor=None, mode="min", save_top_k=1, save_last=False, every_n_epochs=1)
     EarlyStopping(monitor, mode="min", patience=3, min_delta=0.0, check_finite=True)
+    WeightAveraging(avg="ema", decay=0.999, update_on="step", ...)              an EMA / SWA of the weights (optim.AveragedWeights)
     trainer.Trainer(callbacks=[...]).fit(model, train, val, ckpt_path=...)      Trainer.save_checkpoint(path)
 
 The file is a `torch.save` of ONE plain dict with the top-level keys `epoch`, `global_step`, `pytorch-lightning_version`,
@@ -31,6 +32,10 @@ Gradient accumulation (`Trainer(accumulate_grad_batches=k)`): checkpoints are wr
 always closed its window and the optimizer has stepped, so NO accumulator state goes into the file; `global_step` counts
 optimizer steps, and a resumed run with the same k is bitwise the uninterrupted one (tests/test_grad_accum_gpu.py).
 Mid-epoch checkpoints -- which would have to carry an open window's partial sums -- are not built.
+
+Weight averaging (`WeightAveraging`): `state_dict` stays the LIVE model's -- `Trainer.save_checkpoint` swaps the live weights back in
+around the write if the model holds its average just then -- and the average travels in `callbacks["WeightAveraging"]`
+(tensors by parameter name, the number of updates); a resumed eager run continues the average bitwise.
 
 Several ranks: `save_checkpoint` is a collective (every rank calls it; the RNG states are gathered with
 `all_gather_object`), rank 0 alone writes, and a barrier follows.  On resume rank r takes entry r of the saved RNG
@@ -228,6 +233,29 @@ class Callback:
     def on_resume(self, trainer):
         pass
 
+    # The hooks below are no-ops unless a callback overrides them (WeightAveraging does).  Per fit: on_fit_start (the model is on
+    # its device; before a checkpoint is loaded into it) ... on_fit_end (also after early stopping); per optimizer step:
+    # on_optimizer_step, after optimizer.step() and the increment of trainer.global_step, eager or replayed; per epoch:
+    # on_train_epoch_end (before the scheduler step and validation), on_validation_start / on_validation_end around the validation
+    # epoch -- inside fit and in Trainer.validate.
+    def on_fit_start(self, trainer):
+        pass
+
+    def on_optimizer_step(self, trainer):
+        pass
+
+    def on_train_epoch_end(self, trainer):
+        pass
+
+    def on_validation_start(self, trainer):
+        pass
+
+    def on_validation_end(self, trainer):
+        pass
+
+    def on_fit_end(self, trainer):
+        pass
+
     def state_dict(self):
         return {}
 
@@ -380,6 +408,155 @@ class EarlyStopping(Callback):
         self.wait_count, self.stopped_epoch = int(state["wait_count"]), int(state["stopped_epoch"])
         self.best_score = float(state["best_score"])
         self.stopped = bool(state.get("stopped", self.wait_count >= self.patience))
+
+
+def averaging_due(global_step, start_step=0, every_n_steps=1):
+    """WeightAveraging(update_on="step")'s rule: the average is updated after optimizer step number `global_step` (1-based: the
+    Trainer's global_step after its increment) when it lies behind `start_step` and on the every_n_steps grid counted from it."""
+    return global_step > start_step and (global_step - start_step) % every_n_steps == 0
+
+
+def _one_weight_averaging(callbacks):
+    found = [cb for cb in callbacks if isinstance(cb, WeightAveraging)]
+    if len(found) > 1:
+        raise ValueError(f"callbacks hold {len(found)} WeightAveraging callbacks: one model has one average (they would swap the "
+                         "same weights twice for validation and share one key in the checkpoint)")
+    return found[0] if found else None
+
+
+class WeightAveraging(Callback):
+    """An average of the weights over training, modelled on Lightning's WeightAveraging / StochasticWeightAveraging callbacks
+    and torch's AveragedModel; the arithmetic and the memory are optim.AveragedWeights' (one HIP launch per update).
+
+      avg="ema" | "swa", decay    what is averaged (AveragedWeights)
+      update_on="step"            after optimizer step s (= trainer.global_step after its increment) when averaging_due(s,
+                                  start_step, every_n_steps); with accumulate_grad_batches=k that is at window boundaries only.
+                                  Under graphed_steps the update is the last launch of the recorded optimizer part and the rule
+                                  acts through the average's device word `active`
+      update_on="epoch"           one (eager) update at the end of every training epoch >= start_epoch, before the scheduler
+                                  step and validation: classic SWA with avg="swa" (no SWALR annealing: the user's own scheduler)
+      use_buffers                 also average BatchNorm's running statistics (AveragedWeights)
+      validate_with_average       with an average in hand (n_averaged > 0) the weights are swapped in for every validation
+                                  epoch and swapped back after it, bit for bit: ModelCheckpoint / EarlyStopping monitor the
+                                  averaged weights' val_loss / AUC_val
+      apply_at_end                at the end of fit (early stopping included) one swap: the model holds the averaged weights,
+                                  `averager.swapped` is True, restore_live(trainer) undoes it; a later fit swaps back first
+
+    Checkpoints: `state_dict` stays the LIVE model's, so a resume stays what it is; the average travels in
+    callbacks[state_key] and on_resume puts it back.  load_average(model, ckpt) loads a file's averaged weights for inference.
+    Data parallel: no collective -- after the gradient all-reduce every rank steps to identical parameters, hence to identical
+    averages; rank 0 writes them.  Not built: SWALR, a timm-style decay warm-up, mid-epoch checkpoints."""
+
+    def __init__(self, avg="ema", decay=0.999, update_on="step", start_step=0, every_n_steps=1, start_epoch=0, use_buffers=False,
+                 validate_with_average=True, apply_at_end=True):
+        from . import optim
+        self.avg, self.decay = optim._avg_config(avg, decay)
+        if update_on not in ("step", "epoch"):
+            raise ValueError(f"update_on must be 'step' or 'epoch' (got {update_on!r})")
+        for name, v, low in (("start_step", start_step, 0), ("every_n_steps", every_n_steps, 1), ("start_epoch", start_epoch, 0)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < low:
+                raise ValueError(f"{name} must be an int >= {low} (got {v!r})")
+        self.update_on, self.start_step, self.every_n_steps, self.start_epoch = update_on, start_step, every_n_steps, start_epoch
+        self.use_buffers, self.validate_with_average, self.apply_at_end = bool(use_buffers), bool(validate_with_average), bool(apply_at_end)
+        self.averager = None              # optim.AveragedWeights of the model being fitted (built in on_fit_start)
+        self._model = None
+        self._pending = None              # a state loaded before the averager exists
+        self._swapped_for_validation = False
+
+    def due(self, global_step):
+        return averaging_due(global_step, self.start_step, self.every_n_steps)
+
+    @property
+    def in_graph(self):
+        """Whether a graph-replayed step records the update itself (then on_optimizer_step launches nothing)."""
+        return self.update_on == "step"
+
+    def on_fit_start(self, trainer):
+        from . import optim
+        if self.averager is None or self._model is not trainer.model:
+            self.averager = optim.AveragedWeights(trainer.model, avg=self.avg, decay=self.decay, use_buffers=self.use_buffers)
+            self._model = trainer.model
+            if self._pending is not None:
+                self.averager.load_state_dict(self._pending)
+                self._pending = None
+        else:
+            self.averager.graph_prepare()     # the same model again: look once more where its weights live
+        if self.averager.swapped:         # an earlier fit applied the average at its end: training goes on from the live weights
+            self.averager.swap()
+
+    def on_optimizer_step(self, trainer):
+        if self.update_on != "step" or trainer.graphed_step is not None:
+            return                        # a graphed step averages inside its recording (and in its own eager calls)
+        if self.due(trainer.global_step):
+            self.averager.set_active(True)        # a graphed fit before this one may have left the device word off
+            self.averager.update()
+
+    def on_train_epoch_end(self, trainer):
+        if self.update_on == "epoch" and trainer.current_epoch >= self.start_epoch:
+            self.averager.set_active(True)
+            self.averager.update()
+
+    def _holds(self, trainer):
+        return self.averager is not None and self._model is trainer.model
+
+    def on_validation_start(self, trainer):
+        if self.validate_with_average and self._holds(trainer) and self.averager.n_averaged > 0 and not self.averager.swapped:
+            self.averager.swap()
+            self._swapped_for_validation = True
+
+    def on_validation_end(self, trainer):
+        if self._swapped_for_validation:
+            self.averager.swap()
+            self._swapped_for_validation = False
+
+    def on_fit_end(self, trainer):
+        if self.apply_at_end and self.averager.n_averaged > 0 and not self.averager.swapped:
+            self.averager.swap()
+
+    def restore_live(self, trainer=None):
+        """Undo apply_at_end: the model holds the live weights of the last step again, bit for bit."""
+        if self.averager is not None and self.averager.swapped:
+            self.averager.swap()
+
+    def on_resume(self, trainer):
+        if self.averager is not None and self.averager.swapped:
+            self.averager.swap()          # the file's state_dict held the averages and the buffer the live values
+
+    def state_dict(self):
+        inner = self.averager.state_dict() if self.averager is not None else self._pending
+        return {"avg": self.avg, "decay": self.decay, "update_on": self.update_on, "start_step": self.start_step,
+                "every_n_steps": self.every_n_steps, "start_epoch": self.start_epoch, "use_buffers": self.use_buffers,
+                "average": inner}
+
+    def load_state_dict(self, state):
+        if state.get("avg", self.avg) != self.avg:
+            raise ValueError(f"WeightAveraging: the checkpoint's average was made with avg={state['avg']!r}, this callback "
+                             f"averages with avg={self.avg!r}")
+        inner = state.get("average")
+        if inner is None:
+            return
+        if self.averager is not None:
+            self.averager.load_state_dict(inner)
+        else:
+            self._pending = inner
+
+    @staticmethod
+    def load_average(model, ckpt, map_location="cpu"):
+        """The averaged weights of a checkpoint (a path, or the dict load_checkpoint returned) into `model`: its state_dict, then
+        every averaged tensor over it.  Returns the number of updates the average holds."""
+        ckpt = ckpt if isinstance(ckpt, dict) else load_checkpoint(ckpt, map_location=map_location)
+        keys = [k for k in ckpt["callbacks"] if k.startswith("WeightAveraging")]
+        if not keys or ckpt["callbacks"][keys[0]].get("average") is None:
+            raise ValueError("the checkpoint holds no weight average (no WeightAveraging callback wrote into it)")
+        inner = ckpt["callbacks"][keys[0]]["average"]
+        model.load_state_dict(ckpt["state_dict"], strict=True)
+        if not inner["swapped"] and int(inner["n_averaged"]) > 0:      # swapped: the file's state_dict IS the average
+            own = dict(model.named_parameters())
+            own.update(dict(model.named_buffers()))
+            with torch.no_grad():
+                for k, a in inner["averages"].items():
+                    own[k].copy_(a)
+        return int(inner["n_averaged"])
 
 
 def load_optimizer_state(optimizer, state):

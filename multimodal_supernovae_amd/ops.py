@@ -516,8 +516,13 @@ def _bn_allreduce(t):
     return t
 
 
+BN_MOMENTUM = None   # a float while optim.update_bn recomputes running statistics: it replaces every call's momentum
+
+
 def batchnorm_fwd(x, gamma, beta, running_mean, running_var, training, residual=None, momentum=0.1, eps=1e-5,
                   relu=False):
+    if BN_MOMENTUM is not None:
+        momentum = BN_MOMENTUM
     rows, C = x.shape
     dev = x.device
     y = torch.empty_like(x)

@@ -10,6 +10,9 @@ launches, csrc/grad_clip.hip): the gradient clipping pl.Trainer(gradient_clip_va
 
 grad_accumulate_ / GradAccumulator add the gradients of the micro-batches of pl.Trainer(accumulate_grad_batches=k) with one
 multi-tensor HIP launch per micro-batch (csrc/grad_accum.hip) in place of autograd's one add per parameter.
+
+AveragedWeights keeps an EMA or the SWA mean of the trainable weights with one multi-tensor HIP launch per update
+(csrc/weight_avg.hip) -- what checkpoint.WeightAveraging drives from the Trainer; update_bn is torch.optim.swa_utils.update_bn.
 """
 import ctypes
 import math
@@ -504,3 +507,236 @@ class GradAccumulator:
             self.have.clear()
         else:
             self.have.update(recorded)
+
+
+# ---- weight averaging (pl.callbacks.WeightAveraging / StochasticWeightAveraging, torch.optim.swa_utils.AveragedModel) ----------
+# One multi-tensor launch per optimizer step through a device table {avg*, p*, numel} per averaged tensor (csrc/weight_avg.hip) in
+# place of torch._foreach_lerp_.  Unlike the gradient tables this one is STATIC -- parameters are updated in place by the optimizer
+# and by load_state_dict, the averages are views of one buffer -- so it is uploaded at construction (again only if a parameter's
+# storage has moved, as the attention's stacked q / k / v weights do at the first forward) and the same launch with the same
+# table runs eagerly and under stream capture.  Whether a recorded launch averages is a device word (`active`),
+# and the number of updates is counted on the device, as RAdam's step count is.
+AVG_MODES = {"ema": 0, "swa": 1}      # MSN_AVG_EMA, MSN_AVG_SWA of include/msn_hip.h
+_AVG_SWAP = 2                         # MSN_AVG_SWAP
+
+
+def _avg_config(avg, decay):
+    """(avg, decay) as given to AveragedWeights / checkpoint.WeightAveraging, checked: "ema" | "swa", 0 <= decay <= 1."""
+    if avg not in AVG_MODES:
+        raise ValueError(f"avg must be 'ema' or 'swa' (got {avg!r})")
+    decay = float(decay)
+    if not 0.0 <= decay <= 1.0:
+        raise ValueError(f"decay must lie in [0, 1] (got {decay!r})")
+    return avg, decay
+
+
+class AveragedWeights:
+    """A running average of a model's weights, updated by ONE HIP launch (msn_weight_average):
+
+        avg="ema":  average = decay * average + (1 - decay) * weights      (torch's get_ema_multi_avg_fn(decay))
+        avg="swa":  the equal-weight mean of the weights at every update   (AveragedModel's default)
+
+    the first update copies the weights in both.  Averaged are the contiguous float32 CUDA parameters with requires_grad=True
+    of `model_or_parameters` (a module, or an iterable of parameters, then named "0", "1", ...): a frozen parameter equals its
+    own average and costs neither memory nor bandwidth; any other trainable parameter is refused.  use_buffers=True (a module
+    only) also averages the floating-point buffers (BatchNorm's running_mean / running_var), never the integer ones
+    (num_batches_tracked); with use_buffers=False the model's live buffers serve both sets of weights, which is what torch's
+    AveragedModel reaches by copying the buffers at every update (optim.update_bn recomputes them for the average).
+
+    Memory: ONE zeroed fp32 buffer with 16-byte aligned slices, 4 bytes per averaged element -- deliberately not a deep copy of
+    the module as torch's is (it would double every cache and plane buffer of the towers).  To USE the average, swap(): the
+    average and the live values exchange their bits in place (`swapped` says which the model holds), so every address -- the
+    optimizer's, a recorded HIP graph's -- stays valid; swap() again undoes it bit for bit.
+
+    update() may be recorded in a stream capture: the descriptor table and the two device words {n_averaged, active} are built
+    here; the table is rebuilt only if a tensor's storage has moved (graph_prepare, _refresh_table), never under capture.  A
+    replay averages when `active` is set (graph_pre_replay writes it on the replaying stream) and advances the device count
+    itself; the host never writes n_averaged between replays."""
+
+    def __init__(self, model_or_parameters, avg="ema", decay=0.999, use_buffers=False):
+        self.avg, self.decay = _avg_config(avg, decay)
+        self.use_buffers = bool(use_buffers)
+        self.weight = float(torch.tensor(1.0 - self.decay, dtype=torch.float64).to(torch.float32))   # rounded ONCE from the double
+        if isinstance(model_or_parameters, torch.nn.Module):
+            named = [(k, p) for k, p in model_or_parameters.named_parameters() if p.requires_grad]
+            if self.use_buffers:
+                named += [(k, b) for k, b in model_or_parameters.named_buffers() if b.is_floating_point()]
+        else:
+            if self.use_buffers:
+                raise ValueError("AveragedWeights(use_buffers=True) needs a module as its first argument (parameters have no buffers)")
+            ps = [model_or_parameters] if torch.is_tensor(model_or_parameters) else list(model_or_parameters)
+            named = [(str(i), p) for i, p in enumerate(ps) if p.requires_grad]
+        if not named:
+            raise ValueError("AveragedWeights: nothing to average (no parameter with requires_grad=True)")
+        for k, t in named:
+            if t.device.type != "cuda":
+                _lib.require_gpu()
+                raise _lib.MsnHipError(f"AveragedWeights: {k} must live on the GPU (there is no CPU path)")
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise _lib.MsnHipError(f"AveragedWeights supports contiguous float32 tensors only ({k}: {t.dtype}, "
+                                       f"contiguous={t.is_contiguous()})")
+        if len({t.device for _, t in named}) != 1:
+            raise _lib.MsnHipError("AveragedWeights: all averaged tensors must live on one GPU")
+        if len(named) > 65535:
+            raise _lib.MsnHipError(f"AveragedWeights: at most 65535 tensors per launch (got {len(named)})")
+        self.names = [k for k, _ in named]
+        self._sources = [t for _, t in named]                    # the parameters / buffers themselves
+        dev = self._sources[0].device
+        self.numel = sum(t.numel() for t in self._sources)
+        self._max_numel = max(t.numel() for t in self._sources)
+        self.flat = torch.zeros(sum((t.numel() + 3) // 4 * 4 for t in self._sources), dtype=torch.float32, device=dev)
+        self.averages, off = [], 0
+        for t in self._sources:
+            self.averages.append(self.flat[off:off + t.numel()].view(t.shape))
+            off += (t.numel() + 3) // 4 * 4
+        self._ptrs, self._table, self._retired = None, None, []
+        self._refresh_table()
+        self._checks_left = 2             # update() looks for moved storage only this many more times (graph_prepare re-arms it)
+        self._state = torch.tensor([0, 1], dtype=torch.int64).to(dev)          # {n_averaged, active}
+        self._consts = [torch.tensor([0], dtype=torch.int64).pin_memory(), torch.tensor([1], dtype=torch.int64).pin_memory()]
+        self._active = True
+        self.n_averaged = 0               # the host's count, kept in step with the device word
+        self.swapped = False              # True: the model holds the averages and the buffer the live values
+
+    def _refresh_table(self):
+        """The device table {avg*, p*, numel}: built at construction and again only when a tensor's storage has moved since --
+        the optimizer and load_state_dict write in place, but SelfAttention.stacked_qkv re-points its three projection weights
+        at one buffer at the first forward, and .to() moves everything.  Never under stream capture (graph_prepare first): a
+        recorded launch keeps the table it was recorded with.  A replaced table stays allocated (a launch on another stream
+        may still read it; 24 bytes per tensor)."""
+        ptrs = [t.data_ptr() for t in self._sources]
+        if ptrs == self._ptrs:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.MsnHipError("AveragedWeights: a parameter's storage moved since the descriptor table was built; call "
+                                   "graph_prepare() before the capture begins")
+        for k, t in zip(self.names, self._sources):
+            if t.device != self.flat.device or t.dtype != torch.float32 or not t.is_contiguous():
+                raise _lib.MsnHipError(f"AveragedWeights supports contiguous float32 tensors on {self.flat.device} only ({k}: "
+                                       f"{t.dtype}, {t.device}, contiguous={t.is_contiguous()})")
+        self.tensors = [t.detach() for t in self._sources]       # views of the live storage: the addresses the table holds
+        words = []
+        for a, t in zip(self.averages, self.tensors):
+            words += [a.data_ptr(), t.data_ptr(), t.numel()]
+        if self._table is not None:
+            self._retired.append(self._table)
+        self._table = torch.tensor(words, dtype=torch.int64).to(self.flat.device)
+        self._ptrs = ptrs
+
+    def graph_prepare(self):
+        """Call BEFORE a stream capture that records update() (eager, after at least one forward of the model), and after
+        anything that moves the weights later on (.to(), an assignment to .data): the descriptor table for the addresses the
+        weights have now.  update() itself looks only at its first two calls after construction or after this one -- the
+        first forward is what re-points the attention weights -- so that a step does not pay a data_ptr() per tensor."""
+        self._refresh_table()
+        self._checks_left = 2
+
+    def _launch(self, mode, state, look=True):
+        if look:
+            self._refresh_table()
+        check(lib().msn_weight_average(ptr(self._table), len(self.tensors), self._max_numel, mode, self.weight, ptr(state),
+                                       stream_ptr()), "msn_weight_average")
+
+    @torch.no_grad()
+    def update(self):
+        """One averaging step from the live weights (does nothing while `active` is off).  Eager or under stream capture."""
+        if self.swapped:
+            raise RuntimeError("AveragedWeights.update(): the model holds the averages (swapped); swap() back first")
+        self._launch(AVG_MODES[self.avg], self._state, look=self._checks_left > 0)
+        self._checks_left = max(self._checks_left - 1, 0)
+        if not torch.cuda.is_current_stream_capturing():
+            self.n_averaged += int(self._active)
+
+    def set_active(self, active):
+        """Whether the next launches average: the device word, written from one of two pinned constants on the current stream
+        and only when it changes (the way GradAccumulator writes its store / add word)."""
+        active = bool(active)
+        if active != self._active:
+            self._state[1:2].copy_(self._consts[int(active)], non_blocking=True)
+            self._active = active
+
+    def graph_pre_replay(self, active=True):
+        """In front of the replay of a step that recorded update(), on the replaying stream: the `active` word for this
+        replay, and the host count advanced by what the replay will do (the device count is the kernel's own business)."""
+        self.set_active(active)
+        self.n_averaged += int(self._active)
+
+    @torch.no_grad()
+    def swap(self):
+        """Exchange the averages and the live values in place, bit for bit; twice is the identity."""
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.MsnHipError("AveragedWeights.swap() is not part of a recorded step")
+        self._launch(_AVG_SWAP, None)
+        self.swapped = not self.swapped
+
+    def device_n_averaged(self):
+        """The device's count (a synchronising read; for checks)."""
+        return int(self._state[0])
+
+    def averaged_state_dict(self):
+        """name -> a copy of the averaged tensor (wherever it lives now)."""
+        src = self._sources if self.swapped else self.averages
+        return {k: t.detach().clone() for k, t in zip(self.names, src)}
+
+    def state_dict(self):
+        """Tensors and primitives only (readable with weights_only=True).  `averages` is the CONTENT OF THE BUFFER by name: the
+        averages, or with `swapped` set the live values the model's own state_dict then lacks."""
+        return {"avg": self.avg, "decay": self.decay, "use_buffers": self.use_buffers, "n_averaged": int(self.n_averaged),
+                "swapped": bool(self.swapped), "averages": {k: a.detach().clone() for k, a in zip(self.names, self.averages)}}
+
+    @torch.no_grad()
+    def load_state_dict(self, state):
+        if state["avg"] != self.avg:
+            raise ValueError(f"AveragedWeights.load_state_dict: the state was made with avg={state['avg']!r}, this object "
+                             f"averages with avg={self.avg!r}")
+        have, want = set(state["averages"]), set(self.names)
+        if have != want:
+            raise ValueError("AveragedWeights.load_state_dict: the state averages another set of tensors -- missing here: "
+                             f"{sorted(have - want)}; missing in the state: {sorted(want - have)}")
+        for k, a in zip(self.names, self.averages):
+            src = state["averages"][k]
+            if tuple(src.shape) != tuple(a.shape):
+                raise ValueError(f"AveragedWeights.load_state_dict: {k} has shape {tuple(src.shape)} in the state, "
+                                 f"{tuple(a.shape)} here")
+            a.copy_(src)
+        self.n_averaged = int(state["n_averaged"])
+        self._state[0:1].copy_(torch.tensor([self.n_averaged], dtype=torch.int64))
+        self.swapped = bool(state["swapped"])
+
+
+@torch.no_grad()
+def update_bn(loader, model, device=None, forward=None):
+    """torch.optim.swa_utils.update_bn: recompute the BatchNorm running statistics of `model` for the weights it holds now (the
+    averaged ones after AveragedWeights.swap(), when the buffers were not averaged with them).  Under no_grad in train mode:
+    every BatchNorm's statistics are reset, then one pass over `loader` averages the batches cumulatively -- momentum
+    1 / (i + 1) on batch i, handed to the BatchNorm launches per call (ops.BN_MOMENTUM; no kernel changes).  Momentum and
+    train / eval mode are as before afterwards.  `forward(batch, i)` runs one batch (default: model.training_step(batch, i)
+    for a Lightning-style module, else model(batch), a list / tuple batch giving its first entry as torch does); `device`:
+    where to move a batch's tensors first."""
+    from . import ops
+    bns = [m for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.running_mean is not None]
+    if not bns:
+        return
+    was_training = model.training
+    for m in bns:
+        m.running_mean.zero_()
+        m.running_var.fill_(1.0)
+        m.num_batches_tracked.zero_()
+    if forward is None:
+        if callable(getattr(model, "training_step", None)):
+            forward = model.training_step
+        else:
+            forward = lambda batch, i: model(batch[0] if isinstance(batch, (list, tuple)) else batch)    # noqa: E731
+    model.train()
+    try:
+        for i, batch in enumerate(loader):
+            if device is not None:
+                if isinstance(batch, (list, tuple)):
+                    batch = type(batch)(t.to(device) if torch.is_tensor(t) else t for t in batch)
+                elif torch.is_tensor(batch):
+                    batch = batch.to(device)
+            ops.BN_MOMENTUM = 1.0 / (i + 1)
+            forward(batch, i)
+    finally:
+        ops.BN_MOMENTUM = None
+        model.train(was_training)

@@ -9,7 +9,8 @@ sequence as Lightning's automatic optimisation --
 of train_loss / val_loss, (multi-process) SUM all-reduce of the gradients before the step, and
 pl.Trainer's gradient clipping (gradient_clip_val / gradient_clip_algorithm) between the all-reduce and the step.
 Callbacks (checkpoint.ModelCheckpoint, checkpoint.EarlyStopping) run once per epoch where Lightning saves: after
-validation -- after the training epoch without a validation loader -- and after the scheduler step;
+validation -- after the training epoch without a validation loader -- and after the scheduler step; checkpoint.Callback's
+other hooks (fit start / end, optimizer step, training-epoch end, validation start / end) serve checkpoint.WeightAveraging;
 `fit(..., ckpt_path=...)` resumes a run from a checkpoint file (checkpoint.py says what resumes exactly).
 W&B logging of the reference harness is out of scope.
 """
@@ -189,6 +190,7 @@ class Trainer:
         self.global_step = 0
         # as Lightning: checkpoint callbacks run last, so the file holds the state the other callbacks reached this epoch
         callbacks = list(callbacks or [])
+        self.weight_averaging = C._one_weight_averaging(callbacks)      # checkpoint.WeightAveraging, at most one
         self.callbacks = ([c for c in callbacks if not isinstance(c, C.ModelCheckpoint)]
                           + [c for c in callbacks if isinstance(c, C.ModelCheckpoint)])
         self.current_epoch = 0
@@ -229,10 +231,18 @@ class Trainer:
         (checkpoint.save_checkpoint); with several ranks every rank calls it and rank 0 writes."""
         if self.model is None:
             raise RuntimeError("Trainer.save_checkpoint: nothing to save before fit() has started")
-        extra = {"epoch": self.current_epoch, "global_step": self.global_step,
-                 "callbacks": {cb.state_key: cb.state_dict() for cb in self.callbacks},
-                 "history": {k: list(v) for k, v in self.history.items()}}
-        return C.save_checkpoint(path, self.model, self.optimizer, self.scheduler, extra, group=self.group, device=self.device)
+        wa = self.weight_averaging
+        held = wa is not None and wa.averager is not None and wa.averager.swapped and wa._model is self.model
+        if held:                          # the file's state_dict is the LIVE model's, whatever the model holds just now
+            wa.averager.swap()
+        try:
+            extra = {"epoch": self.current_epoch, "global_step": self.global_step,
+                     "callbacks": {cb.state_key: cb.state_dict() for cb in self.callbacks},
+                     "history": {k: list(v) for k, v in self.history.items()}}
+            return C.save_checkpoint(path, self.model, self.optimizer, self.scheduler, extra, group=self.group, device=self.device)
+        finally:
+            if held:
+                wa.averager.swap()
 
     def _resume(self, ckpt, model, optimizer, scheduler):
         """optimizer -> scheduler -> callbacks -> history -> global_step -> RNG (the model is loaded before); returns the epoch
@@ -260,6 +270,9 @@ class Trainer:
         for one) to resume from: training continues at the saved epoch + 1 up to `max_epochs` epochs in total."""
         model.to(self.device)
         self.should_stop = False
+        self.model = model
+        for cb in self.callbacks:
+            cb.on_fit_start(self)         # before a checkpoint is loaded: a model that holds its average gets its live weights back
         ckpt = None
         if ckpt_path is not None:
             ckpt = ckpt_path if isinstance(ckpt_path, dict) else C.load_checkpoint(ckpt_path, map_location="cpu")
@@ -278,10 +291,15 @@ class Trainer:
         scheduler = self._scheduler_of(optim_config)
         self.model, self.scheduler = model, scheduler
         first_epoch = self._resume(ckpt, model, optimizer, scheduler) if ckpt is not None else 0
+        wa = self.weight_averaging
+        in_graph = wa is not None and wa.in_graph
         graphed = GraphedTrainStep(model.train(), optimizer, reducer=reducer, group=self.group,
                                    gradient_clip_val=self.gradient_clip_val,
                                    gradient_clip_algorithm=self.gradient_clip_algorithm,
-                                   accumulate_grad_batches=self.accumulate_grad_batches) if self.graphed_steps else None
+                                   accumulate_grad_batches=self.accumulate_grad_batches,
+                                   weight_averaging=wa.averager if in_graph else None,
+                                   weight_averaging_due=(lambda: wa.due(self.global_step + 1)) if in_graph else None,
+                                   ) if self.graphed_steps else None
         self.graphed_step = graphed
         k = self.accumulate_grad_batches
         accum = None
@@ -305,6 +323,7 @@ class Trainer:
                     if graphed is not None:
                         losses.append(graphed(batch, batch_idx).detach().clone())   # the graph's loss tensor is overwritten by the next replay
                         self.global_step += 1
+                        self._stepped()
                         continue
                     optimizer.zero_grad(set_to_none=True)
                     with markers.range("forward + loss"):
@@ -317,20 +336,41 @@ class Trainer:
                         optimizer.step()
                     losses.append(loss.detach())
                     self.global_step += 1
+                    self._stepped()
             _hook(model, "on_train_epoch_end")
+            for cb in self.callbacks:
+                cb.on_train_epoch_end(self)
             self.step_losses += losses
             if losses:
                 self.history["train_loss"].append(_weighted_mean(losses, rows))
             if scheduler is not None:
                 scheduler.step()                  # Lightning steps an epoch-interval scheduler after the training epoch
             if val_dataloaders is not None:
-                self._validate(model, val_dataloaders, world)
+                self._validate_with_callbacks(model, val_dataloaders, world)
             if self.log_fn:
                 self.log_fn(epoch, {k: v[-1] for k, v in self.history.items() if v})
             for cb in self.callbacks:
                 cb.on_epoch_end(self)
         reducer.remove()
+        for cb in self.callbacks:
+            cb.on_fit_end(self)
         return self
+
+    def _stepped(self):
+        """The optimizer has stepped and global_step counts it."""
+        for cb in self.callbacks:
+            cb.on_optimizer_step(self)
+
+    def _validate_with_callbacks(self, model, val_dataloaders, world):
+        """_validate between the callbacks' on_validation_start / on_validation_end (WeightAveraging swaps the average in and
+        out); the end hooks run whatever the validation did."""
+        for cb in self.callbacks:
+            cb.on_validation_start(self)
+        try:
+            self._validate(model, val_dataloaders, world)
+        finally:
+            for cb in self.callbacks:
+                cb.on_validation_end(self)
 
     def _accumulating_epoch(self, model, optimizer, reducer, accum, graphed, loader, losses, rows):
         """The batches of one epoch with accumulate_grad_batches > 1: the window's rule lives in _closes_window, and
@@ -346,6 +386,8 @@ class Trainer:
                 stepped = _closes_window(batch_idx, k, last)
                 losses.append(self._micro_batch(model, optimizer, reducer, accum, batch, batch_idx, stepped))
             self.global_step += int(stepped)
+            if stepped:
+                self._stepped()
 
     def _micro_batch(self, model, optimizer, reducer, accum, batch, batch_idx, boundary):
         """One micro-batch of an accumulation window (accumulate_grad_batches > 1), eager: backward on loss / k into fresh
@@ -378,14 +420,18 @@ class Trainer:
     def validate(self, model, val_dataloaders, ckpt_path=None):
         """pl.Trainer.validate: one validation epoch of `model` (with the weights of `ckpt_path`, if given) outside a fit.
         Returns {"val_loss": the batch-weighted epoch mean}; what the model's hooks log (AUC_val, f1_val, ...) is in
-        model.logged.  Trainer.history is left as it is."""
+        model.logged.  Trainer.history is left as it is.  Without `ckpt_path` a WeightAveraging callback that holds an average of
+        this model swaps it in for the epoch; with `ckpt_path` the file's state_dict is validated as it is."""
         model.to(self.device)
         if ckpt_path is not None:
             ckpt = ckpt_path if isinstance(ckpt_path, dict) else C.load_checkpoint(ckpt_path, map_location="cpu")
             model.load_state_dict(ckpt["state_dict"], strict=True)
         self.model = model
         kept = list(self.history["val_loss"])
-        self._validate(model, val_dataloaders, D.world_size(self.group))
+        if ckpt_path is not None:         # the weights asked for are the file's: no average of an earlier fit is swapped in
+            self._validate(model, val_dataloaders, D.world_size(self.group))
+        else:
+            self._validate_with_callbacks(model, val_dataloaders, D.world_size(self.group))
         new, self.history["val_loss"] = self.history["val_loss"][len(kept):], kept
         return {"val_loss": new[0] if new else None}
 
@@ -536,9 +582,13 @@ class GraphedTrainStep:
     """
 
     def __init__(self, model, optimizer, warmup=3, concurrent_towers=None, reducer=None, group=None, gradient_clip_val=None,
-                 gradient_clip_algorithm=None, accumulate_grad_batches=1):
+                 gradient_clip_algorithm=None, accumulate_grad_batches=1, weight_averaging=None, weight_averaging_due=None):
         self.k = _accumulate_config(accumulate_grad_batches)
         self.clip = _clip_config(gradient_clip_val, gradient_clip_algorithm)    # as Trainer's: None = no clipping
+        # optim.AveragedWeights updated after every optimizer step: the last launch of the recorded optimizer part, and the same
+        # object in the eager calls.  weight_averaging_due(): asked once in front of each optimizer step whether that step is
+        # averaged (None: every one); in a replay the answer travels as the average's device word `active`.
+        self.averager, self._averaging_due = weight_averaging, weight_averaging_due
         self.concurrent_towers = concurrent_towers      # None: as the model is set (towers fork / join inside the graph)
         self.group = group
         self.world = D.world_size(group)
@@ -571,8 +621,18 @@ class GraphedTrainStep:
                 self.reducer.finish()
             _clip_gradients(self.optimizer, self.clip)
             self.optimizer.step()
+            self._average_eager()
             self._eager_steps += 1
         return loss
+
+    def _due(self):
+        return True if self._averaging_due is None else bool(self._averaging_due())
+
+    def _average_eager(self):
+        """The averaging step of an eager call (warm-up, a batch of another shape): the same object the replays update."""
+        if self.averager is not None and self._due():
+            self.averager.set_active(True)
+            self.averager.update()
 
     def _eager(self, batch, batch_idx=0):
         self.optimizer.zero_grad(set_to_none=True)
@@ -582,6 +642,7 @@ class GraphedTrainStep:
             self.reducer.finish()
         _clip_gradients(self.optimizer, self.clip)
         self.optimizer.step()
+        self._average_eager()
         return loss
 
     def _capture(self, batch):
@@ -600,6 +661,8 @@ class GraphedTrainStep:
             optim.clip_graph_prepare(_clip_params(self.optimizer))    # the clip's pinned descriptor table (eager)
         if self.accum is not None:
             self.accum.graph_prepare()        # the selector word and the accumulate launch's pinned table (eager)
+        if self.averager is not None:
+            self.averager.graph_prepare()     # the descriptor table for the addresses the weights have now (eager)
         import gc
         gc.collect()                          # no autograd graph of an earlier step (bound to other streams) may survive
         device = self.static_device()
@@ -636,6 +699,8 @@ class GraphedTrainStep:
                     self.reducer.finish()         # several ranks: the clip below runs in the last segment, after the exchange
                 _clip_gradients(self.optimizer, self.clip)
                 self.optimizer.step()
+                if self.averager is not None:
+                    self.averager.update()        # the static table and the device words {n_averaged, active}
                 rec.end()
         except Exception as exc:   # noqa: BLE001 -- out of memory in the private pool, an op that is illegal under capture, ...
             failure = exc
@@ -693,6 +758,8 @@ class GraphedTrainStep:
         self.accum.graph_pre_replay()
         if boundary:
             self.optimizer.graph_pre_replay()     # RAdam's device step count advances once per optimizer step
+            if self.averager is not None:
+                self.averager.graph_pre_replay(self._due())
         self.graph.replay(boundary)
         self.accum.graph_post_replay(self._recorded, boundary)
         if boundary:
@@ -725,5 +792,7 @@ class GraphedTrainStep:
             if torch.is_tensor(dst):
                 dst.copy_(src, non_blocking=True)
         self.optimizer.graph_pre_replay()
+        if self.averager is not None:
+            self.averager.graph_pre_replay(self._due())
         self.graph.replay()
         return self.loss
