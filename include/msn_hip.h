@@ -596,6 +596,47 @@ int msn_radam_step_dev(const void* table, int n_tensors, int64_t max_numel, void
                        msn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Fused multi-tensor Adam / AdamW step: torch.optim's _single_tensor_adam (no amsgrad, not capturable) with every scalar
+ * rounded to float once from the double given here.  table: DEVICE array of n_tensors (1 .. 65535) records of five 64-bit
+ * words {p*, g*, m*, v*, numel}; step is the 1-based update count; 28 B of HBM traffic / parameter.  Per element:
+ *   decoupled == 0 (Adam):   if (weight_decay != 0) grad = grad.add(param, alpha=weight_decay)     g = fma(wd, p, g)
+ *   decoupled != 0 (AdamW):  param.mul_(1 - lr * weight_decay)                                     p = p * (float)(1 - lr*wd)
+ *   exp_avg.lerp_(grad, 1 - beta1)                                                 m = fma(1 - beta1, g - m, m)   [1 - beta1 < 0.5;
+ *                                                                                  else fma(-(1 - (1 - beta1)), g - m, g), as lerp_]
+ *   exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)                   v = fma(beta2, v, ((1 - beta2) * g) * g)
+ *   denom = (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)                  denom = sqrtf(v) / bc2_sqrt + eps
+ *   param.addcdiv_(exp_avg, denom, value=-step_size)                               p = fma(-step_size, m / denom, p)
+ * with step_size = (float)(lr / (1 - beta1^t)) and bc2_sqrt = (float)sqrt(1 - beta2^t) formed in double. */
+int msn_adam_step(const void* table, int n_tensors, int64_t max_numel, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, int decoupled, int64_t step, msn_stream_t stream);
+/* The same step for a training step recorded in a HIP graph.  hyper: DEVICE block of 64 bytes, 8-byte aligned:
+ *   bytes  0 .. 31  double lr, beta1, beta2, weight_decay (exact)
+ *   bytes 32 .. 47  float beta2, eps, 1 - beta1, 1 - beta2 (each rounded once from double by the host)
+ *   bytes 48 .. 59  float step_size, bc2_sqrt, wd_term (written by every launch; wd_term = weight_decay, or for
+ *                   decoupled != 0 the factor 1 - lr * weight_decay);  bytes 60 .. 63 padding
+ * step_counter[1] (device int64: steps taken so far).  Every launch increments the counter and derives the last three floats
+ * from the doubles ON the device with the code the eager entry point runs on the host; a changed hyper-parameter is carried
+ * in by rewriting bytes 0 .. 47 on the replaying stream between two replays. */
+int msn_adam_step_dev(const void* table, int n_tensors, int64_t max_numel, void* hyper, int decoupled,
+                      long long* step_counter, msn_stream_t stream);
+/* Fused multi-tensor SGD step: torch.optim's _single_tensor_sgd (not maximize).  table: DEVICE array of n_tensors
+ * (1 .. 65535) records of four 64-bit words {p*, g*, buf*, numel}, buf = NULL without momentum; 20 B of HBM traffic /
+ * parameter with momentum, 12 B without.  Per element:
+ *   if (weight_decay != 0) grad = grad.add(param, alpha=weight_decay)              g = fma(wd, p, g)
+ *   if (momentum != 0)  buf = clone(grad) the first time (first != 0), else
+ *                       buf.mul_(momentum).add_(grad, alpha=1 - dampening)         buf = fma(momentum, buf, (1 - dampening) * g)
+ *                       grad = nesterov ? grad.add(buf, alpha=momentum) : buf      g = nesterov ? fma(momentum, buf, g) : buf
+ *   param.add_(grad, alpha=-lr)                                                    p = fma(-lr, g, p)
+ * nesterov needs momentum > 0 and dampening == 0. */
+int msn_sgd_step(const void* table, int n_tensors, int64_t max_numel, double lr, double momentum, double dampening,
+                 double weight_decay, int nesterov, int first, msn_stream_t stream);
+/* The recorded form.  hyper: DEVICE block of 64 bytes, 8-byte aligned: bytes 0 .. 31 double lr, momentum, dampening,
+ * weight_decay; bytes 32 .. 47 float lr, momentum, 1 - dampening, weight_decay (rounded once by the host); bytes 48 .. 63
+ * padding.  The launch only reads the block (SGD has no step count) and never takes the `first` branch: the momentum buffers
+ * exist before the capture. */
+int msn_sgd_step_dev(const void* table, int n_tensors, int64_t max_numel, void* hyper, int nesterov, msn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Gradient clipping: torch.nn.utils.clip_grad_norm_ / clip_grad_value_ as pl.Trainer(gradient_clip_val=...,
  * gradient_clip_algorithm="norm" | "value") calls them after the gradient all-reduce and before optimizer.step().
  * table: DEVICE array of n_tensors (1 .. 65535) records of two 64-bit words {g*, numel} (fp32 gradients, in place);

@@ -212,7 +212,8 @@ class ClipMLP(nn.Module):
     driven by trainer.Trainer / GraphedTrainStep.  state_dict: clip_model.*, mlp.layers.{0,3,6,...}.*, class_weights."""
 
     def __init__(self, clip_model, learning_rate=1e-3, regression=False, classification=False, n_classes=5, hidden_dim=128,
-                 num_layers=2, dropout=0.0, freeze_backbone=False, class_weights=None, optimizer_kwargs=None):
+                 num_layers=2, dropout=0.0, freeze_backbone=False, class_weights=None, optimizer_kwargs=None,
+                 optimizer="radam"):
         super().__init__()
         if bool(regression) == bool(classification):
             raise ValueError("ClipMLP needs exactly one of regression=True / classification=True")
@@ -229,6 +230,7 @@ class ClipMLP(nn.Module):
         self.n_classes = int(n_classes)
         self.learning_rate = learning_rate
         self.optimizer_kwargs = dict(optimizer_kwargs or {})
+        self.optimizer = optimizer            # optim.build_optimizer's name: "radam", "adam", "adamw" or "sgd"
         self.freeze_backbone = bool(freeze_backbone)
         self.mlp = MLP(input_dim=len(self.towers) * clip_model.enc_dim, hidden_dim=hidden_dim,
                        output_dim=self.n_classes if classification else 1, num_layers=num_layers, dropout=dropout)
@@ -272,13 +274,13 @@ class ClipMLP(nn.Module):
         return self.mlp(self.features(*batch))
 
     def configure_optimizers(self):
-        """RAdam over the parameters that take part: the head, plus towers and projections unless frozen -- never the
+        """RAdam (or the optimizer named by `optimizer=`) over the parameters that take part: the head, plus towers and projections unless frozen -- never the
         contrastive logit_scale / logit_bias (no gradient here; coupled weight decay must not move them)."""
-        from .optim import RAdam
+        from .optim import build_optimizer
         params = list(self.mlp.parameters())
         if not self.freeze_backbone:
             params += [p for n, p in self.clip_model.named_parameters() if n not in ("logit_scale", "logit_bias")]
-        return {"optimizer": RAdam(params, lr=self.learning_rate, **self.optimizer_kwargs)}
+        return {"optimizer": build_optimizer(self.optimizer, params, lr=self.learning_rate, **self.optimizer_kwargs)}
 
     # -- losses ------------------------------------------------------------------------------------------------------
     def _all_true(self, n, device):

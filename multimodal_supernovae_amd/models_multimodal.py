@@ -112,7 +112,7 @@ class LightCurveImageCLIP(nn.Module):
                  conv_kwargs: Optional[Dict] = None, meta_kwargs: Optional[Dict] = None,
                  combinations: List[str] = ("host_galaxy", "spectral"), optimizer_kwargs: Optional[Dict] = None,
                  lr: float = 1e-4, loss: str = "sigmoid", regression: bool = False, classification: bool = False,
-                 n_classes: int = 5, global_negatives: bool = True):
+                 n_classes: int = 5, global_negatives: bool = True, optimizer: str = "radam"):
         super().__init__()
         if regression or classification:
             raise NotImplementedError("this class is the contrastive model; the supervised regression / classification "
@@ -125,6 +125,7 @@ class LightCurveImageCLIP(nn.Module):
         meta_kwargs = dict(meta_kwargs or {"input_dim": 128, "hidden_dim": 128, "num_layers": 2})
         self.lr = lr
         self.optimizer_kwargs = dict(optimizer_kwargs or {})
+        self.optimizer = optimizer            # optim.build_optimizer's name: "radam" (the reference's), "adam", "adamw", "sgd"
         self.enc_dim = enc_dim
         self.combinations = set(combinations)
         self.regression, self.classification = False, False
@@ -217,8 +218,8 @@ class LightCurveImageCLIP(nn.Module):
         return F_.l2_normalise(self.meta_encoder(x_meta))
 
     def configure_optimizers(self):
-        from .optim import RAdam
-        return {"optimizer": RAdam(self.parameters(), lr=self.lr, **self.optimizer_kwargs)}
+        from .optim import build_optimizer
+        return {"optimizer": build_optimizer(self.optimizer, self.parameters(), lr=self.lr, **self.optimizer_kwargs)}
 
     def _loss(self, embs):
         if self.loss == "softmax":

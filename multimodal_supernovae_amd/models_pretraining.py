@@ -94,11 +94,12 @@ class MaskedLightCurveEncoder(nn.Module):
     """ref src/models_pretraining.py:101-259 (Lightning hooks as plain methods)."""
 
     def __init__(self, f_mask: float = 0.2, nband: int = 1, transformer_kwargs: Dict = None, optimizer_kwargs: Dict = None,
-                 lr_scheduler_kwargs: Dict = None, lr: float = 1e-3):
+                 lr_scheduler_kwargs: Dict = None, lr: float = 1e-3, optimizer: str = "radam"):
         super().__init__()
         transformer_kwargs = dict(transformer_kwargs or {"n_out": 1, "emb": 128, "heads": 2, "depth": 4})
         self.nband, self.lr, self.f_mask = nband, lr, f_mask
         self.optimizer_kwargs = dict(optimizer_kwargs or {})
+        self.optimizer = optimizer            # optim.build_optimizer's name: "radam", "adam", "adamw" or "sgd"
         self.lr_scheduler_kwargs = dict(lr_scheduler_kwargs or {})
         self.net = TransformerWithTimeEmbeddings(nband=nband, agg="pretraining", **transformer_kwargs)
         self.last_layer = nn.Linear(transformer_kwargs["emb"], 1)
@@ -115,8 +116,8 @@ class MaskedLightCurveEncoder(nn.Module):
     def configure_optimizers(self):
         """RAdam + StepLR stepped once per epoch (ref src/models_pretraining.py:167-189); trainer.Trainer steps the
         scheduler it finds under "lr_scheduler" after every training epoch, as Lightning does."""
-        from .optim import RAdam
-        optimizer = RAdam(self.parameters(), lr=self.lr, **self.optimizer_kwargs)
+        from .optim import build_optimizer
+        optimizer = build_optimizer(self.optimizer, self.parameters(), lr=self.lr, **self.optimizer_kwargs)
         out = {"optimizer": optimizer}
         if self.lr_scheduler_kwargs:
             out["lr_scheduler"] = {"scheduler": torch.optim.lr_scheduler.StepLR(optimizer, **self.lr_scheduler_kwargs),

@@ -13,6 +13,10 @@ multi-tensor HIP launch per micro-batch (csrc/grad_accum.hip) in place of autogr
 
 AveragedWeights keeps an EMA or the SWA mean of the trainable weights with one multi-tensor HIP launch per update
 (csrc/weight_avg.hip) -- what checkpoint.WeightAveraging drives from the Trainer; update_bn is torch.optim.swa_utils.update_bn.
+
+Adam / AdamW / SGD are torch.optim's classes of the same names (constructors, param_groups, state keys) stepped by one fused
+HIP launch per param group (csrc/optim_steps.hip) with RAdam's graph interface, for fine-tuning a head or a ViT;
+build_optimizer(name, params, lr, **kwargs) is what the models' `optimizer=` keyword goes through.
 """
 import ctypes
 import math
@@ -740,3 +744,372 @@ def update_bn(loader, model, device=None, forward=None):
     finally:
         ops.BN_MOMENTUM = None
         model.train(was_training)
+
+
+# ---- fused Adam / AdamW / SGD (torch.optim.Adam / AdamW / SGD, csrc/optim_steps.hip) --------------------------------------------
+# RAdam's pattern applied to three more update rules: one multi-tensor launch per param group, step count and device through a
+# descriptor table staged in pinned memory (_PinnedTables); under stream capture the table comes from a pinned buffer reserved
+# by graph_prepare(), the hyper-parameters sit in a 64-byte device block and Adam's step-dependent terms are derived on the
+# device from a device-resident step counter -- nothing is written by the host between replays but a changed hyper-parameter,
+# on the replaying stream (graph_pre_replay).  RAdam itself is left exactly as it is.
+_IGNORED_KEYWORDS = ("foreach", "capturable", "fused")              # accepted for torch's signatures, without effect
+_REFUSED_KEYWORDS = ("amsgrad", "maximize", "differentiable")       # not built: True raises
+
+
+def _torch_keywords(name, kwargs):
+    """The torch.optim keywords beyond the hyper-parameters: some are ignored, some refused when set, anything else is unknown."""
+    for key, value in kwargs.items():
+        if key in _REFUSED_KEYWORDS:
+            if value:
+                raise ValueError(f"optim.{name}: {key}=True is not built (the fused step has no such form)")
+        elif key not in _IGNORED_KEYWORDS:
+            raise TypeError(f"optim.{name}.__init__() got an unexpected keyword argument {key!r}")
+
+
+class _FusedStep(torch.optim.Optimizer):
+    """What optim.Adam / AdamW / SGD share: state interchange, the descriptor tables on their way to the device and the graph
+    interface of trainer.GraphedTrainStep (graph_prepare, step() under capture, graph_pre_replay, graph_note_eager_step, with
+    RAdam's meanings).  A subclass says what a record holds (_record), which state it needs (_init_state, _has_state), what
+    tells two launches of a group apart (_advance: Adam's step count, SGD's first-step flag) and how to launch."""
+    _WORDS = 5               # 64-bit words per record of the table
+    _HOST_WORDS = 12         # float32 words at the start of the device block that the host owns
+
+    def load_state_dict(self, state_dict):
+        """torch.optim.Optimizer.load_state_dict on a DEEP COPY of `state_dict` (torch's `.to()` of a tensor that already has
+        the parameter's device and dtype returns that very tensor: the live state of another optimizer would be shared and
+        stepped twice), then every `step` as a Python int: torch.optim stores tensor(7.), a Lightning checkpoint loaded with
+        map_location="cuda" a CUDA tensor, and the recorded step reads int(step)."""
+        import copy
+        super().load_state_dict(copy.deepcopy(state_dict))
+        for st in self.state.values():
+            if "step" in st:
+                st["step"] = int(st["step"])
+
+    def _pinned(self):
+        tables = getattr(self, "_tables", None)
+        if tables is None:
+            tables = self._tables = _PinnedTables(self._WORDS, f"{type(self).__name__}.step()", "graph_prepare")
+        return tables
+
+    def _check(self, p):
+        name = type(self).__name__
+        if p.device.type != "cuda":
+            _lib.require_gpu()
+            raise _lib.MsnHipError(f"{name} parameters must live on the GPU")
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            raise _lib.MsnHipError(f"{name} supports contiguous float32 parameters only")
+
+    @staticmethod
+    def _flat_views(ps, count):
+        """`count` zeroed buffers shaped like every parameter of `ps` (one device), as views of ONE buffer with 16-byte aligned
+        slices: one fill launch instead of `count` per parameter."""
+        n = sum((p.numel() + 3) // 4 * 4 for p in ps)
+        flat = torch.zeros(count * n, dtype=torch.float32, device=ps[0].device)
+        out, off = [], 0
+        for p in ps:
+            m = p.numel()
+            out.append([flat[c * n + off:c * n + off + m].view(p.shape) for c in range(count)])
+            off += (m + 3) // 4 * 4
+        return out
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            self._step_captured()
+            return None
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        todo = []
+        for group in self.param_groups:
+            ps = [p for p in group["params"] if p.grad is not None]
+            for p in ps:
+                self._check(p)
+            todo.append((group, ps))
+        fresh = self._init_state(todo)
+        for group, ps in todo:
+            # parameters of one group that share a step count (SGD: a first step) and a device go into one launch
+            buckets = {}
+            for p in ps:
+                buckets.setdefault((self._advance(group, p, p in fresh), p.device), []).append(p)
+            for (key, dev), items in buckets.items():
+                words, max_n, keep = [], 0, []
+                for p in items:
+                    g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                    keep.append(g)
+                    words += self._record(group, p, g)
+                    max_n = max(max_n, p.numel())
+                # persistent pinned staging buffer + async copy: the step never blocks the host on the stream
+                table = self._pinned().upload(words, dev)
+                self._launch(group, key, table, len(items), max_n)
+        return loss
+
+    # ---- HIP-graph capture (trainer.GraphedTrainStep) --------------------------------------------------------------
+    def graph_prepare(self):
+        """Call BEFORE the capture (eager): per group the device block of the hyper-parameters, the device step count and the
+        pinned buffer the capture fills with the descriptor table."""
+        self._graph_ready, self._graph_hyper_captured = {}, {}
+        for gi, group in enumerate(self.param_groups):
+            ps = [p for p in group["params"] if p.device.type == "cuda"]
+            if not ps:
+                continue
+            dev = ps[0].device
+            hyper = self._hyper_block(group).to(dev)
+            counter = torch.tensor([self._group_step(group)], dtype=torch.int64, device=dev)
+            self._pinned().reserve(len(group["params"]))
+            self._graph_ready[gi] = (hyper, counter)
+            self._graph_hyper_captured[gi] = self._hyper_of(group)
+        torch.cuda.synchronize()
+
+    def _step_captured(self):
+        name = type(self).__name__
+        self._graph_launches, self._graph_hyper_seen = [], {}
+        for gi, group in enumerate(self.param_groups):
+            ps = [p for p in group["params"] if p.grad is not None]
+            if not ps:
+                continue
+            for p in ps:
+                self._check(p)
+                if not p.grad.is_contiguous():
+                    raise _lib.MsnHipError("graph capture needs contiguous gradients")
+                if self._needs_state(group) and not self._has_state(p):
+                    raise _lib.MsnHipError("capture the training step after at least one eager optimizer step "
+                                           f"(the state buffers of {name} must exist)")
+            self._capture_check(group, ps)
+            ready = getattr(self, "_graph_ready", {})
+            if gi not in ready or not self._pinned().reserved:
+                raise _lib.MsnHipError(f"{name}.graph_prepare() must run before the training step is captured")
+            hyper, counter = ready.pop(gi)
+            words = []
+            for p in ps:
+                words += self._record(group, p, p.grad)
+            table = self._pinned().upload(words, ps[0].device)          # a copy node of the graph (static content)
+            self._launch_dev(group, table, len(ps), max(p.numel() for p in ps), hyper, counter)
+            self._graph_launches.append((gi, group, ps, table, hyper, counter))
+
+    def graph_pre_replay(self):
+        """Keep the host-side step counts in line with the device counter a replay increments, and carry a changed
+        hyper-parameter (an lr scheduler, a manual edit of param_groups) into the device block the recorded launch reads: the
+        copy is enqueued on the replaying stream BEFORE the replay, so it is ordered against the previous replay's read and
+        this replay's."""
+        for li, (gi, group, ps, _, hyper, _) in enumerate(self._graph_launches):
+            self._replay_advance(ps)
+            now = self._hyper_of(group)
+            if self._graph_hyper_seen.setdefault(li, self._graph_hyper_captured[gi]) != now:
+                self._replay_check(group, self._graph_hyper_seen[li], now)
+                n = self._HOST_WORDS                 # the words behind them are the device's own
+                hyper.view(torch.float32)[:n].copy_(self._hyper_block(group).view(torch.float32)[:n], non_blocking=False)
+                self._graph_hyper_seen[li] = now
+
+    def _replay_check(self, group, was, now):
+        pass
+
+    def _capture_check(self, group, ps):
+        pass
+
+
+class Adam(_FusedStep):
+    """torch.optim.Adam (coupled L2 weight decay) stepped by ONE fused HIP launch (msn_adam_step): torch's constructor,
+    `param_groups` and state keys (`step` as a Python int, `exp_avg`, `exp_avg_sq`), so optimizer states of torch and
+    Lightning checkpoints load.  amsgrad, maximize and differentiable are not built."""
+    _DECOUPLED = 0
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, **kwargs):
+        _torch_keywords(type(self).__name__, kwargs)
+        if torch.is_tensor(lr):
+            raise ValueError("Tensor lr is not supported (the fused step takes the learning rate as a host scalar)")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def _init_state(self, todo):
+        """Moment buffers of every parameter that has a gradient and no state yet, as views of ONE zeroed buffer per device."""
+        fresh = {}
+        for _, ps in todo:
+            for p in ps:
+                if len(self.state.get(p, ())) == 0:
+                    fresh.setdefault(p.device, []).append(p)
+        for ps in fresh.values():
+            for p, (m, v) in zip(ps, self._flat_views(ps, 2)):
+                st = self.state[p]
+                st["step"], st["exp_avg"], st["exp_avg_sq"] = 0, m, v
+        return ()
+
+    def _has_state(self, p):
+        return len(self.state.get(p, ())) != 0
+
+    def _needs_state(self, group):
+        return True
+
+    def _advance(self, group, p, fresh):
+        st = self.state[p]
+        st["step"] = int(st["step"]) + 1
+        return st["step"]
+
+    def _record(self, group, p, g):
+        st = self.state[p]
+        return [p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()]
+
+    def _launch(self, group, step, table, n, max_n):
+        b1, b2 = group["betas"]                  # every scalar travels as a double: the library rounds each once
+        check(lib().msn_adam_step(ptr(table), n, max_n, group["lr"], b1, b2, group["eps"], group["weight_decay"],
+                                  self._DECOUPLED, step, stream_ptr()), "msn_adam_step")
+
+    def _launch_dev(self, group, table, n, max_n, hyper, counter):
+        check(lib().msn_adam_step_dev(ptr(table), n, max_n, ptr(hyper), self._DECOUPLED, ptr(counter), stream_ptr()),
+              "msn_adam_step_dev")
+
+    def _group_step(self, group):
+        steps = [int(self.state[p]["step"]) for p in group["params"] if len(self.state.get(p, ()))]
+        return steps[0] if steps else 0
+
+    def _capture_check(self, group, ps):
+        if len({int(self.state[p]["step"]) for p in ps}) != 1:
+            raise _lib.MsnHipError("graph capture needs one step count per parameter group")
+
+    def _replay_advance(self, ps):
+        step = int(self.state[ps[0]]["step"]) + 1
+        for p in ps:
+            self.state[p]["step"] = step
+
+    def graph_note_eager_step(self):
+        """An eager step() ran between two replays (a batch of another shape): advance the device counters with it."""
+        for _, _, _, _, _, counter in getattr(self, "_graph_launches", []):
+            counter.add_(1)
+
+    @staticmethod
+    def _hyper_of(group):
+        b1, b2 = group["betas"]
+        return (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
+
+    @classmethod
+    def _hyper_block(cls, group):
+        """Host image of the 64-byte device block msn_adam_step_dev reads (csrc/optim_steps.hip, AdamHyperDev), as 8 float64
+        words: words 0 .. 3 = the exact lr, betas and weight decay (adam_prepare_kernel derives the step-dependent terms from
+        them in double); then, as float32, {beta2, eps, 1 - beta1, 1 - beta2}, each rounded ONCE from the double value, and
+        {step_size, bc2_sqrt, wd_term}, which the device writes; 4 bytes of padding."""
+        lr, b1, b2, eps, wd = cls._hyper_of(group)
+        block = torch.zeros(8, dtype=torch.float64)
+        block[0], block[1], block[2], block[3] = lr, b1, b2, wd
+        block.view(torch.float32)[8:12] = torch.tensor([b2, eps, 1.0 - b1, 1.0 - b2], dtype=torch.float64)
+        return block
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW: Adam with decoupled weight decay, p *= 1 - lr * weight_decay before the update (default 1e-2)."""
+    _DECOUPLED = 1
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, **kwargs):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **kwargs)
+
+
+class SGD(_FusedStep):
+    """torch.optim.SGD (momentum, dampening, Nesterov, coupled L2 weight decay) stepped by ONE fused HIP launch
+    (msn_sgd_step).  State as torch's: `momentum_buffer` when momentum != 0, nothing otherwise -- SGD has no step count."""
+    _WORDS = 4
+    _HOST_WORDS = 12
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, **kwargs):
+        _torch_keywords("SGD", kwargs)
+        if torch.is_tensor(lr):
+            raise ValueError("Tensor lr is not supported (the fused step takes the learning rate as a host scalar)")
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                                      nesterov=nesterov))
+
+    def _has_state(self, p):
+        return self.state.get(p, {}).get("momentum_buffer") is not None
+
+    def _needs_state(self, group):
+        return group["momentum"] != 0
+
+    def _init_state(self, todo):
+        """Momentum buffers of every parameter that has a gradient and none yet (groups with momentum only), as views of ONE
+        buffer per device.  Returns those parameters: their first step stores the gradient in the buffer."""
+        fresh = {}
+        for group, ps in todo:
+            if group["momentum"] != 0:
+                for p in ps:
+                    if not self._has_state(p):
+                        fresh.setdefault(p.device, []).append(p)
+        for ps in fresh.values():
+            for p, (buf,) in zip(ps, self._flat_views(ps, 1)):
+                self.state[p]["momentum_buffer"] = buf
+        return {p for ps in fresh.values() for p in ps}
+
+    def _advance(self, group, p, fresh):
+        return bool(fresh)
+
+    def _record(self, group, p, g):
+        buf = self.state.get(p, {}).get("momentum_buffer") if group["momentum"] != 0 else None
+        return [p.data_ptr(), g.data_ptr(), 0 if buf is None else buf.data_ptr(), p.numel()]
+
+    def _launch(self, group, first, table, n, max_n):
+        if group["nesterov"] and (group["momentum"] <= 0 or group["dampening"] != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        check(lib().msn_sgd_step(ptr(table), n, max_n, group["lr"], group["momentum"], group["dampening"], group["weight_decay"],
+                                 1 if group["nesterov"] else 0, 1 if first else 0, stream_ptr()), "msn_sgd_step")
+
+    def _launch_dev(self, group, table, n, max_n, hyper, counter):
+        check(lib().msn_sgd_step_dev(ptr(table), n, max_n, ptr(hyper), 1 if group["nesterov"] else 0, stream_ptr()),
+              "msn_sgd_step_dev")
+
+    def _group_step(self, group):
+        return 0
+
+    def _replay_advance(self, ps):
+        pass
+
+    def _replay_check(self, group, was, now):
+        """What a recorded launch cannot follow: `nesterov` is an argument of the launch, and a momentum that becomes non-zero
+        needs buffers the recorded table does not hold."""
+        if was[4] != now[4] or (was[1] == 0.0) != (now[1] == 0.0):
+            raise _lib.MsnHipError("SGD: nesterov, or momentum between zero and non-zero, changed after the step was recorded; "
+                                   "record the step again")
+
+    def graph_note_eager_step(self):
+        """An eager step() ran between two replays: SGD keeps no step count, so there is nothing to advance."""
+
+    @staticmethod
+    def _hyper_of(group):
+        return (float(group["lr"]), float(group["momentum"]), float(group["dampening"]), float(group["weight_decay"]),
+                bool(group["nesterov"]))
+
+    @classmethod
+    def _hyper_block(cls, group):
+        """Host image of the 64-byte device block msn_sgd_step_dev reads (csrc/optim_steps.hip, SgdHyperDev), as 8 float64
+        words: words 0 .. 3 = lr, momentum, dampening, weight decay; then, as float32, {lr, momentum, 1 - dampening, weight
+        decay}, each rounded ONCE from the double value; 16 bytes of padding."""
+        lr, mom, damp, wd, _ = cls._hyper_of(group)
+        block = torch.zeros(8, dtype=torch.float64)
+        block[0], block[1], block[2], block[3] = lr, mom, damp, wd
+        block.view(torch.float32)[8:12] = torch.tensor([lr, mom, 1.0 - damp, wd], dtype=torch.float64)
+        return block
+
+
+OPTIMIZERS = {"radam": RAdam, "adam": Adam, "adamw": AdamW, "sgd": SGD}
+
+
+def build_optimizer(name, params, lr, **kwargs):
+    """The fused optimizer called `name` ("radam", "adam", "adamw" or "sgd", in any letter case) over `params`: what the models'
+    configure_optimizers build from their `optimizer=` keyword and `optimizer_kwargs`."""
+    cls = OPTIMIZERS.get(str(name).lower())
+    if cls is None:
+        raise ValueError(f"unknown optimizer {name!r}: choose one of {', '.join(sorted(OPTIMIZERS))}")
+    return cls(params, lr=lr, **kwargs)

@@ -12,6 +12,9 @@ Callbacks (checkpoint.ModelCheckpoint, checkpoint.EarlyStopping) run once per ep
 validation -- after the training epoch without a validation loader -- and after the scheduler step; checkpoint.Callback's
 other hooks (fit start / end, optimizer step, training-epoch end, validation start / end) serve checkpoint.WeightAveraging;
 `fit(..., ckpt_path=...)` resumes a run from a checkpoint file (checkpoint.py says what resumes exactly).
+A scheduler returned under "lr_scheduler" is stepped as Lightning's dict says: {"interval": "epoch"} (the default) after the
+training epoch, {"interval": "step"} after every optimizer step, either one every `frequency`-th time; a scheduler that
+needs a monitored value (ReduceLROnPlateau) is refused.
 W&B logging of the reference harness is out of scope.
 """
 import torch
@@ -196,6 +199,7 @@ class Trainer:
         self.current_epoch = 0
         self.should_stop = False
         self.model = self.optimizer = self.scheduler = self.graphed_step = self.reducer = self.accumulator = None
+        self.scheduler_interval, self.scheduler_frequency = "epoch", 1      # Lightning's lr_scheduler dict: "epoch" | "step", every n-th
 
     # ---- what callbacks see ----------------------------------------------------------------------------------------
     @property
@@ -288,7 +292,7 @@ class Trainer:
         world = D.world_size(self.group)
         if world > 1:
             _check_sharded_loader(train_dataloaders, self.group, "train_dataloaders")
-        scheduler = self._scheduler_of(optim_config)
+        scheduler, self.scheduler_interval, self.scheduler_frequency = self._scheduler_of(optim_config)
         self.model, self.scheduler = model, scheduler
         first_epoch = self._resume(ckpt, model, optimizer, scheduler) if ckpt is not None else 0
         wa = self.weight_averaging
@@ -343,7 +347,7 @@ class Trainer:
             self.step_losses += losses
             if losses:
                 self.history["train_loss"].append(_weighted_mean(losses, rows))
-            if scheduler is not None:
+            if scheduler is not None and self.scheduler_interval == "epoch" and (epoch + 1) % self.scheduler_frequency == 0:
                 scheduler.step()                  # Lightning steps an epoch-interval scheduler after the training epoch
             if val_dataloaders is not None:
                 self._validate_with_callbacks(model, val_dataloaders, world)
@@ -357,7 +361,11 @@ class Trainer:
         return self
 
     def _stepped(self):
-        """The optimizer has stepped and global_step counts it."""
+        """The optimizer has stepped and global_step counts it: a step-interval scheduler follows every `frequency`-th such
+        step (with accumulate_grad_batches that is once per window, never per micro-batch).  The new lr reaches an eager step
+        through param_groups and a recorded one through the optimizer's graph_pre_replay in front of the next replay."""
+        if self.scheduler is not None and self.scheduler_interval == "step" and self.global_step % self.scheduler_frequency == 0:
+            self.scheduler.step()
         for cb in self.callbacks:
             cb.on_optimizer_step(self)
 
@@ -438,9 +446,23 @@ class Trainer:
     @staticmethod
     def _scheduler_of(cfg):
         """`configure_optimizers` may return {"optimizer": ..., "lr_scheduler": scheduler | {"scheduler": ...}} as the
-        reference's MaskedLightCurveEncoder does (src/models_pretraining.py:167-189: RAdam + StepLR per epoch)."""
+        reference's MaskedLightCurveEncoder does (src/models_pretraining.py:167-189: RAdam + StepLR per epoch).  Returns
+        (scheduler | None, interval, frequency) with Lightning's defaults "epoch" and 1: interval "step" steps the scheduler
+        after every `frequency`-th optimizer step, "epoch" after every `frequency`-th training epoch.  A `monitor` entry is
+        accepted and unused: a scheduler that needs the monitored value (ReduceLROnPlateau) is not built."""
         sch = cfg.get("lr_scheduler")
-        return sch.get("scheduler") if isinstance(sch, dict) else sch
+        interval, frequency = "epoch", 1
+        if isinstance(sch, dict):
+            interval, frequency = sch.get("interval", "epoch"), sch.get("frequency", 1)
+            sch = sch.get("scheduler")
+        if interval not in ("epoch", "step"):
+            raise ValueError(f"lr_scheduler: interval must be 'epoch' or 'step' (got {interval!r})")
+        if isinstance(frequency, bool) or not isinstance(frequency, int) or frequency < 1:
+            raise ValueError(f"lr_scheduler: frequency must be an int >= 1 (got {frequency!r})")
+        if isinstance(sch, torch.optim.lr_scheduler.ReduceLROnPlateau):
+            raise ValueError("lr_scheduler: ReduceLROnPlateau steps on a monitored value, which this Trainer does not hand to "
+                             "a scheduler; use a scheduler that steps on its own count")
+        return sch, interval, frequency
 
     def _validate(self, model, val_dataloaders, world):
         """on_validation_start -> validation_step* -> on_validation_epoch_end (ref src/models_multimodal.py:415-556).
