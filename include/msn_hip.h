@@ -637,6 +637,58 @@ int msn_sgd_step(const void* table, int n_tensors, int64_t max_numel, double lr,
 int msn_sgd_step_dev(const void* table, int n_tensors, int64_t max_numel, void* hyper, int nesterov, msn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Layer-wise adaptive optimizers, LAMB and LARS (csrc/optim_layerwise.hip): per tensor a trust ratio from the 2-norms of the
+ * whole tensor, the parameter's taken BEFORE the update.  One call = three multi-tensor launches over the table (fp32, n_tensors
+ * 1 .. 65535, max_numel >= every numel): moments + per-block fp64 partial sums, one block per tensor that adds them in a fixed
+ * order and writes the ratio, the update.  Blocks per tensor: ceil(max_numel / 4096), at most min(1024, max(32, 8192 /
+ * n_tensors)); a larger tensor is covered in several passes.
+ *   ws:    DEVICE scratch, 8-byte aligned, of msn_layerwise_workspace_bytes(n_tensors, max_numel) bytes or more.  The size
+ *          never shrinks with more tensors or larger ones, so scratch sized for a param group serves any subset of it.
+ *   ratio: n_tensors DEVICE floats: the trust ratios in table order, written by the second launch, read by the third and left
+ *          for the caller.  They never visit the host: the calls can be recorded in a HIP graph.
+ * Every scalar arrives in double and is rounded to float once; the ratio itself is formed in double from the exact scalars.
+ *
+ * msn_lamb_step: You et al. 2020 as timm's Lamb has it, without its gradient-norm pre-clipping.  table: records of five 64-bit
+ * words {p*, g*, m*, v*, numel}; step is the 1-based update count; 40 B of HBM traffic / parameter.  With c1 = 1 - beta1^t and
+ * c2 = 1 - beta2^t (both 1 when bias_correction == 0), 1 / c1 and sqrt(c2) formed in double:
+ *   m = fma(1 - beta1, g - m, m)      [the fused lerp of msn_adam_step]        v = fma(beta2, v, ((1 - beta2) * g) * g)
+ *   u = (m * (1 / c1)) / (sqrtf(v) / sqrt(c2) + eps);   if (weight_decay != 0) u = fma(weight_decay, p, u)
+ *   ratio = ||p|| / ||u||  if (weight_decay != 0 or always_adapt) and ||p|| > 0 and ||u|| > 0, else 1;  trust_clip: min(ratio, 1)
+ *   p = fma(-(lr * ratio), u, p)
+ * u is formed twice, by one device function: for its norm in the first launch and again in the third, which reads the updated
+ * m and v.  The gradient is never written.  A NaN norm fails the comparisons (ratio 1); the NaN reaches p through u. */
+size_t msn_layerwise_workspace_bytes(int n_tensors, int64_t max_numel);
+int msn_lamb_step(const void* table, int n_tensors, int64_t max_numel, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, int bias_correction, int always_adapt, int trust_clip, int64_t step, void* ws,
+                  size_t ws_bytes, float* ratio, msn_stream_t stream);
+/* The same step for a training step recorded in a HIP graph.  hyper: DEVICE block of 64 bytes, 8-byte aligned:
+ *   bytes  0 .. 31  double lr, beta1, beta2, weight_decay (exact)
+ *   bytes 32 .. 55  float beta2, eps, 1 - beta1, 1 - beta2, lr, weight_decay (each rounded once from double by the host)
+ *   bytes 56 .. 63  float 1 / c1, sqrt(c2) (written by every call)
+ * step_counter[1] (device int64: steps taken so far).  Every call increments the counter from a one-thread launch and derives
+ * the last two floats from the exact betas ON the device with the code msn_lamb_step runs on the host; a changed
+ * hyper-parameter is carried in by rewriting bytes 0 .. 55 on the replaying stream between two replays. */
+int msn_lamb_step_dev(const void* table, int n_tensors, int64_t max_numel, void* hyper, int bias_correction, int always_adapt,
+                      int trust_clip, long long* step_counter, void* ws, size_t ws_bytes, float* ratio, msn_stream_t stream);
+/* msn_lars_step: lightning-bolts' LARS, torch's SGD with a layer-wise rate on the decayed gradient.  table: records of four
+ * 64-bit words {p*, g*, buf*, numel}, buf = NULL without momentum; 28 B of HBM traffic / parameter with momentum.
+ *   ratio = trust_coefficient ||p|| / (||g|| + weight_decay ||p|| + eps)  if weight_decay != 0 and ||p|| > 0 and ||g|| > 0, else 1
+ *   d = ratio * fma(weight_decay, p, g)                      [weight_decay == 0: d = g, and the step is msn_sgd_step's bit for bit]
+ *   if (momentum != 0)  buf = d the first time (first != 0), else buf = fma(momentum, buf, (1 - dampening) * d)
+ *                       d = nesterov ? fma(momentum, buf, d) : buf
+ *   p = fma(-lr, d, p)
+ * nesterov needs momentum > 0 and dampening == 0; trust_coefficient > 0. */
+int msn_lars_step(const void* table, int n_tensors, int64_t max_numel, double lr, double momentum, double dampening,
+                  double weight_decay, int nesterov, double trust_coefficient, double eps, int first, void* ws, size_t ws_bytes,
+                  float* ratio, msn_stream_t stream);
+/* The recorded form.  hyper: DEVICE block of 64 bytes, 8-byte aligned: bytes 0 .. 31 double lr, momentum, dampening,
+ * weight_decay; bytes 32 .. 47 float lr, momentum, 1 - dampening, weight_decay (rounded once by the host); bytes 48 .. 63 double
+ * trust_coefficient, eps.  The launches only read the block (LARS has no step count) and never take the `first` branch: the
+ * momentum buffers exist before the capture. */
+int msn_lars_step_dev(const void* table, int n_tensors, int64_t max_numel, void* hyper, int nesterov, void* ws, size_t ws_bytes,
+                      float* ratio, msn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Gradient clipping: torch.nn.utils.clip_grad_norm_ / clip_grad_value_ as pl.Trainer(gradient_clip_val=...,
  * gradient_clip_algorithm="norm" | "value") calls them after the gradient all-reduce and before optimizer.step().
  * table: DEVICE array of n_tensors (1 .. 65535) records of two 64-bit words {g*, numel} (fp32 gradients, in place);

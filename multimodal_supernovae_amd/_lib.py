@@ -160,6 +160,13 @@ SIGNATURES = {
     "msn_adam_step_dev": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_int, c_ptr, c_ptr]),
     "msn_sgd_step": (c_int, [c_ptr, c_int, c_i64, c_f64, c_f64, c_f64, c_f64, c_int, c_int, c_ptr]),
     "msn_sgd_step_dev": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_int, c_ptr]),
+    "msn_layerwise_workspace_bytes": (c_size, [c_int, c_i64]),
+    "msn_lamb_step": (c_int, [c_ptr, c_int, c_i64, c_f64, c_f64, c_f64, c_f64, c_f64, c_int, c_int, c_int, c_i64, c_ptr, c_size,
+                              c_ptr, c_ptr]),
+    "msn_lamb_step_dev": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_size, c_ptr, c_ptr]),
+    "msn_lars_step": (c_int, [c_ptr, c_int, c_i64, c_f64, c_f64, c_f64, c_f64, c_int, c_f64, c_f64, c_int, c_ptr, c_size, c_ptr,
+                              c_ptr]),
+    "msn_lars_step_dev": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_int, c_ptr, c_size, c_ptr, c_ptr]),
     "msn_grad_norm_workspace_bytes": (c_size, [c_int, c_i64]),
     "msn_grad_norm": (c_int, [c_ptr, c_int, c_i64, c_f32, c_f32, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "msn_grad_scale": (c_int, [c_ptr, c_int, c_i64, c_ptr, c_ptr]),

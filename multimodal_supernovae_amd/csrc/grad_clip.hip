@@ -38,15 +38,7 @@ __device__ __forceinline__ int tensor_blocks(int64_t n, int gx) {
     return (int)std::min<int64_t>((n + kBlockElems - 1) / kBlockElems, (int64_t)gx);
 }
 
-// NaN-keeping max: a NaN on either side wins
-__device__ __forceinline__ double nan_max(double a, double b) { return (a > b || a != a) ? a : b; }
-
-template <int P>  // 1, 2, or 0 = inf
-__device__ __forceinline__ double norm_combine(double acc, double v) {
-    if constexpr (P == 0) return nan_max(acc, v);
-    else return acc + v;
-}
-
+// nan_max, norm_combine<P>: msn_common.h (shared with optim_layerwise.hip)
 template <int P>
 __device__ __forceinline__ double norm_term(float x) {
     const double d = (double)x;
@@ -54,18 +46,7 @@ __device__ __forceinline__ double norm_term(float x) {
     else return fabs(d);
 }
 
-// Block-wide combine in a fixed order: xor-shuffle tree inside each wave, then the waves' results in wave order.
-template <int P, int THREADS>
-__device__ __forceinline__ double block_combine(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = norm_combine<P>(v, __shfl_xor(v, o, 64));
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    double t = red[0];
-    for (int i = 1; i < THREADS / kWave; ++i) t = norm_combine<P>(t, red[i]);
-    return t;
-}
+// block_combine<P, THREADS>: msn_common.h
 
 template <int P>
 __global__ __launch_bounds__(kClipThreads) void grad_norm_partial_kernel(const GradTensor* __restrict__ table, int gx,

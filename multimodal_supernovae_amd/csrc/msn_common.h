@@ -161,6 +161,29 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return t;
 }
 
+// ---- fixed-order fp64 norm reductions (grad_clip.hip, optim_layerwise.hip) ----------------------
+// NaN-keeping max: a NaN on either side wins
+__device__ __forceinline__ double nan_max(double a, double b) { return (a > b || a != a) ? a : b; }
+
+template <int P>  // 1, 2, or 0 = inf
+__device__ __forceinline__ double norm_combine(double acc, double v) {
+    if constexpr (P == 0) return nan_max(acc, v);
+    else return acc + v;
+}
+
+// Block-wide combine in a fixed order: xor-shuffle tree inside each wave, then the waves' results in wave order.
+template <int P, int THREADS>
+__device__ __forceinline__ double block_combine(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = norm_combine<P>(v, __shfl_xor(v, o, 64));
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    double t = red[0];
+    for (int i = 1; i < THREADS / kWave; ++i) t = norm_combine<P>(t, red[i]);
+    return t;
+}
+
 // Exact (erf) GELU, as torch.nn.GELU() default, and its derivative.
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_grad_f(float x) {

@@ -230,7 +230,7 @@ class ClipMLP(nn.Module):
         self.n_classes = int(n_classes)
         self.learning_rate = learning_rate
         self.optimizer_kwargs = dict(optimizer_kwargs or {})
-        self.optimizer = optimizer            # optim.build_optimizer's name: "radam", "adam", "adamw" or "sgd"
+        self.optimizer = optimizer            # optim.build_optimizer's name ("radam", "adam", "adamw", "sgd", "lars") or an Optimizer class (optim.LAMB)
         self.freeze_backbone = bool(freeze_backbone)
         self.mlp = MLP(input_dim=len(self.towers) * clip_model.enc_dim, hidden_dim=hidden_dim,
                        output_dim=self.n_classes if classification else 1, num_layers=num_layers, dropout=dropout)

@@ -125,7 +125,7 @@ class LightCurveImageCLIP(nn.Module):
         meta_kwargs = dict(meta_kwargs or {"input_dim": 128, "hidden_dim": 128, "num_layers": 2})
         self.lr = lr
         self.optimizer_kwargs = dict(optimizer_kwargs or {})
-        self.optimizer = optimizer            # optim.build_optimizer's name: "radam" (the reference's), "adam", "adamw", "sgd"
+        self.optimizer = optimizer            # optim.build_optimizer's name: "radam" (the reference's), "adam", "adamw", "sgd", "lars", or an Optimizer class (optim.LAMB)
         self.enc_dim = enc_dim
         self.combinations = set(combinations)
         self.regression, self.classification = False, False

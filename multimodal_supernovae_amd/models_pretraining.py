@@ -99,7 +99,7 @@ class MaskedLightCurveEncoder(nn.Module):
         transformer_kwargs = dict(transformer_kwargs or {"n_out": 1, "emb": 128, "heads": 2, "depth": 4})
         self.nband, self.lr, self.f_mask = nband, lr, f_mask
         self.optimizer_kwargs = dict(optimizer_kwargs or {})
-        self.optimizer = optimizer            # optim.build_optimizer's name: "radam", "adam", "adamw" or "sgd"
+        self.optimizer = optimizer            # optim.build_optimizer's name ("radam", "adam", "adamw", "sgd", "lars") or an Optimizer class (optim.LAMB)
         self.lr_scheduler_kwargs = dict(lr_scheduler_kwargs or {})
         self.net = TransformerWithTimeEmbeddings(nband=nband, agg="pretraining", **transformer_kwargs)
         self.last_layer = nn.Linear(transformer_kwargs["emb"], 1)

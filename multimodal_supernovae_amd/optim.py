@@ -17,6 +17,11 @@ AveragedWeights keeps an EMA or the SWA mean of the trainable weights with one m
 Adam / AdamW / SGD are torch.optim's classes of the same names (constructors, param_groups, state keys) stepped by one fused
 HIP launch per param group (csrc/optim_steps.hip) with RAdam's graph interface, for fine-tuning a head or a ViT;
 build_optimizer(name, params, lr, **kwargs) is what the models' `optimizer=` keyword goes through.
+
+LAMB / LARS are the layer-wise adaptive optimizers of large-batch training (timm's Lamb without its gradient pre-clipping,
+lightning-bolts' LARS): per tensor a trust ratio from fp64 2-norms, formed and applied on the device by three multi-tensor HIP
+launches per param group (csrc/optim_layerwise.hip), with the same graph interface; layerwise_param_groups splits a model into
+the group that adapts (weights) and the one that does not (biases, norm weights).
 """
 import ctypes
 import math
@@ -1103,13 +1108,243 @@ class SGD(_FusedStep):
         return block
 
 
-OPTIMIZERS = {"radam": RAdam, "adam": Adam, "adamw": AdamW, "sgd": SGD}
+# ---- layer-wise adaptive optimizers: LAMB, LARS (csrc/optim_layerwise.hip) -------------------------------------------------------
+# The fused steps above plus one thing: a per-tensor scalar (the trust ratio) that a reduction over the tensor feeds back into the
+# same step.  It stays on the device -- step() holds no .item(), no synchronisation and no host read -- so the step records into a
+# HIP graph as the others do.  The scratch of the reduction and the ratios belong to the optimizer: one pair of buffers per launch
+# of a step, allocated at the first step that needs it or in graph_prepare(), reused afterwards, never allocated under capture.
+# Data parallel needs no collective: the gradients are all-reduced before the step, so every rank forms the same norms.
+class _LayerwiseStep(_FusedStep):
+    def _scratch(self, n, max_n, dev):
+        """(workspace, ratios) of the next launch of this step; remembers the launch for trust_ratios()."""
+        i = len(self._lw_launches)
+        slots = self.__dict__.setdefault("_lw_slots", [])
+        need = int(lib().msn_layerwise_workspace_bytes(n, max_n))
+        capturing = torch.cuda.is_current_stream_capturing()
+        if i >= len(slots) or slots[i][0].device != dev or slots[i][0].numel() < need or slots[i][1].numel() < n:
+            if capturing:
+                raise _lib.MsnHipError(f"{type(self).__name__}.graph_prepare() must run before the training step is captured "
+                                       "(the scratch of the norms is not allocated under capture)")
+            pair = (torch.empty(need, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.float32, device=dev))
+            if i < len(slots):
+                slots[i] = pair
+            else:
+                slots.append(pair)
+        if capturing:
+            self.__dict__.setdefault("_lw_captured", []).append(slots[i])       # a recorded launch keeps its buffers
+        self._lw_launches.append((slots[i][1], n))
+        return slots[i]
+
+    def trust_ratios(self):
+        """The trust ratios of the last step: per launch (param group, in order) a float32 device tensor, one entry per tensor
+        that had a gradient, in the group's order.  A DEVICE READ (a clone enqueued on the current stream; looking at the
+        values synchronises) -- for logging and for tests, not for the step itself."""
+        return [ratio[:n].clone() for ratio, n in getattr(self, "_lw_launches", [])]
+
+    def graph_prepare(self):
+        super().graph_prepare()
+        groups = [[p for p in g["params"] if p.device.type == "cuda"] for g in self.param_groups]
+        groups = [ps for ps in groups if ps]
+        if groups:
+            # one pair per group, each large enough for any of them: a group without gradients records no launch
+            n, max_n = max(len(ps) for ps in groups), max(max(p.numel() for ps in groups for p in ps), 1)
+            self._lw_launches = []
+            for ps in groups:
+                self._scratch(n, max_n, ps[0].device)
+        self._lw_launches = []
+
+    def _step_captured(self):
+        self._lw_launches = []
+        super()._step_captured()
+        self._lw_recorded = list(self._lw_launches)
+
+    def graph_pre_replay(self):
+        super().graph_pre_replay()
+        self._lw_launches = list(self._lw_recorded)          # what trust_ratios() reads after the replay
+
+
+class LAMB(_LayerwiseStep):
+    """LAMB (You et al. 2020) in the form of timm's `Lamb`, without its gradient-norm pre-clipping (clip with the Trainer's
+    gradient_clip_val), stepped by three fused HIP launches per param group (msn_lamb_step).  State keys `step` (a Python int),
+    `exp_avg`, `exp_avg_sq`.  At step t, c1 = 1 - beta1^t and c2 = 1 - beta2^t (both 1 with bias_correction=False):
+
+        m <- m + (1 - beta1) (g - m);  v <- beta2 v + (1 - beta2) g^2;  u = (m / c1) / (sqrt(v / c2) + eps) + weight_decay p
+        ratio = ||p|| / ||u||  if (weight_decay != 0 or always_adapt) and ||p|| > 0 and ||u|| > 0, else 1;  trust_clip: min(ratio, 1)
+        p <- p - lr ratio u
+
+    with the 2-norms over the whole tensor, the parameter's taken before the update.  A param group with weight_decay=0 (biases,
+    norm weights: layerwise_param_groups) is not adapted.  Not built: the pre-clipping, exclusion lists other than param groups."""
+    _WORDS = 5
+    _HOST_WORDS = 14
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, bias_correction=True, always_adapt=False,
+                 trust_clip=False, **kwargs):
+        _torch_keywords("LAMB", kwargs)
+        if torch.is_tensor(lr):
+            raise ValueError("Tensor lr is not supported (the fused step takes the learning rate as a host scalar)")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, bias_correction=bias_correction,
+                                      always_adapt=always_adapt, trust_clip=trust_clip))
+
+    # the state is Adam's
+    _has_state, _needs_state, _advance, _record = Adam._has_state, Adam._needs_state, Adam._advance, Adam._record
+    _group_step, _capture_check, _replay_advance = Adam._group_step, Adam._capture_check, Adam._replay_advance
+    graph_note_eager_step = Adam.graph_note_eager_step
+
+    def _init_state(self, todo):
+        self._lw_launches = []
+        return Adam._init_state(self, todo)
+
+    @staticmethod
+    def _flags(group):
+        return (1 if group["bias_correction"] else 0, 1 if group["always_adapt"] else 0, 1 if group["trust_clip"] else 0)
+
+    def _launch(self, group, step, table, n, max_n):
+        ws, ratio = self._scratch(n, max_n, table.device)
+        b1, b2 = group["betas"]                  # every scalar travels as a double: the library rounds each once
+        check(lib().msn_lamb_step(ptr(table), n, max_n, group["lr"], b1, b2, group["eps"], group["weight_decay"],
+                                  *self._flags(group), step, ptr(ws), ws.numel(), ptr(ratio), stream_ptr()), "msn_lamb_step")
+
+    def _launch_dev(self, group, table, n, max_n, hyper, counter):
+        ws, ratio = self._scratch(n, max_n, table.device)
+        check(lib().msn_lamb_step_dev(ptr(table), n, max_n, ptr(hyper), *self._flags(group), ptr(counter), ptr(ws), ws.numel(),
+                                      ptr(ratio), stream_ptr()), "msn_lamb_step_dev")
+
+    def _replay_check(self, group, was, now):
+        if was[5:] != now[5:]:
+            raise _lib.MsnHipError("LAMB: bias_correction, always_adapt or trust_clip changed after the step was recorded (they are "
+                                   "arguments of the recorded launch); record the step again")
+
+    @staticmethod
+    def _hyper_of(group):
+        b1, b2 = group["betas"]
+        return (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"])) + LAMB._flags(group)
+
+    @classmethod
+    def _hyper_block(cls, group):
+        """Host image of the 64-byte device block msn_lamb_step_dev reads (csrc/optim_layerwise.hip, LambHyperDev), as 8 float64
+        words: words 0 .. 3 = the exact lr, betas and weight decay (lamb_prepare_kernel derives the step-dependent terms from the
+        betas in double, the finishing launch decides on the exact weight decay); then, as float32, {beta2, eps, 1 - beta1,
+        1 - beta2, lr, weight decay}, each rounded ONCE from the double value, and {1 / c1, sqrt(c2)}, which the device writes."""
+        lr, b1, b2, eps, wd = cls._hyper_of(group)[:5]
+        block = torch.zeros(8, dtype=torch.float64)
+        block[0], block[1], block[2], block[3] = lr, b1, b2, wd
+        block.view(torch.float32)[8:14] = torch.tensor([b2, eps, 1.0 - b1, 1.0 - b2, lr, wd], dtype=torch.float64)
+        return block
+
+
+class LARS(_LayerwiseStep):
+    """LARS in the form of lightning-bolts' `LARS`: torch's SGD (momentum, dampening, Nesterov) with a layer-wise rate on the
+    decayed gradient, stepped by three fused HIP launches per param group (msn_lars_step).  State as optim.SGD's:
+    `momentum_buffer` when momentum != 0, nothing otherwise.
+
+        q = trust_coefficient ||p|| / (||g|| + weight_decay ||p|| + eps)  if weight_decay != 0 and ||p|| > 0 and ||g|| > 0, else 1
+        d = q (g + weight_decay p), then torch's SGD: buf = d (first step) | momentum buf + (1 - dampening) d;
+        d <- d + momentum buf (nesterov) | buf;  p <- p - lr d
+
+    A param group with weight_decay=0 (biases, norm weights: layerwise_param_groups) is stepped by plain SGD, bit for bit."""
+    _WORDS = 4
+    _HOST_WORDS = 16
+
+    def __init__(self, params, lr, momentum=0.9, dampening=0.0, weight_decay=0.0, nesterov=False, trust_coefficient=1e-3,
+                 eps=1e-8, **kwargs):
+        _torch_keywords("LARS", kwargs)
+        if torch.is_tensor(lr):
+            raise ValueError("Tensor lr is not supported (the fused step takes the learning rate as a host scalar)")
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if eps < 0.0:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not trust_coefficient > 0.0:
+            raise ValueError(f"Invalid trust_coefficient value: {trust_coefficient}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                                      trust_coefficient=trust_coefficient, eps=eps))
+
+    # the state is SGD's, and with it SGD's rule about a capture before the first eager step
+    _has_state, _needs_state, _advance, _record = SGD._has_state, SGD._needs_state, SGD._advance, SGD._record
+    _group_step, _replay_advance, graph_note_eager_step = SGD._group_step, SGD._replay_advance, SGD.graph_note_eager_step
+
+    def _init_state(self, todo):
+        self._lw_launches = []
+        return SGD._init_state(self, todo)
+
+    def _launch(self, group, first, table, n, max_n):
+        if group["nesterov"] and (group["momentum"] <= 0 or group["dampening"] != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        ws, ratio = self._scratch(n, max_n, table.device)
+        check(lib().msn_lars_step(ptr(table), n, max_n, group["lr"], group["momentum"], group["dampening"], group["weight_decay"],
+                                  1 if group["nesterov"] else 0, group["trust_coefficient"], group["eps"], 1 if first else 0,
+                                  ptr(ws), ws.numel(), ptr(ratio), stream_ptr()), "msn_lars_step")
+
+    def _launch_dev(self, group, table, n, max_n, hyper, counter):
+        ws, ratio = self._scratch(n, max_n, table.device)
+        check(lib().msn_lars_step_dev(ptr(table), n, max_n, ptr(hyper), 1 if group["nesterov"] else 0, ptr(ws), ws.numel(),
+                                      ptr(ratio), stream_ptr()), "msn_lars_step_dev")
+
+    def _replay_check(self, group, was, now):
+        """As SGD's: `nesterov` is an argument of the launch, and a momentum that becomes non-zero needs buffers the recorded
+        table does not hold."""
+        if was[4] != now[4] or (was[1] == 0.0) != (now[1] == 0.0):
+            raise _lib.MsnHipError("LARS: nesterov, or momentum between zero and non-zero, changed after the step was recorded; "
+                                   "record the step again")
+
+    @staticmethod
+    def _hyper_of(group):
+        return (float(group["lr"]), float(group["momentum"]), float(group["dampening"]), float(group["weight_decay"]),
+                bool(group["nesterov"]), float(group["trust_coefficient"]), float(group["eps"]))
+
+    @classmethod
+    def _hyper_block(cls, group):
+        """Host image of the 64-byte device block msn_lars_step_dev reads (csrc/optim_layerwise.hip, LarsHyperDev), as 8 float64
+        words: words 0 .. 3 = lr, momentum, dampening, weight decay; then, as float32, {lr, momentum, 1 - dampening, weight
+        decay}, each rounded ONCE from the double value; words 6, 7 = trust_coefficient and eps, exact: the ratio is formed in
+        double."""
+        lr, mom, damp, wd, _, tc, eps = cls._hyper_of(group)
+        block = torch.zeros(8, dtype=torch.float64)
+        block[0], block[1], block[2], block[3], block[6], block[7] = lr, mom, damp, wd, tc, eps
+        block.view(torch.float32)[8:12] = torch.tensor([lr, mom, 1.0 - damp, wd], dtype=torch.float64)
+        return block
+
+
+def layerwise_param_groups(module_or_named_parameters, weight_decay):
+    """The two param groups layer-wise optimizers are usually given: the trainable tensors with ndim <= 1 (biases, norm weights
+    and other scalars and vectors) at weight_decay=0 -- which LAMB and LARS then do not adapt -- and the rest at `weight_decay`,
+    each in the module's order.  Takes a module or an iterable of (name, parameter)."""
+    named = module_or_named_parameters
+    if isinstance(named, torch.nn.Module):
+        named = named.named_parameters()
+    ps = [p for _, p in named if p.requires_grad]
+    return [dict(params=[p for p in ps if p.ndim <= 1], weight_decay=0.0),
+            dict(params=[p for p in ps if p.ndim > 1], weight_decay=weight_decay)]
+
+
+# "lamb" is deliberately no name yet (tests/test_optimizers_cpu.py pins it as unknown): pass the class, optimizer=optim.LAMB
+OPTIMIZERS = {"radam": RAdam, "adam": Adam, "adamw": AdamW, "sgd": SGD, "lars": LARS}
 
 
 def build_optimizer(name, params, lr, **kwargs):
-    """The fused optimizer called `name` ("radam", "adam", "adamw" or "sgd", in any letter case) over `params`: what the models'
-    configure_optimizers build from their `optimizer=` keyword and `optimizer_kwargs`."""
-    cls = OPTIMIZERS.get(str(name).lower())
+    """The fused optimizer called `name` ("radam", "adam", "adamw", "sgd" or "lars", in any letter case) over `params`, or `name`
+    itself when it is a torch.optim.Optimizer subclass (optim.LAMB): what the models' configure_optimizers build from their
+    `optimizer=` keyword and `optimizer_kwargs`, as cls(params, lr=lr, **optimizer_kwargs)."""
+    if isinstance(name, type) and issubclass(name, torch.optim.Optimizer):
+        cls = name
+    else:
+        cls = None if isinstance(name, type) else OPTIMIZERS.get(str(name).lower())
     if cls is None:
         raise ValueError(f"unknown optimizer {name!r}: choose one of {', '.join(sorted(OPTIMIZERS))}")
     return cls(params, lr=lr, **kwargs)
