@@ -72,7 +72,7 @@ __global__ void maxpool_fwd_kernel(const float* __restrict__ x, ConvGeom g, floa
                 const int xx = ow * g.sw + v - g.pw;
                 if (xx < 0 || xx >= g.W) continue;
                 const float val = x[((b * g.H + yy) * g.W + xx) * g.C + c];
-                if (val > best) { best = val; bi = yy * g.W + xx; }
+                if (val > best || val != val) { best = val; bi = yy * g.W + xx; }   // a NaN is selected, as torch's max_pool2d does
             }
         }
         y[i] = best;
@@ -124,7 +124,7 @@ __global__ void maxpool_fwd4_kernel(const float* __restrict__ x, ConvGeom g, flo
                 const float val[4] = {t.x, t.y, t.z, t.w};
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    if (val[k] > best[k]) { best[k] = val[k]; bi[k] = yy * g.W + xx; }
+                    if (val[k] > best[k] || val[k] != val[k]) { best[k] = val[k]; bi[k] = yy * g.W + xx; }
             }
         }
         reinterpret_cast<float4*>(y)[i] = make_float4(best[0], best[1], best[2], best[3]);

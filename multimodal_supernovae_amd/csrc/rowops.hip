@@ -640,7 +640,7 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(const float* __restrict__
             } else {
                 for (int t = t0; t < t1; ++t) {
                     const float v = xb[(int64_t)t * e + c] * (mb[t] ? 1.f : 0.f);
-                    if (v > best) { best = v; bi = t; }
+                    if (v > best || (v != v && best == best)) { best = v; bi = t; }   // the first NaN wins and stays, as torch's max
                 }
             }
         }
@@ -660,7 +660,7 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(const float* __restrict__
                 int ii = red_i[0][cl];
 #pragma unroll
                 for (int k = 1; k < 4; ++k)
-                    if (red_v[k][cl] > bb) { bb = red_v[k][cl]; ii = red_i[k][cl]; }
+                    if (red_v[k][cl] > bb || (red_v[k][cl] != red_v[k][cl] && bb == bb)) { bb = red_v[k][cl]; ii = red_i[k][cl]; }
                 out[(int64_t)b * e + c] = bb;
                 arg[(int64_t)b * e + c] = ii;
             }
