@@ -812,6 +812,27 @@ int msn_masked_mse_fwd(const float* pred, const float* target, const uint8_t* se
 int msn_masked_mse_bwd(const float* pred, const float* target, const uint8_t* select, int64_t n,
                        const float* stats, const float* grad_out, float* dpred, msn_stream_t stream);
 
+/* The masks of that objective, drawn on the device (csrc/pretrain_masks.hip): one launch, one workgroup per sample.
+ *   pad (B, T) bytes: the padding mask (non-zero = observed); x (B, T) fp32 or NULL
+ *   mask_in = the padding mask without the hidden points, mask_pred = the hidden points (bytes 0 / 1);
+ *   x_masked = mask_in ? x : 0 (a select: a NaN at a hidden point leaves as 0), written only when x is given;
+ *   starts (B, nbands) or NULL: the first position of every band's hidden run (contiguous mode only).
+ * With mix(seed, c) = the 64-bit mixer of msn_dropout applied to c * 0x9E3779B97F4A7C15 + seed:
+ *   MSN_MASK_CONTIGUOUS  get_continous_random_mask's rules (src/models_pretraining.py:58-98): band = T / nbands; in band k of
+ *     sample i with n observed points, h = floor((double)n * f_mask) points from start = band k + mulhi64(mix(seed, i nbands + k),
+ *     n - h + 1) on are hidden; positions at or behind band * nbands keep the padding mask in BOTH outputs.
+ *   MSN_MASK_RANDOM  get_random_mask's meaning (:17-55): the h = floor(n_observed * f_mask) observed positions j of sample i that
+ *     come first in the order by (mix(seed, i T + j), j) are hidden; nbands is not used (but checked).
+ * T <= 4096, 1 <= nbands <= T, 0 <= f_mask <= 1, else MSN_ERR_SHAPE before any launch.  The _dev form takes the seed as
+ * seed_base[0] (DEVICE memory) + seed_offset, as msn_dropout_dev does; for one seed value the two forms agree bit for bit. */
+#define MSN_MASK_CONTIGUOUS 0
+#define MSN_MASK_RANDOM 1
+int msn_pretrain_masks(const uint8_t* pad, const float* x, int64_t B, int T, int nbands, double f_mask, int mode, uint64_t seed,
+                       uint8_t* mask_in, uint8_t* mask_pred, float* x_masked, int32_t* starts, msn_stream_t stream);
+int msn_pretrain_masks_dev(const uint8_t* pad, const float* x, int64_t B, int T, int nbands, double f_mask, int mode,
+                           const uint64_t* seed_base, uint64_t seed_offset, uint8_t* mask_in, uint8_t* mask_pred,
+                           float* x_masked, int32_t* starts, msn_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Supervised heads on the towers (models_finetune.py: ClipMLP): classification / regression loss and validation metrics.
  * Cross-entropy with the semantics of torch.nn.functional.cross_entropy(logits, target, weight=w, reduction="mean"):

@@ -119,6 +119,9 @@ SIGNATURES = {
     "msn_augment_series": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_f32, c_ptr, c_ptr]),
     "msn_masked_mse_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
     "msn_masked_mse_bwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "msn_pretrain_masks": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_int, c_f64, c_int, ctypes.c_uint64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "msn_pretrain_masks_dev": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_int, c_f64, c_int, c_ptr, ctypes.c_uint64, c_ptr, c_ptr, c_ptr,
+                                       c_ptr, c_ptr]),
     "msn_cross_entropy_workspace_bytes": (c_size, [c_i64, c_int]),
     "msn_cross_entropy_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "msn_cross_entropy_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),

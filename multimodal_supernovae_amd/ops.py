@@ -817,6 +817,36 @@ def dropout(x, p, seed, residual=None, out=None):
     return y
 
 
+MASK_CONTIGUOUS, MASK_RANDOM = 0, 1
+
+
+def pretrain_masks(pad_u8, nbands, f_mask, mode, seed, x=None, want_starts=False):
+    """The pretraining masks of (B, T) byte padding mask `pad_u8`, drawn on its device in one launch (msn_pretrain_masks;
+    `seed`: an int, or a SeedToken while a step is being recorded) -> (mask_in, mask_pred, x_masked | None, starts | None):
+    byte masks, x_masked = mask_in ? x : 0 when `x` (B, T) fp32 is given, starts (B, nbands) int32 (contiguous mode) on request."""
+    if pad_u8.device.type != "cuda":
+        _lib.require_gpu()
+        raise _lib.MsnHipError(f"padding_mask must live on the GPU (got {pad_u8.device})")
+    if pad_u8.dim() != 2 or pad_u8.dtype != torch.uint8 or not pad_u8.is_contiguous():
+        raise _lib.MsnHipError(f"padding_mask must be a contiguous (B, T) byte mask (got {tuple(pad_u8.shape)}, {pad_u8.dtype})")
+    B, T = pad_u8.shape
+    if x is not None:
+        x = _f32c(x, "x")
+        if x.shape != pad_u8.shape or not x.is_contiguous():
+            raise _lib.MsnHipError(f"x must be contiguous and shaped as the padding mask {(B, T)} (got {tuple(x.shape)})")
+    mask_in, mask_pred = torch.empty_like(pad_u8), torch.empty_like(pad_u8)
+    x_masked = torch.empty_like(x) if x is not None else None
+    starts = torch.empty((B, int(nbands)), dtype=torch.int32, device=pad_u8.device) if want_starts and nbands >= 1 else None
+    tail = (ptr(mask_in), ptr(mask_pred), ptr(x_masked), ptr(starts), stream_ptr())
+    if isinstance(seed, SeedToken):
+        check(lib().msn_pretrain_masks_dev(ptr(pad_u8), ptr(x), B, T, int(nbands), float(f_mask), mode, ptr(seed.base), seed.offset,
+                                           *tail), "msn_pretrain_masks_dev")
+    else:
+        check(lib().msn_pretrain_masks(ptr(pad_u8), ptr(x), B, T, int(nbands), float(f_mask), mode,
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF, *tail), "msn_pretrain_masks")
+    return mask_in, mask_pred, x_masked, starts
+
+
 # ------------------------------------------------------------------- bf16-resident products (BASELINE cfg5 image tower)
 BEPI_NONE, BEPI_GELU, BEPI_GELU_BWD, BEPI_ADD = range(4)
 

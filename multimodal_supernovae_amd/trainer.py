@@ -596,7 +596,10 @@ class GraphedTrainStep:
     Restrictions: fixed batch shapes (others run eagerly, with the same reducer); synchronised BatchNorm issues
     collectives from inside autograd's backward threads and is refused.
     Dropout seeds are device-resident inside the graph (a base that one launch per replay advances + the ordinal of
-    the call), so every replay draws new masks.  The towers' side streams fork from and join the capturing stream, so the
+    the call), so every replay draws new masks; the pretraining masks of MaskedLightCurveEncoder(mask_generator="device") take
+    their seeds the same way (mask_generator="reference" draws on the host and is refused with an error that says so).  The
+    base is drawn from torch's CPU generator when the step is recorded: a replayed run repeats under torch.manual_seed, but
+    not the eager run's stream.  The towers' side streams fork from and join the capturing stream, so the
     graph keeps their concurrency.
 
         step = GraphedTrainStep(model, model.configure_optimizers()["optimizer"])
@@ -621,7 +624,9 @@ class GraphedTrainStep:
                                "would be issued from autograd's threads in the middle of a graph segment")
         self.reducer = reducer
         self.model, self.optimizer, self.warmup = model, optimizer, int(warmup)
+        self._check_capturable()              # e.g. a pretraining model that draws its masks on the host: refused here already
         self.calls, self.graph, self.static, self.loss = 0, None, None, None
+        self._static_attrs = {}               # model attributes the recorded step writes (graph_static_attrs), kept after the capture
         # accumulate_grad_batches > 1: the window's buffers (shared by eager calls and replays), the position in the window
         self.accum = optim.GradAccumulator(_clip_params(optimizer)) if self.k > 1 and optimizer is not None else None
         self._micro, self._recorded, self._eager_steps = 0, [], 0
@@ -667,9 +672,17 @@ class GraphedTrainStep:
         self._average_eager()
         return loss
 
+    def _check_capturable(self):
+        """A model may name what keeps its step from being recorded (check_graph_capturable raises): asked at construction
+        and again in front of the recording, before capture begins."""
+        check = getattr(self.model, "check_graph_capturable", None)
+        if check is not None:
+            check()
+
     def _capture(self, batch):
         model = self.model
         from . import ops
+        self._check_capturable()
         if self.world > 1 and ops.BN_SYNC_GROUP is not None:
             raise RuntimeError("GraphedTrainStep: synchronised BatchNorm exchanges statistics from inside backward and "
                                "cannot be recorded; use per-replica statistics or the eager step")
@@ -744,8 +757,16 @@ class GraphedTrainStep:
             self.static, self.loss = None, None
             raise failure
         self.graph = rec
+        # tensors the recorded step writes for the caller to read (a model names them in `graph_static_attrs`, e.g. the pretraining
+        # masks): an eager call in between -- a batch of another shape, a validation step -- rebinds the attributes, a replay puts
+        # the recorded tensors back, as it does for the loss and the gradients
+        self._static_attrs = {name: getattr(model, name) for name in getattr(model, "graph_static_attrs", ())}
         self._final_grads = [(p, p.grad) for p in self._recorded]     # the accumulators, or the reducer's bucket slices
         self._recorded_set = set(self._recorded)
+
+    def _rebind_static(self):
+        for name, tensor in self._static_attrs.items():
+            setattr(self.model, name, tensor)
 
     def static_device(self):
         return next(t.device for t in self.static if torch.is_tensor(t))
@@ -783,6 +804,7 @@ class GraphedTrainStep:
             if self.averager is not None:
                 self.averager.graph_pre_replay(self._due())
         self.graph.replay(boundary)
+        self._rebind_static()
         self.accum.graph_post_replay(self._recorded, boundary)
         if boundary:
             for p, g in self._final_grads:        # after the step p.grad holds the accumulated (clipped) gradient
@@ -817,4 +839,5 @@ class GraphedTrainStep:
         if self.averager is not None:
             self.averager.graph_pre_replay(self._due())
         self.graph.replay()
+        self._rebind_static()
         return self.loss

@@ -79,4 +79,16 @@ for bad in (lambda: L.msn_cls_attention_fwd(fake, 768, fake, 1536, 0, 2, 12, 300
             lambda: L.msn_cls_attention_bwd(fake, 768, fake, 1536, 1, 2, 12, 197, 64, 0.125, fake, 768, fake, fake, 768, fake, 760, fake, 1536, None),
             lambda: L.msn_cls_attention_bwd(fake, 768, fake, 1536, 0, 2, 12, 197, 64, 0.125, fake, 768, fake, fake, 768, fake, 768, None, 1536, None)):
     assert bad() == 1, L.msn_last_error()
+# device-drawn pretraining masks (pretrain_masks.hip): the argument checks of both entry points, which return before a launch
+for bad in (lambda: L.msn_pretrain_masks(fake, None, 4, 4097, 2, 0.15, 0, 7, fake, fake, None, None, None),
+            lambda: L.msn_pretrain_masks(fake, None, 4, 12, 0, 0.15, 0, 7, fake, fake, None, None, None),
+            lambda: L.msn_pretrain_masks(fake, None, 4, 12, 13, 0.15, 1, 7, fake, fake, None, None, None),
+            lambda: L.msn_pretrain_masks(fake, None, 4, 12, 2, 1.5, 0, 7, fake, fake, None, None, None),
+            lambda: L.msn_pretrain_masks(fake, None, 4, 12, 2, 0.15, 2, 7, fake, fake, None, None, None),
+            lambda: L.msn_pretrain_masks(fake, fake, 4, 12, 2, 0.15, 0, 7, fake, fake, None, None, None),
+            lambda: L.msn_pretrain_masks(None, None, 4, 12, 2, 0.15, 0, 7, fake, fake, None, None, None),
+            lambda: L.msn_pretrain_masks_dev(fake, None, 4, 12, 2, 0.15, 0, None, 7, fake, fake, None, None, None),
+            lambda: L.msn_pretrain_masks_dev(fake, None, 4, 4097, 2, 0.15, 1, fake, 7, fake, fake, None, None, None),
+            lambda: L.msn_pretrain_masks_dev(fake, None, 4, 12, 2, float("nan"), 0, fake, 7, fake, fake, None, None, None)):
+    assert bad() == 1, L.msn_last_error()
 print("HOST SANITIZER PROBE OK")
