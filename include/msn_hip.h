@@ -576,7 +576,7 @@ int msn_dwconv_bwd(const float* dpre, const float* x, const float* w, int B, int
                    msn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * Fused multi-tensor RAdam step with torch.optim.RAdam semantics (betas, eps, coupled L2 weight
+ * Fused multi-tensor RAdam step (csrc/optim_steps.hip) with torch.optim.RAdam semantics (betas, eps, coupled L2 weight
  * decay, rectification once rho_t > 5) -- the optimiser of src/models_multimodal.py:306-310.
  * table: DEVICE array of n_tensors records of five 64-bit words {p*, g*, m*, v*, numel};
  * step is the 1-based update count.  One launch for the whole model; 28 B of HBM traffic / parameter.

@@ -1,7 +1,7 @@
 // Gradient accumulation over micro-batches (pl.Trainer(accumulate_grad_batches=k)): ONE multi-tensor launch per micro-batch
 // instead of autograd's AccumulateGrad, which issues one stock add per parameter when backward() runs again on a live .grad.
 // A device table of per-tensor descriptors {dst*, acc*, g*, numel} (blockIdx.y = tensor), the idiom of grad_clip.hip and of
-// the RAdam step (optim.hip): a float4 path when every pointer of a tensor is 16-byte aligned, a scalar path otherwise.
+// the RAdam step (optim_steps.hip): a float4 path when every pointer of a tensor is 16-byte aligned, a scalar path otherwise.
 //   store: dst = g          the first micro-batch of a window
 //   add:   dst = acc + g    every later one: one correctly rounded fp32 add per element -- no multiply (the 1/k factor is the
 //                           seed of backward), no reduction, so the result is defined bit for bit; NaN and inf as the add has them

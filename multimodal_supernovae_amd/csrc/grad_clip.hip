@@ -1,7 +1,7 @@
 // Gradient clipping by norm or by value (torch.nn.utils.clip_grad_norm_ / clip_grad_value_, as pl.Trainer(gradient_clip_val=...,
 // gradient_clip_algorithm=...) calls them between the gradient all-reduce and optimizer.step()).
 // HBM-bound multi-tensor launches through a device table of per-tensor descriptors {g*, numel} (blockIdx.y = tensor), the
-// idiom of the RAdam step (optim.hip): a float4 path when a gradient is 16-byte aligned, a scalar tail otherwise.
+// idiom of the RAdam step (optim_steps.hip): a float4 path when a gradient is 16-byte aligned, a scalar tail otherwise.
 //   norm:  per-block partials in fp64 into caller-owned scratch, then ONE block combines them in a fixed order and writes the
 //          total norm and the clip coefficient to device memory (no float atomics: the same bits on every run)
 //   scale: g *= coef[0] in place (the coefficient never leaves the device)

@@ -1,6 +1,6 @@
 // Weight averaging over training (pl.callbacks.WeightAveraging / torch.optim.swa_utils.AveragedModel): ONE multi-tensor launch per
 // optimizer step over every trainable parameter instead of torch._foreach_lerp_ on stock ATen.  A device table of per-tensor
-// descriptors {avg*, p*, numel} (blockIdx.y = tensor), the idiom of grad_accum.hip, grad_clip.hip and the RAdam step (optim.hip):
+// descriptors {avg*, p*, numel} (blockIdx.y = tensor), the idiom of grad_accum.hip, grad_clip.hip and the RAdam step (optim_steps.hip):
 // a float4 path when both pointers of a tensor are 16-byte aligned, a scalar path otherwise.  Reads avg and p, writes avg: 12 B
 // per element (swap: 16 B).  Per element, each line ONE rounding, so the result is defined bit for bit:
 //   n_averaged == 0:   avg = p                                  a copy of the bits (NaN payloads, infinities, -0.0, denormals)

@@ -1,9 +1,21 @@
-"""RAdam with torch.optim.RAdam's semantics and state layout, stepped by ONE fused HIP launch.
+"""The optimizers and what runs around their step, each as multi-tensor HIP launches through device tables of per-tensor records.
 
-The reference builds `torch.optim.RAdam(self.parameters(), lr=..., **optimizer_kwargs)` in
-configure_optimizers (src/models_multimodal.py:306-310) with torch defaults; this class keeps the
-constructor, `param_groups`, `state` keys (`step`, `exp_avg`, `exp_avg_sq`), `zero_grad` and
-`step`, so optimiser states of reference checkpoints map one to one.
+RAdam / Adam / AdamW / SGD are torch.optim's classes of the same names (constructors, `param_groups`, `state` keys, `zero_grad`,
+`step`, state_dict interchange) stepped by one fused HIP launch per param group (csrc/optim_steps.hip).  RAdam is the one the
+reference builds, `torch.optim.RAdam(self.parameters(), lr=..., **optimizer_kwargs)` in configure_optimizers
+(src/models_multimodal.py:306-310) with torch defaults, so optimiser states of reference checkpoints map one to one; the others
+are for fine-tuning a head or a ViT.  build_optimizer(name, params, lr, **kwargs) is what the models' `optimizer=` keyword goes
+through.
+
+LAMB / LARS are the layer-wise adaptive optimizers of large-batch training (timm's Lamb without its gradient pre-clipping,
+lightning-bolts' LARS): per tensor a trust ratio from fp64 2-norms, formed and applied on the device by three multi-tensor HIP
+launches per param group (csrc/optim_layerwise.hip); layerwise_param_groups splits a model into the group that adapts (weights)
+and the one that does not (biases, norm weights).
+
+All six share one piece of plumbing, _FusedStep: the checks, the bucketing of a group into launches, the descriptor tables on
+their way to the device and the interface a step recorded in a HIP graph needs (graph_prepare, step() under capture,
+graph_pre_replay, graph_note_eager_step).  Their state comes from one of two families: _MomentState (`step`, `exp_avg`,
+`exp_avg_sq`: RAdam, Adam, AdamW, LAMB) or _MomentumState (`momentum_buffer`: SGD, LARS).
 
 clip_grad_norm_ / clip_grad_value_ restate torch.nn.utils' functions of the same names on the GPU (multi-tensor HIP
 launches, csrc/grad_clip.hip): the gradient clipping pl.Trainer(gradient_clip_val=...) applies before the step.
@@ -13,15 +25,6 @@ multi-tensor HIP launch per micro-batch (csrc/grad_accum.hip) in place of autogr
 
 AveragedWeights keeps an EMA or the SWA mean of the trainable weights with one multi-tensor HIP launch per update
 (csrc/weight_avg.hip) -- what checkpoint.WeightAveraging drives from the Trainer; update_bn is torch.optim.swa_utils.update_bn.
-
-Adam / AdamW / SGD are torch.optim's classes of the same names (constructors, param_groups, state keys) stepped by one fused
-HIP launch per param group (csrc/optim_steps.hip) with RAdam's graph interface, for fine-tuning a head or a ViT;
-build_optimizer(name, params, lr, **kwargs) is what the models' `optimizer=` keyword goes through.
-
-LAMB / LARS are the layer-wise adaptive optimizers of large-batch training (timm's Lamb without its gradient pre-clipping,
-lightning-bolts' LARS): per tensor a trust ratio from fp64 2-norms, formed and applied on the device by three multi-tensor HIP
-launches per param group (csrc/optim_layerwise.hip), with the same graph interface; layerwise_param_groups splits a model into
-the group that adapts (weights) and the one that does not (biases, norm weights).
 """
 import ctypes
 import math
@@ -32,210 +35,24 @@ from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
 
 
-class RAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
-            raise ValueError("invalid RAdam hyper-parameters")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-
-    def load_state_dict(self, state_dict):
-        """torch.optim.Optimizer.load_state_dict on a DEEP COPY of `state_dict` (torch's `.to()` of a tensor that already has
-        the parameter's device and dtype returns that very tensor, so the live state of another optimizer would be shared and
-        stepped twice), then every `step` as a Python int: torch.optim.RAdam stores tensor(7.), a Lightning checkpoint
-        loaded with map_location="cuda" a CUDA tensor, and `_step_captured` / `graph_prepare` read int(step) -- on a CUDA
-        tensor a synchronisation inside a stream capture."""
-        import copy
-        super().load_state_dict(copy.deepcopy(state_dict))
-        for st in self.state.values():
-            if "step" in st:
-                st["step"] = int(st["step"])
-
-    def _init_state(self):
-        """Moment buffers of every parameter that has a gradient and no state yet, as views of ONE zeroed buffer per
-        device (one fill launch instead of two per parameter; the step's launch reads them through the pointer table)."""
-        fresh = {}
-        for group in self.param_groups:
-            for p in group["params"]:
-                if p.grad is not None and len(self.state[p]) == 0 and p.device.type == "cuda" and p.dtype == torch.float32:
-                    fresh.setdefault(p.device, []).append(p)
-        for dev, ps in fresh.items():
-            n = sum((p.numel() + 3) // 4 * 4 for p in ps)            # 16-byte aligned slices
-            flat = torch.zeros(2 * n, dtype=torch.float32, device=dev)
-            off = 0
-            for p in ps:
-                m = p.numel()
-                st = self.state[p]
-                st["step"] = 0
-                st["exp_avg"] = flat[off:off + m].view(p.shape)
-                st["exp_avg_sq"] = flat[n + off:n + off + m].view(p.shape)
-                off += (m + 3) // 4 * 4
-
-    def _staging(self, n):
-        """Two pinned buffers used alternately; a buffer is rewritten only after the copy that last read it
-        has completed (its event), so the host may run a whole step ahead of the GPU."""
-        slots = getattr(self, "_pinned", None)
-        if slots is None:
-            slots = self._pinned = [[None, None], [None, None]]
-            self._slot = 0
-        self._slot ^= 1
-        slot = slots[self._slot]
-        if slot[1] is not None:
-            slot[1].synchronize()
-        if slot[0] is None or slot[0].numel() < n:
-            slot[0] = torch.empty(max(n, 1024), dtype=torch.int64).pin_memory()
-        return slot
-
-    # ---- HIP-graph capture (trainer.GraphedTrainStep) --------------------------------------------------------------
-    # Under stream capture the launch is recorded through msn_radam_step_dev: the descriptor table is copied by a copy
-    # node of the graph from a pinned buffer that never changes, the hyper-parameters sit in device memory, and the
-    # step-dependent terms are derived on the device from a device-resident step counter that every replay increments
-    # -- no host write between replays (it would race with a replay still in flight).
-    def _step_captured(self):
-        self._graph_launches = []
-        for group in self.param_groups:
-            items = []
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                st = self.state[p]
-                if len(st) == 0:
-                    raise _lib.MsnHipError("capture the training step after at least one eager optimizer step "
-                                           "(the moment buffers must exist)")
-                items.append((p, st))
-            if not items:
-                continue
-            steps = {int(st["step"]) for _, st in items}
-            if len(steps) != 1:
-                raise _lib.MsnHipError("graph capture needs one step count per parameter group")
-            dev = items[0][0].device
-            words, max_n = [], 0
-            for p, st in items:
-                if not p.grad.is_contiguous():
-                    raise _lib.MsnHipError("graph capture needs contiguous gradients")
-                words += [p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()]
-                max_n = max(max_n, p.numel())
-            hyper, counter, table_host = self._graph_buffers()
-            table_host = table_host[:len(words)]                      # pinned before the capture began
-            table_host.copy_(torch.tensor(words, dtype=torch.int64))
-            table = table_host.to(dev, non_blocking=True)             # a copy node of the graph (static content)
-            check(lib().msn_radam_step_dev(ptr(table), len(items), max_n, ptr(hyper), ptr(counter), stream_ptr()),
-                  "msn_radam_step_dev")
-            self._graph_launches.append((group, items, table_host, table, hyper, counter))
-
-    def graph_prepare(self):
-        """Call BEFORE the capture (eager): device copies of the hyper-parameters and of the step count per group."""
-        self._graph_ready = {}
-        for gi, group in enumerate(self.param_groups):
-            ps = [p for p in group["params"] if len(self.state[p])]
-            if not ps:
-                continue
-            dev = ps[0].device
-            hyper = self._hyper_block(group).to(dev)
-            counter = torch.tensor([int(self.state[ps[0]]["step"])], dtype=torch.int64, device=dev)
-            table_host = torch.empty(5 * len(group["params"]), dtype=torch.int64).pin_memory()
-            self._graph_ready[gi] = (hyper, counter, table_host)
-            self._graph_hyper_captured = getattr(self, "_graph_hyper_captured", {})
-            self._graph_hyper_captured[id(group)] = self._hyper_of(group)
-        torch.cuda.synchronize()
-
-    def _graph_buffers(self):
-        ready = getattr(self, "_graph_ready", {})
-        if not ready:
-            raise _lib.MsnHipError("RAdam.graph_prepare() must run before the training step is captured")
-        return ready.pop(min(ready))
-
-    def graph_note_eager_step(self):
-        """An eager step() ran between two replays (a batch of another shape): advance the device counters with it."""
-        for _, _, _, _, _, counter in getattr(self, "_graph_launches", []):
-            counter.add_(1)
-
-    @staticmethod
-    def _hyper_of(group):
-        b1, b2 = group["betas"]
-        return (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
-
-    @staticmethod
-    def _hyper_block(group):
-        """Host image of the 64-byte device block msn_radam_step_dev reads (csrc/optim.hip, RadamHyperDev), as 8 float64 words:
-        words 0, 1 = the exact betas (radam_prepare_kernel derives the step-dependent terms from them in double); then, as
-        float32, {lr, beta1, beta2, eps, weight_decay, 1 - beta1, 1 - beta2}, each rounded ONCE from the double value, and
-        {inv_c1, rect_scale} which the device writes."""
-        lr, b1, b2, eps, wd = RAdam._hyper_of(group)
-        block = torch.zeros(8, dtype=torch.float64)
-        block[0], block[1] = b1, b2
-        block.view(torch.float32)[4:11] = torch.tensor([lr, b1, b2, eps, wd, 1.0 - b1, 1.0 - b2], dtype=torch.float64)
-        return block
-
-    def graph_pre_replay(self):
-        """Keep the host-side step counts in line with the device counter a replay increments, and carry a changed
-        learning rate / betas / eps / weight decay (an lr scheduler, a manual edit of param_groups) into the device
-        copy the recorded launch reads: the copy is enqueued on the replaying stream BEFORE the replay, so it is
-        ordered against the previous replay's read and this replay's."""
-        seen = getattr(self, "_graph_hyper_seen", None)
-        if seen is None:
-            seen = self._graph_hyper_seen = {}
-        for li, (group, items, _, _, hyper, _) in enumerate(self._graph_launches):
-            step = int(items[0][1]["step"]) + 1
-            for _, st in items:
-                st["step"] = step
-            now = self._hyper_of(group)
-            if seen.setdefault(li, self._graph_hyper_captured.get(id(group), now)) != now:
-                # bytes 0 .. 43: the exact betas and the seven rounded scalars; inv_c1 / rect_scale stay the device's
-                hyper.view(torch.float32)[:11].copy_(self._hyper_block(group).view(torch.float32)[:11], non_blocking=False)
-                seen[li] = now
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            self._step_captured()
-            return None
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        self._init_state()
-        for group in self.param_groups:
-            # parameters of one group that share a step count go into one launch
-            buckets = {}
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if p.device.type != "cuda":
-                    _lib.require_gpu()
-                    raise _lib.MsnHipError("RAdam parameters must live on the GPU")
-                if p.dtype != torch.float32 or not p.is_contiguous():
-                    raise _lib.MsnHipError("RAdam supports contiguous float32 parameters only")
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["step"] = int(st["step"]) + 1
-                buckets.setdefault((st["step"], p.device), []).append((p, st))
-            for (step, dev), items in buckets.items():
-                words, max_n = [], 0
-                keep = []
-                for p, st in items:
-                    g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                    keep.append(g)
-                    words += [p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()]
-                    max_n = max(max_n, p.numel())
-                # descriptor table: persistent pinned staging buffer + async copy, so the step never
-                # blocks the host on the stream (a pageable H2D copy would drain the whole queue)
-                slot = self._staging(len(words))
-                slot[0][:len(words)] = torch.tensor(words, dtype=torch.int64)
-                table = slot[0][:len(words)].to(dev, non_blocking=True)
-                slot[1] = torch.cuda.Event()
-                slot[1].record()
-                b1, b2 = group["betas"]                  # passed as doubles: the library rounds beta and 1 - beta once each
-                check(lib().msn_radam_step(ptr(table), len(items), max_n, group["lr"], b1, b2, group["eps"],
-                                           group["weight_decay"], step, stream_ptr()), "msn_radam_step")
-        return loss
+def _flat_views(tensors, count=1, zeroed=True):
+    """(flat, views): `count` float32 buffers shaped like every tensor of `tensors` (one device), views[i][c] = the c-th of
+    tensors[i], as views of ONE buffer `flat` with 16-byte aligned slices -- one fill launch (none with zeroed=False) instead of
+    `count` per tensor, and every view takes the float4 path of the multi-tensor launches.  Copy c of tensor i starts at
+    c * n + off_i, n being the padded total; with zeroed=True the padding is zero and stays zero."""
+    n = sum((t.numel() + 3) // 4 * 4 for t in tensors)
+    flat = (torch.zeros if zeroed else torch.empty)(count * n, dtype=torch.float32, device=tensors[0].device)
+    views, off = [], 0
+    for t in tensors:
+        m = t.numel()
+        views.append([flat[c * n + off:c * n + off + m].view(t.shape) for c in range(count)])
+        off += (m + 3) // 4 * 4
+    return flat, views
 
 
 # ---- gradient clipping (torch.nn.utils.clip_grad_norm_ / clip_grad_value_, as pl.Trainer(gradient_clip_val=...) calls them) --
 # One multi-tensor launch per pass through a device table {g*, numel} per gradient (csrc/grad_clip.hip).  Eager calls stage
-# the table in pinned host memory (two buffers used alternately, as RAdam._staging); under stream capture the table comes
+# the table in pinned host memory (two buffers used alternately, _PinnedTables); under stream capture the table comes
 # from a pinned buffer reserved BEFORE the capture (clip_graph_prepare), is filled at capture time and copied by a copy
 # node of the graph, and the clip coefficient stays on the device -- nothing is written by the host between replays.
 class _PinnedTables:
@@ -426,12 +243,8 @@ class GradAccumulator:
 
     def _buffers(self):
         if self.flat is None and self.params:
-            n = sum((p.numel() + 3) // 4 * 4 for p in self.params)
-            self.flat = torch.empty(n, dtype=torch.float32, device=self.params[0].device)
-            off = 0
-            for p in self.params:
-                self.acc[p] = self.flat[off:off + p.numel()].view(p.shape)
-                off += (p.numel() + 3) // 4 * 4
+            self.flat, views = _flat_views(self.params, zeroed=False)
+            self.acc = {p: v for p, (v,) in zip(self.params, views)}
         return self.acc
 
     def _check(self, p):
@@ -593,11 +406,8 @@ class AveragedWeights:
         dev = self._sources[0].device
         self.numel = sum(t.numel() for t in self._sources)
         self._max_numel = max(t.numel() for t in self._sources)
-        self.flat = torch.zeros(sum((t.numel() + 3) // 4 * 4 for t in self._sources), dtype=torch.float32, device=dev)
-        self.averages, off = [], 0
-        for t in self._sources:
-            self.averages.append(self.flat[off:off + t.numel()].view(t.shape))
-            off += (t.numel() + 3) // 4 * 4
+        self.flat, views = _flat_views(self._sources)
+        self.averages = [v for (v,) in views]
         self._ptrs, self._table, self._retired = None, None, []
         self._refresh_table()
         self._checks_left = 2             # update() looks for moved storage only this many more times (graph_prepare re-arms it)
@@ -751,12 +561,12 @@ def update_bn(loader, model, device=None, forward=None):
         model.train(was_training)
 
 
-# ---- fused Adam / AdamW / SGD (torch.optim.Adam / AdamW / SGD, csrc/optim_steps.hip) --------------------------------------------
-# RAdam's pattern applied to three more update rules: one multi-tensor launch per param group, step count and device through a
-# descriptor table staged in pinned memory (_PinnedTables); under stream capture the table comes from a pinned buffer reserved
-# by graph_prepare(), the hyper-parameters sit in a 64-byte device block and Adam's step-dependent terms are derived on the
-# device from a device-resident step counter -- nothing is written by the host between replays but a changed hyper-parameter,
-# on the replaying stream (graph_pre_replay).  RAdam itself is left exactly as it is.
+# ---- fused RAdam / Adam / AdamW / SGD (torch.optim's classes, csrc/optim_steps.hip) -----------------------------------------------
+# One multi-tensor launch per param group, step count and device through a descriptor table staged in pinned memory
+# (_PinnedTables), so the step never blocks the host on the stream.  Under stream capture the table comes from a pinned buffer
+# reserved by graph_prepare(), the hyper-parameters sit in a 64-byte device block and the step-dependent terms are derived on the
+# device from a device-resident step counter that every replay increments -- nothing is written by the host between replays (it
+# would race with a replay still in flight) but a changed hyper-parameter, on the replaying stream (graph_pre_replay).
 _IGNORED_KEYWORDS = ("foreach", "capturable", "fused")              # accepted for torch's signatures, without effect
 _REFUSED_KEYWORDS = ("amsgrad", "maximize", "differentiable")       # not built: True raises
 
@@ -772,10 +582,12 @@ def _torch_keywords(name, kwargs):
 
 
 class _FusedStep(torch.optim.Optimizer):
-    """What optim.Adam / AdamW / SGD share: state interchange, the descriptor tables on their way to the device and the graph
-    interface of trainer.GraphedTrainStep (graph_prepare, step() under capture, graph_pre_replay, graph_note_eager_step, with
-    RAdam's meanings).  A subclass says what a record holds (_record), which state it needs (_init_state, _has_state), what
-    tells two launches of a group apart (_advance: Adam's step count, SGD's first-step flag) and how to launch."""
+    """What every optimizer of this module shares: state interchange, the bucketing of a group into launches, the descriptor
+    tables on their way to the device and the graph interface of trainer.GraphedTrainStep (graph_prepare, step() under capture,
+    graph_pre_replay, graph_note_eager_step).  The state family (_MomentState, _MomentumState) says which state a parameter
+    needs (_init_state, _has_state, _needs_state), what tells two launches of a group apart (_advance: the step count, SGD's
+    first-step flag) and what a record holds (_record); the optimizer itself says how to launch (_launch, _launch_dev) and what
+    the device block of its hyper-parameters looks like (_hyper_block)."""
     _WORDS = 5               # 64-bit words per record of the table
     _HOST_WORDS = 12         # float32 words at the start of the device block that the host owns
 
@@ -783,7 +595,8 @@ class _FusedStep(torch.optim.Optimizer):
         """torch.optim.Optimizer.load_state_dict on a DEEP COPY of `state_dict` (torch's `.to()` of a tensor that already has
         the parameter's device and dtype returns that very tensor: the live state of another optimizer would be shared and
         stepped twice), then every `step` as a Python int: torch.optim stores tensor(7.), a Lightning checkpoint loaded with
-        map_location="cuda" a CUDA tensor, and the recorded step reads int(step)."""
+        map_location="cuda" a CUDA tensor, and the recorded step reads int(step) -- on a CUDA tensor a synchronisation inside
+        a stream capture."""
         import copy
         super().load_state_dict(copy.deepcopy(state_dict))
         for st in self.state.values():
@@ -803,19 +616,6 @@ class _FusedStep(torch.optim.Optimizer):
             raise _lib.MsnHipError(f"{name} parameters must live on the GPU")
         if p.dtype != torch.float32 or not p.is_contiguous():
             raise _lib.MsnHipError(f"{name} supports contiguous float32 parameters only")
-
-    @staticmethod
-    def _flat_views(ps, count):
-        """`count` zeroed buffers shaped like every parameter of `ps` (one device), as views of ONE buffer with 16-byte aligned
-        slices: one fill launch instead of `count` per parameter."""
-        n = sum((p.numel() + 3) // 4 * 4 for p in ps)
-        flat = torch.zeros(count * n, dtype=torch.float32, device=ps[0].device)
-        out, off = [], 0
-        for p in ps:
-            m = p.numel()
-            out.append([flat[c * n + off:c * n + off + m].view(p.shape) for c in range(count)])
-            off += (m + 3) // 4 * 4
-        return out
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -839,15 +639,9 @@ class _FusedStep(torch.optim.Optimizer):
             for p in ps:
                 buckets.setdefault((self._advance(group, p, p in fresh), p.device), []).append(p)
             for (key, dev), items in buckets.items():
-                words, max_n, keep = [], 0, []
-                for p in items:
-                    g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                    keep.append(g)
-                    words += self._record(group, p, g)
-                    max_n = max(max_n, p.numel())
-                # persistent pinned staging buffer + async copy: the step never blocks the host on the stream
-                table = self._pinned().upload(words, dev)
-                self._launch(group, key, table, len(items), max_n)
+                grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in items]     # alive up to the launch
+                table = self._pinned().upload(self._record(group, items, grads), dev)
+                self._launch(group, key, table, len(items), max(p.numel() for p in items))
         return loss
 
     # ---- HIP-graph capture (trainer.GraphedTrainStep) --------------------------------------------------------------
@@ -868,6 +662,8 @@ class _FusedStep(torch.optim.Optimizer):
         torch.cuda.synchronize()
 
     def _step_captured(self):
+        """step() under stream capture.  Leaves one record per launch in _graph_launches: (group, [(parameter, its state)],
+        group index, device table, device hyper block, device step counter)."""
         name = type(self).__name__
         self._graph_launches, self._graph_hyper_seen = [], {}
         for gi, group in enumerate(self.param_groups):
@@ -886,20 +682,18 @@ class _FusedStep(torch.optim.Optimizer):
             if gi not in ready or not self._pinned().reserved:
                 raise _lib.MsnHipError(f"{name}.graph_prepare() must run before the training step is captured")
             hyper, counter = ready.pop(gi)
-            words = []
-            for p in ps:
-                words += self._record(group, p, p.grad)
+            words = self._record(group, ps, [p.grad for p in ps])
             table = self._pinned().upload(words, ps[0].device)          # a copy node of the graph (static content)
             self._launch_dev(group, table, len(ps), max(p.numel() for p in ps), hyper, counter)
-            self._graph_launches.append((gi, group, ps, table, hyper, counter))
+            self._graph_launches.append((group, [(p, self.state.get(p, {})) for p in ps], gi, table, hyper, counter))
 
     def graph_pre_replay(self):
         """Keep the host-side step counts in line with the device counter a replay increments, and carry a changed
         hyper-parameter (an lr scheduler, a manual edit of param_groups) into the device block the recorded launch reads: the
         copy is enqueued on the replaying stream BEFORE the replay, so it is ordered against the previous replay's read and
         this replay's."""
-        for li, (gi, group, ps, _, hyper, _) in enumerate(self._graph_launches):
-            self._replay_advance(ps)
+        for li, (group, items, gi, _, hyper, _) in enumerate(self._graph_launches):
+            self._replay_advance(items)
             now = self._hyper_of(group)
             if self._graph_hyper_seen.setdefault(li, self._graph_hyper_captured[gi]) != now:
                 self._replay_check(group, self._graph_hyper_seen[li], now)
@@ -914,16 +708,18 @@ class _FusedStep(torch.optim.Optimizer):
         pass
 
 
-class Adam(_FusedStep):
-    """torch.optim.Adam (coupled L2 weight decay) stepped by ONE fused HIP launch (msn_adam_step): torch's constructor,
-    `param_groups` and state keys (`step` as a Python int, `exp_avg`, `exp_avg_sq`), so optimizer states of torch and
-    Lightning checkpoints load.  amsgrad, maximize and differentiable are not built."""
-    _DECOUPLED = 0
+def _refuse_tensor_lr(lr):
+    if torch.is_tensor(lr):
+        raise ValueError("Tensor lr is not supported (the fused step takes the learning rate as a host scalar)")
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, **kwargs):
-        _torch_keywords(type(self).__name__, kwargs)
-        if torch.is_tensor(lr):
-            raise ValueError("Tensor lr is not supported (the fused step takes the learning rate as a host scalar)")
+
+class _MomentState:
+    """The state of RAdam, Adam, AdamW and LAMB: `step` (a Python int), `exp_avg`, `exp_avg_sq`; a record is {p, g, m, v, n}."""
+
+    @staticmethod
+    def _check_hypers(lr, betas, eps, weight_decay):
+        """torch.optim.Adam's checks, with its messages."""
+        _refuse_tensor_lr(lr)
         if not 0.0 <= lr:
             raise ValueError(f"Invalid learning rate: {lr}")
         if not 0.0 <= eps:
@@ -934,7 +730,6 @@ class Adam(_FusedStep):
             raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
         if not 0.0 <= weight_decay:
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
 
     def _init_state(self, todo):
         """Moment buffers of every parameter that has a gradient and no state yet, as views of ONE zeroed buffer per device."""
@@ -944,7 +739,7 @@ class Adam(_FusedStep):
                 if len(self.state.get(p, ())) == 0:
                     fresh.setdefault(p.device, []).append(p)
         for ps in fresh.values():
-            for p, (m, v) in zip(ps, self._flat_views(ps, 2)):
+            for p, (m, v) in zip(ps, _flat_views(ps, 2)[1]):
                 st = self.state[p]
                 st["step"], st["exp_avg"], st["exp_avg_sq"] = 0, m, v
         return ()
@@ -960,18 +755,12 @@ class Adam(_FusedStep):
         st["step"] = int(st["step"]) + 1
         return st["step"]
 
-    def _record(self, group, p, g):
-        st = self.state[p]
-        return [p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()]
-
-    def _launch(self, group, step, table, n, max_n):
-        b1, b2 = group["betas"]                  # every scalar travels as a double: the library rounds each once
-        check(lib().msn_adam_step(ptr(table), n, max_n, group["lr"], b1, b2, group["eps"], group["weight_decay"],
-                                  self._DECOUPLED, step, stream_ptr()), "msn_adam_step")
-
-    def _launch_dev(self, group, table, n, max_n, hyper, counter):
-        check(lib().msn_adam_step_dev(ptr(table), n, max_n, ptr(hyper), self._DECOUPLED, ptr(counter), stream_ptr()),
-              "msn_adam_step_dev")
+    def _record(self, group, ps, grads):
+        words = []
+        for p, g in zip(ps, grads):
+            st = self.state[p]
+            words += [p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()]
+        return words
 
     def _group_step(self, group):
         steps = [int(self.state[p]["step"]) for p in group["params"] if len(self.state.get(p, ()))]
@@ -981,20 +770,145 @@ class Adam(_FusedStep):
         if len({int(self.state[p]["step"]) for p in ps}) != 1:
             raise _lib.MsnHipError("graph capture needs one step count per parameter group")
 
-    def _replay_advance(self, ps):
-        step = int(self.state[ps[0]]["step"]) + 1
-        for p in ps:
-            self.state[p]["step"] = step
+    def _replay_advance(self, items):
+        step = int(items[0][1]["step"]) + 1
+        for _, st in items:
+            st["step"] = step
 
     def graph_note_eager_step(self):
         """An eager step() ran between two replays (a batch of another shape): advance the device counters with it."""
-        for _, _, _, _, _, counter in getattr(self, "_graph_launches", []):
+        for *_, counter in getattr(self, "_graph_launches", []):
             counter.add_(1)
 
     @staticmethod
     def _hyper_of(group):
         b1, b2 = group["betas"]
         return (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
+
+
+class _MomentumState:
+    """The state of SGD and LARS, as torch's: `momentum_buffer` when momentum != 0, nothing otherwise -- there is no step count;
+    a record is {p, g, buf | NULL, n}."""
+
+    @staticmethod
+    def _check_hypers(lr, momentum, weight_decay):
+        """torch.optim.SGD's checks, with its messages (Nesterov's: _check_nesterov)."""
+        _refuse_tensor_lr(lr)
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+
+    @staticmethod
+    def _check_nesterov(nesterov, momentum, dampening):
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+
+    def _has_state(self, p):
+        return self.state.get(p, {}).get("momentum_buffer") is not None
+
+    def _needs_state(self, group):
+        return group["momentum"] != 0
+
+    def _init_state(self, todo):
+        """Momentum buffers of every parameter that has a gradient and none yet (groups with momentum only), as views of ONE
+        buffer per device.  Returns those parameters: their first step stores the gradient in the buffer."""
+        fresh = {}
+        for group, ps in todo:
+            if group["momentum"] != 0:
+                for p in ps:
+                    if not self._has_state(p):
+                        fresh.setdefault(p.device, []).append(p)
+        for ps in fresh.values():
+            for p, (buf,) in zip(ps, _flat_views(ps)[1]):
+                self.state[p]["momentum_buffer"] = buf
+        return {p for ps in fresh.values() for p in ps}
+
+    def _advance(self, group, p, fresh):
+        return bool(fresh)
+
+    def _record(self, group, ps, grads):
+        words = []
+        for p, g in zip(ps, grads):
+            buf = self.state.get(p, {}).get("momentum_buffer") if group["momentum"] != 0 else None
+            words += [p.data_ptr(), g.data_ptr(), 0 if buf is None else buf.data_ptr(), p.numel()]
+        return words
+
+    def _group_step(self, group):
+        return 0
+
+    def _replay_advance(self, items):
+        pass
+
+    def _replay_check(self, group, was, now):
+        """What a recorded launch cannot follow: `nesterov` is an argument of the launch, and a momentum that becomes non-zero
+        needs buffers the recorded table does not hold."""
+        if was[4] != now[4] or (was[1] == 0.0) != (now[1] == 0.0):
+            raise _lib.MsnHipError(f"{type(self).__name__}: nesterov, or momentum between zero and non-zero, changed after the "
+                                   "step was recorded; record the step again")
+
+    def graph_note_eager_step(self):
+        """An eager step() ran between two replays: there is no step count, so there is nothing to advance."""
+
+    @staticmethod
+    def _hyper_of(group):
+        return (float(group["lr"]), float(group["momentum"]), float(group["dampening"]), float(group["weight_decay"]),
+                bool(group["nesterov"]))
+
+
+class RAdam(_MomentState, _FusedStep):
+    """torch.optim.RAdam (L2 weight decay folded into the gradient, variance rectification once rho_t > 5) stepped by ONE fused
+    HIP launch (msn_radam_step): the optimizer the reference builds, with torch's constructor, `param_groups` and state keys."""
+    _WORDS = 5
+    _HOST_WORDS = 11
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
+            raise ValueError("invalid RAdam hyper-parameters")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def _launch(self, group, step, table, n, max_n):
+        b1, b2 = group["betas"]                  # passed as doubles: the library rounds beta and 1 - beta once each
+        check(lib().msn_radam_step(ptr(table), n, max_n, group["lr"], b1, b2, group["eps"], group["weight_decay"], step,
+                                   stream_ptr()), "msn_radam_step")
+
+    def _launch_dev(self, group, table, n, max_n, hyper, counter):
+        check(lib().msn_radam_step_dev(ptr(table), n, max_n, ptr(hyper), ptr(counter), stream_ptr()), "msn_radam_step_dev")
+
+    @classmethod
+    def _hyper_block(cls, group):
+        """Host image of the 64-byte device block msn_radam_step_dev reads (csrc/optim_steps.hip, RadamHyperDev), as 8 float64
+        words: words 0, 1 = the exact betas (radam_prepare_kernel derives the step-dependent terms from them in double); then,
+        as float32, {lr, beta1, beta2, eps, weight_decay, 1 - beta1, 1 - beta2}, each rounded ONCE from the double value, and
+        {inv_c1, rect_scale}, which the device writes."""
+        lr, b1, b2, eps, wd = cls._hyper_of(group)
+        block = torch.zeros(8, dtype=torch.float64)
+        block[0], block[1] = b1, b2
+        block.view(torch.float32)[4:11] = torch.tensor([lr, b1, b2, eps, wd, 1.0 - b1, 1.0 - b2], dtype=torch.float64)
+        return block
+
+
+class Adam(_MomentState, _FusedStep):
+    """torch.optim.Adam (coupled L2 weight decay) stepped by ONE fused HIP launch (msn_adam_step): torch's constructor,
+    `param_groups` and state keys (`step` as a Python int, `exp_avg`, `exp_avg_sq`), so optimizer states of torch and
+    Lightning checkpoints load.  amsgrad, maximize and differentiable are not built."""
+    _DECOUPLED = 0
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, **kwargs):
+        _torch_keywords(type(self).__name__, kwargs)
+        self._check_hypers(lr, betas, eps, weight_decay)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def _launch(self, group, step, table, n, max_n):
+        b1, b2 = group["betas"]                  # every scalar travels as a double: the library rounds each once
+        check(lib().msn_adam_step(ptr(table), n, max_n, group["lr"], b1, b2, group["eps"], group["weight_decay"],
+                                  self._DECOUPLED, step, stream_ptr()), "msn_adam_step")
+
+    def _launch_dev(self, group, table, n, max_n, hyper, counter):
+        check(lib().msn_adam_step_dev(ptr(table), n, max_n, ptr(hyper), self._DECOUPLED, ptr(counter), stream_ptr()),
+              "msn_adam_step_dev")
 
     @classmethod
     def _hyper_block(cls, group):
@@ -1017,7 +931,7 @@ class AdamW(Adam):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **kwargs)
 
 
-class SGD(_FusedStep):
+class SGD(_MomentumState, _FusedStep):
     """torch.optim.SGD (momentum, dampening, Nesterov, coupled L2 weight decay) stepped by ONE fused HIP launch
     (msn_sgd_step).  State as torch's: `momentum_buffer` when momentum != 0, nothing otherwise -- SGD has no step count."""
     _WORDS = 4
@@ -1025,76 +939,19 @@ class SGD(_FusedStep):
 
     def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, **kwargs):
         _torch_keywords("SGD", kwargs)
-        if torch.is_tensor(lr):
-            raise ValueError("Tensor lr is not supported (the fused step takes the learning rate as a host scalar)")
-        if lr < 0.0:
-            raise ValueError(f"Invalid learning rate: {lr}")
-        if momentum < 0.0:
-            raise ValueError(f"Invalid momentum value: {momentum}")
-        if weight_decay < 0.0:
-            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
-        if nesterov and (momentum <= 0 or dampening != 0):
-            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        self._check_hypers(lr, momentum, weight_decay)
+        self._check_nesterov(nesterov, momentum, dampening)
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                                       nesterov=nesterov))
 
-    def _has_state(self, p):
-        return self.state.get(p, {}).get("momentum_buffer") is not None
-
-    def _needs_state(self, group):
-        return group["momentum"] != 0
-
-    def _init_state(self, todo):
-        """Momentum buffers of every parameter that has a gradient and none yet (groups with momentum only), as views of ONE
-        buffer per device.  Returns those parameters: their first step stores the gradient in the buffer."""
-        fresh = {}
-        for group, ps in todo:
-            if group["momentum"] != 0:
-                for p in ps:
-                    if not self._has_state(p):
-                        fresh.setdefault(p.device, []).append(p)
-        for ps in fresh.values():
-            for p, (buf,) in zip(ps, self._flat_views(ps, 1)):
-                self.state[p]["momentum_buffer"] = buf
-        return {p for ps in fresh.values() for p in ps}
-
-    def _advance(self, group, p, fresh):
-        return bool(fresh)
-
-    def _record(self, group, p, g):
-        buf = self.state.get(p, {}).get("momentum_buffer") if group["momentum"] != 0 else None
-        return [p.data_ptr(), g.data_ptr(), 0 if buf is None else buf.data_ptr(), p.numel()]
-
     def _launch(self, group, first, table, n, max_n):
-        if group["nesterov"] and (group["momentum"] <= 0 or group["dampening"] != 0):
-            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        self._check_nesterov(group["nesterov"], group["momentum"], group["dampening"])
         check(lib().msn_sgd_step(ptr(table), n, max_n, group["lr"], group["momentum"], group["dampening"], group["weight_decay"],
                                  1 if group["nesterov"] else 0, 1 if first else 0, stream_ptr()), "msn_sgd_step")
 
     def _launch_dev(self, group, table, n, max_n, hyper, counter):
         check(lib().msn_sgd_step_dev(ptr(table), n, max_n, ptr(hyper), 1 if group["nesterov"] else 0, stream_ptr()),
               "msn_sgd_step_dev")
-
-    def _group_step(self, group):
-        return 0
-
-    def _replay_advance(self, ps):
-        pass
-
-    def _replay_check(self, group, was, now):
-        """What a recorded launch cannot follow: `nesterov` is an argument of the launch, and a momentum that becomes non-zero
-        needs buffers the recorded table does not hold."""
-        if was[4] != now[4] or (was[1] == 0.0) != (now[1] == 0.0):
-            raise _lib.MsnHipError("SGD: nesterov, or momentum between zero and non-zero, changed after the step was recorded; "
-                                   "record the step again")
-
-    def graph_note_eager_step(self):
-        """An eager step() ran between two replays: SGD keeps no step count, so there is nothing to advance."""
-
-    @staticmethod
-    def _hyper_of(group):
-        return (float(group["lr"]), float(group["momentum"]), float(group["dampening"]), float(group["weight_decay"]),
-                bool(group["nesterov"]))
 
     @classmethod
     def _hyper_block(cls, group):
@@ -1141,6 +998,11 @@ class _LayerwiseStep(_FusedStep):
         values synchronises) -- for logging and for tests, not for the step itself."""
         return [ratio[:n].clone() for ratio, n in getattr(self, "_lw_launches", [])]
 
+    @torch.no_grad()
+    def step(self, closure=None):
+        self._lw_launches = []               # the launches of a step, eager or recorded, take the scratch pairs from the first on
+        return super().step(closure)
+
     def graph_prepare(self):
         super().graph_prepare()
         groups = [[p for p in g["params"] if p.device.type == "cuda"] for g in self.param_groups]
@@ -1154,7 +1016,6 @@ class _LayerwiseStep(_FusedStep):
         self._lw_launches = []
 
     def _step_captured(self):
-        self._lw_launches = []
         super()._step_captured()
         self._lw_recorded = list(self._lw_launches)
 
@@ -1163,7 +1024,7 @@ class _LayerwiseStep(_FusedStep):
         self._lw_launches = list(self._lw_recorded)          # what trust_ratios() reads after the replay
 
 
-class LAMB(_LayerwiseStep):
+class LAMB(_MomentState, _LayerwiseStep):
     """LAMB (You et al. 2020) in the form of timm's `Lamb`, without its gradient-norm pre-clipping (clip with the Trainer's
     gradient_clip_val), stepped by three fused HIP launches per param group (msn_lamb_step).  State keys `step` (a Python int),
     `exp_avg`, `exp_avg_sq`.  At step t, c1 = 1 - beta1^t and c2 = 1 - beta2^t (both 1 with bias_correction=False):
@@ -1180,29 +1041,9 @@ class LAMB(_LayerwiseStep):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, bias_correction=True, always_adapt=False,
                  trust_clip=False, **kwargs):
         _torch_keywords("LAMB", kwargs)
-        if torch.is_tensor(lr):
-            raise ValueError("Tensor lr is not supported (the fused step takes the learning rate as a host scalar)")
-        if not 0.0 <= lr:
-            raise ValueError(f"Invalid learning rate: {lr}")
-        if not 0.0 <= eps:
-            raise ValueError(f"Invalid epsilon value: {eps}")
-        if not 0.0 <= betas[0] < 1.0:
-            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
-        if not 0.0 <= betas[1] < 1.0:
-            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
-        if not 0.0 <= weight_decay:
-            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        self._check_hypers(lr, betas, eps, weight_decay)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, bias_correction=bias_correction,
                                       always_adapt=always_adapt, trust_clip=trust_clip))
-
-    # the state is Adam's
-    _has_state, _needs_state, _advance, _record = Adam._has_state, Adam._needs_state, Adam._advance, Adam._record
-    _group_step, _capture_check, _replay_advance = Adam._group_step, Adam._capture_check, Adam._replay_advance
-    graph_note_eager_step = Adam.graph_note_eager_step
-
-    def _init_state(self, todo):
-        self._lw_launches = []
-        return Adam._init_state(self, todo)
 
     @staticmethod
     def _flags(group):
@@ -1226,8 +1067,7 @@ class LAMB(_LayerwiseStep):
 
     @staticmethod
     def _hyper_of(group):
-        b1, b2 = group["betas"]
-        return (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"])) + LAMB._flags(group)
+        return _MomentState._hyper_of(group) + LAMB._flags(group)
 
     @classmethod
     def _hyper_block(cls, group):
@@ -1242,7 +1082,7 @@ class LAMB(_LayerwiseStep):
         return block
 
 
-class LARS(_LayerwiseStep):
+class LARS(_MomentumState, _LayerwiseStep):
     """LARS in the form of lightning-bolts' `LARS`: torch's SGD (momentum, dampening, Nesterov) with a layer-wise rate on the
     decayed gradient, stepped by three fused HIP launches per param group (msn_lars_step).  State as optim.SGD's:
     `momentum_buffer` when momentum != 0, nothing otherwise.
@@ -1258,34 +1098,17 @@ class LARS(_LayerwiseStep):
     def __init__(self, params, lr, momentum=0.9, dampening=0.0, weight_decay=0.0, nesterov=False, trust_coefficient=1e-3,
                  eps=1e-8, **kwargs):
         _torch_keywords("LARS", kwargs)
-        if torch.is_tensor(lr):
-            raise ValueError("Tensor lr is not supported (the fused step takes the learning rate as a host scalar)")
-        if lr < 0.0:
-            raise ValueError(f"Invalid learning rate: {lr}")
-        if momentum < 0.0:
-            raise ValueError(f"Invalid momentum value: {momentum}")
-        if weight_decay < 0.0:
-            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        self._check_hypers(lr, momentum, weight_decay)
         if eps < 0.0:
             raise ValueError(f"Invalid epsilon value: {eps}")
         if not trust_coefficient > 0.0:
             raise ValueError(f"Invalid trust_coefficient value: {trust_coefficient}")
-        if nesterov and (momentum <= 0 or dampening != 0):
-            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        self._check_nesterov(nesterov, momentum, dampening)
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
                                       trust_coefficient=trust_coefficient, eps=eps))
 
-    # the state is SGD's, and with it SGD's rule about a capture before the first eager step
-    _has_state, _needs_state, _advance, _record = SGD._has_state, SGD._needs_state, SGD._advance, SGD._record
-    _group_step, _replay_advance, graph_note_eager_step = SGD._group_step, SGD._replay_advance, SGD.graph_note_eager_step
-
-    def _init_state(self, todo):
-        self._lw_launches = []
-        return SGD._init_state(self, todo)
-
     def _launch(self, group, first, table, n, max_n):
-        if group["nesterov"] and (group["momentum"] <= 0 or group["dampening"] != 0):
-            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        self._check_nesterov(group["nesterov"], group["momentum"], group["dampening"])
         ws, ratio = self._scratch(n, max_n, table.device)
         check(lib().msn_lars_step(ptr(table), n, max_n, group["lr"], group["momentum"], group["dampening"], group["weight_decay"],
                                   1 if group["nesterov"] else 0, group["trust_coefficient"], group["eps"], 1 if first else 0,
@@ -1296,17 +1119,9 @@ class LARS(_LayerwiseStep):
         check(lib().msn_lars_step_dev(ptr(table), n, max_n, ptr(hyper), 1 if group["nesterov"] else 0, ptr(ws), ws.numel(),
                                       ptr(ratio), stream_ptr()), "msn_lars_step_dev")
 
-    def _replay_check(self, group, was, now):
-        """As SGD's: `nesterov` is an argument of the launch, and a momentum that becomes non-zero needs buffers the recorded
-        table does not hold."""
-        if was[4] != now[4] or (was[1] == 0.0) != (now[1] == 0.0):
-            raise _lib.MsnHipError("LARS: nesterov, or momentum between zero and non-zero, changed after the step was recorded; "
-                                   "record the step again")
-
     @staticmethod
     def _hyper_of(group):
-        return (float(group["lr"]), float(group["momentum"]), float(group["dampening"]), float(group["weight_decay"]),
-                bool(group["nesterov"]), float(group["trust_coefficient"]), float(group["eps"]))
+        return _MomentumState._hyper_of(group) + (float(group["trust_coefficient"]), float(group["eps"]))
 
     @classmethod
     def _hyper_block(cls, group):

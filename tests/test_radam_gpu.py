@@ -1,4 +1,4 @@
-"""The fused RAdam step (csrc/optim.hip through optim.RAdam) against torch's own definition in float64.
+"""The fused RAdam step (csrc/optim_steps.hip through optim.RAdam) against torch's own definition in float64.
 
 Reference: torch.optim.RAdam(foreach=False) on float64 CPU copies of the same weights, fed the same gradients.
 Yardstick: the same optimiser on float32 CPU copies.  Every accuracy assertion has the form
@@ -213,7 +213,7 @@ def test_memory_path_does_not_change_a_bit():
     ob = _kernel_radam([dict(params=b, **hyper)])
     for p, gv in zip(b, bg):
         p.grad = gv
-    ob._init_state()
+    ob._init_state([(group, group["params"]) for group in ob.param_groups])
     sflat = ob.state[b[0]]["exp_avg"]._base
     smask = torch.ones(sflat.numel(), dtype=torch.bool, device=DEV)
     for p in b:
@@ -562,3 +562,103 @@ def test_recorded_step_follows_hyper_parameter_changes():
     # The device derives 1 / (1 - beta1^t) and the rectification term with its own pow: nothing promises the host's last bit.
     # On an MI355X the two runs were measured bit-identical (profiles/radam_accuracy.txt), so equality is held.
     assert same, f"the recorded steps and the eager steps differ (max |dp| = {drift:.3e})"
+
+
+# ---- f. the shared plumbing (optim._FusedStep) under RAdam -----------------------------------------------------------------------
+def test_class_step_equals_the_raw_c_abi_bit_for_bit():
+    """optim.RAdam.step() against a loop written here that builds the {p, g, m, v, numel} table itself and calls msn_radam_step
+    with the group's values, one launch per (group, step count): the argument types and the bucketing of the class.  Two param
+    groups with their own lr and weight_decay; one parameter of the second group gets its first gradient at step 3, so that group
+    holds two step counts and takes two launches.  The moments of the loop are separate allocations, those of the class slices
+    of one buffer: alignment changes no bit (test_memory_path_does_not_change_a_bit)."""
+    from multimodal_supernovae_amd._lib import check, lib, ptr, stream_ptr
+    shapes = [(), (5,), (7, 3), (129, 33)]
+    hypers = [dict(lr=1e-2, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-3), dict(lr=3e-3, betas=(0.8, 0.95), eps=1e-6, weight_decay=0.05)]
+    members, late = [[0, 1], [2, 3]], 2
+    w0 = _weights(shapes, 0.02, seed=121)
+    a, b = [w.clone().to(DEV) for w in w0], [w.clone().to(DEV) for w in w0]
+    opt = _kernel_radam([dict(params=[a[i] for i in idx], **h) for idx, h in zip(members, hypers)])
+    state = {}                                           # of the loop: index -> [step, exp_avg, exp_avg_sq]
+    for step, gs in enumerate(_random_grads(shapes, 6, seed=122), start=1):
+        grads = [None if (i == late and step < 3) else g.to(DEV) for i, g in enumerate(gs)]
+        for p, g in zip(a, grads):
+            p.grad = None if g is None else g.clone()
+        opt.step()
+        for idx, h in zip(members, hypers):
+            buckets = {}
+            for i in idx:
+                if grads[i] is not None:
+                    st = state.setdefault(i, [0, torch.zeros_like(b[i]), torch.zeros_like(b[i])])
+                    st[0] += 1
+                    buckets.setdefault(st[0], []).append(i)
+            for count, items in buckets.items():
+                words = []
+                for i in items:
+                    words += [b[i].data_ptr(), grads[i].data_ptr(), state[i][1].data_ptr(), state[i][2].data_ptr(), b[i].numel()]
+                table = torch.tensor(words, dtype=torch.int64).to(DEV)
+                check(lib().msn_radam_step(ptr(table), len(items), max(b[i].numel() for i in items), h["lr"], h["betas"][0],
+                                           h["betas"][1], h["eps"], h["weight_decay"], count, stream_ptr()), "msn_radam_step")
+        torch.cuda.synchronize()
+    assert [state[i][0] for i in range(4)] == [6, 6, 4, 6]
+    for i in range(4):
+        st = opt.state[a[i]]
+        assert type(st["step"]) is int and st["step"] == state[i][0], f"tensor {i}: step {st['step']!r} against {state[i][0]}"
+        assert torch.equal(a[i], b[i]), f"tensor {i}: p differs"
+        assert torch.equal(st["exp_avg"], state[i][1]) and torch.equal(st["exp_avg_sq"], state[i][2]), f"tensor {i}: moments differ"
+
+
+def _record_one_step(opt, params):
+    """One eager step, graph_prepare(), step() recorded on a side stream.  Returns the graph."""
+    g = torch.Generator().manual_seed(131)
+    for p in params:
+        p.grad = torch.randn(p.shape, generator=g).to(DEV)
+    opt.step()
+    opt.graph_prepare()
+    graph, side = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        graph.capture_begin(capture_error_mode="thread_local")
+        opt.step()                                        # recorded, not run
+        graph.capture_end()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    return graph
+
+
+@pytest.mark.parametrize("name", ["RAdam", "AdamW", "SGD", "LAMB", "LARS"])
+def test_every_optimizer_leaves_the_same_record_of_a_recorded_launch(name):
+    """_graph_launches after a recorded step: (group, [(parameter, its state)], ..., device step counter) whatever the optimizer
+    -- the shape bench.py's snapshot and the accumulation tests unpack by position.  With a step count (RAdam, AdamW, LAMB) the
+    device counter and the host's `step` agree after a replay that graph_pre_replay() announced."""
+    from multimodal_supernovae_amd import optim
+    params = [w.to(DEV) for w in _weights([(7, 3), (7, 3)], 0.02, seed=130)]
+    kwargs = {"SGD": dict(momentum=0.9), "LAMB": dict(weight_decay=1e-2), "LARS": dict(weight_decay=1e-2)}.get(name, {})
+    opt = getattr(optim, name)(params, lr=1e-2, **kwargs)
+    graph = _record_one_step(opt, params)
+    assert len(opt._graph_launches) == 1
+    opt.graph_pre_replay()
+    graph.replay()
+    torch.cuda.synchronize()
+    for entry in opt._graph_launches:
+        assert isinstance(entry, tuple) and len(entry) == 6
+        assert entry[0] is opt.param_groups[0]
+        assert isinstance(entry[1], list) and len(entry[1]) == 2
+        for (p, st), q in zip(entry[1], params):
+            assert p is q and st is opt.state[q]
+        counter = entry[5]
+        assert counter.dtype == torch.int64 and counter.numel() == 1 and counter.device.type == DEV
+        if name in ("RAdam", "AdamW", "LAMB"):
+            assert int(counter) == entry[1][0][1]["step"] == 2
+
+
+def test_graph_prepare_invents_no_state():
+    """A parameter that never had a gradient has no entry in `state` -- torch's own rule, which state_dict() (a checkpoint) shows
+    -- and graph_prepare(), which looks at every parameter of a group, must not leave an empty one behind."""
+    params = [w.to(DEV) for w in _weights(SMALL, 0.02, seed=141)]
+    opt = _kernel_radam([dict(params=params, **INTERCHANGE)])
+    for p, g in zip(params[:2], _random_grads(SMALL[:2], 1, seed=142)[0]):
+        p.grad = g.to(DEV)
+    opt.step()
+    opt.graph_prepare()
+    assert len(opt.state) == 2 and params[2] not in opt.state
+    assert len(opt.state_dict()["state"]) == 2
