@@ -1,8 +1,9 @@
 """Plain torch / numpy references for the gather, mask and pooling glue kernels of csrc/conv.hip and csrc/rowops.hip: im2col and
 its adjoint in both column orders, the convolution weight re-layouts, channel padding, 2-D max pooling, masked pooling, token
-masking, ViT token assembly, the 1-D CNN's input features, the masked MSE and the counter-based dropout mask.  Shared by
-tests/test_glue_kernels_gpu.py (the kernels against these, on the card) and tests/test_glue_refs_cpu.py (these against F.conv2d,
-autograd and numpy, on any machine).
+masking, ViT token assembly, the 1-D CNN's input features, the masked MSE and the counter-based dropout mask; and for the
+implicit-GEMM convolutions of csrc/gemm.hip: the convolution with its three gradients in the layouts of the C ABI.  Shared by
+tests/test_glue_kernels_gpu.py and tests/test_conv_implicit_gpu.py (the kernels against these, on the card) and
+tests/test_glue_refs_cpu.py (these against F.conv2d, autograd and numpy, on any machine).
 
 Nothing here imports the package under test.  Data movement is compared bit for bit; references that add take a `dtype`:
 float64 gives the reference, float32 the yardstick e32 of convmixer_refs.check_all."""
@@ -83,6 +84,65 @@ def relayout_ref(w, co, ci, taps, mode, ci_pad=None):
 
 def pad_channels_ref(x, cp):
     return F.pad(x, (0, cp - x.shape[-1]))
+
+
+# ---------------------------------------------------------------------------------- the convolution and its gradients
+def conv_w_tap(w):
+    """(Cout, C, kh, kw) -> (Cout, kh*kw*C), tap-major with the channel fastest: the weight operand of the forward launch."""
+    co, ci, kh, kw = w.shape
+    return relayout_ref(w.reshape(co, -1), co, ci, kh * kw, 1).contiguous()
+
+
+def conv_w_tco(w):
+    """(Cout, C, kh, kw) -> (kh*kw*Cout, C), rows (tap, c_out): the weight operand of the dgrad launch."""
+    co, ci, kh, kw = w.shape
+    return relayout_ref(w.reshape(co, -1), co, ci, kh * kw, 2).contiguous()
+
+
+def conv2d_ref(x_cl, w, bias, stride, padding, dy_rows, relu, dtype=torch.float64):
+    """[relu](F.conv2d(x, w, bias)) and its autograd gradients under the cotangent `dy_rows`, at `dtype`, on the NCHW view of the
+    channels-last x_cl (B, H, W, C); w is (Cout, C, kh, kw), dy_rows is (B*OH*OW, Cout).  Returns, in the layouts of the C ABI:
+    y as rows (B*OH*OW, Cout), dx channels-last (B, H, W, C), dw_tap (Cout, kh*kw*C) tap-major, db (Cout).  bias = None is a zero
+    bias: db is then the gradient such a bias would get.  With relu the cotangent goes through relu(conv): ReLU'(0) = 0."""
+    co = w.shape[0]
+    x = x_cl.detach().to(dtype).permute(0, 3, 1, 2).contiguous().requires_grad_()
+    wr = w.detach().to(dtype, copy=True).requires_grad_()
+    br = (torch.zeros(co, dtype=dtype) if bias is None else bias.detach().to(dtype, copy=True)).requires_grad_()
+    y = F.conv2d(x, wr, br, stride=tuple(stride), padding=tuple(padding))
+    if relu:
+        y = torch.relu(y)
+    y_rows = y.permute(0, 2, 3, 1).reshape(-1, co)
+    dx, dw, db = torch.autograd.grad(y_rows, (x, wr, br), dy_rows.to(dtype).reshape(y_rows.shape))
+    return y_rows.detach().contiguous(), dx.permute(0, 2, 3, 1).contiguous(), conv_w_tap(dw), db
+
+
+# (B, H, W, C, Cout, kh, kw, sh, sw, ph, pw) of tests/test_conv_implicit_gpu.py (what each one is for: its docstring)
+IMPLICIT_GEOMS = [
+    (2, 6, 10, 64, 96, 3, 5, 1, 1, 0, 1),
+    (4, 6, 6, 96, 96, 3, 3, 1, 1, 0, 0),
+    (2, 6, 6, 96, 64, 3, 3, 1, 1, 2, 2),
+    (16, 5, 12, 64, 64, 2, 3, 1, 2, 1, 0),
+    (16, 7, 9, 64, 64, 3, 3, 2, 3, 1, 1),
+    (32, 7, 9, 64, 128, 1, 1, 2, 2, 0, 0),
+    (8, 1, 64, 64, 128, 1, 5, 1, 1, 0, 0),
+    (2, 8, 8, 160, 128, 3, 3, 1, 1, 1, 1),
+    (2, 8, 8, 128, 160, 3, 3, 1, 1, 1, 1),
+    (4, 8, 8, 256, 256, 3, 3, 1, 1, 1, 1),
+    (128, 8, 8, 64, 64, 3, 3, 1, 1, 1, 1),
+]
+
+
+def conv_inputs(case, integers):
+    """x_cl (B, H, W, C), w (Cout, C, kh, kw), bias (Cout), dy (B*OH*OW, Cout) of one geometry, seeded by it.  integers: values
+    in [-2, 2], the bias in [-3, 3] (every sum of the convolution and its gradients is exact in float32, in any order:
+    test_glue_refs_cpu.py checks that);  else x, dy ~ N(0, 1), w ~ 0.1 N(0, 1), bias ~ N(0, 1)."""
+    B, H, W, C, co, kh, kw, sh, sw, ph, pw = case
+    g = gen(sum(case) + 1000 * integers)
+    rows = B * conv_out(H, kh, sh, ph) * conv_out(W, kw, sw, pw)
+    if integers:
+        return ints((B, H, W, C), g, -2, 2), ints((co, C, kh, kw), g, -2, 2), ints((co,), g, -3, 3), ints((rows, co), g, -2, 2)
+    return (torch.randn(B, H, W, C, generator=g), 0.1 * torch.randn(co, C, kh, kw, generator=g), torch.randn(co, generator=g),
+            torch.randn(rows, co, generator=g))
 
 
 # ---------------------------------------------------------------------------------------------------- 2-D max pool

@@ -1,5 +1,6 @@
 """The references of tests/glue_refs.py against torch itself, on the CPU: the column orders against F.conv2d, the adjoints
-against the inner-product identity, the pooling backward against autograd, the dropout hash against its statistics."""
+against the inner-product identity, the convolution with its gradients against those two, the pooling backward against autograd,
+the dropout hash against its statistics."""
 import numpy as np
 import pytest
 import torch
@@ -49,6 +50,47 @@ def test_relayout_refs_invert_each_other_and_pad_with_zeros():
     assert torch.equal(t.view(co, taps, cp)[2, 4, :ci], w.view(co, ci, taps)[2, :, 4])
     assert torch.equal(G.relayout_ref(t, co, ci, taps, 0, cp), w)
     assert torch.equal(G.relayout_ref(w, co, ci, taps, 2).view(taps, co, ci)[4, 2], w.view(co, ci, taps)[2, :, 4])
+
+
+@pytest.mark.parametrize("relu", [False, True])
+@pytest.mark.parametrize("case", G.IMPLICIT_GEOMS, ids=lambda c: "-".join(map(str, c)))
+def test_conv2d_ref_is_the_verified_column_references_on_integers(case, relu):
+    """conv2d_ref (F.conv2d + autograd) against im2col_tap_ref / col2im_tap_ref / relayout_ref, which the tests above verify, in
+    float64 on the integer inputs the GPU tests use: equality, and every sum stays inside float32's exact range in any order."""
+    B, H, W, C, co, kh, kw = case[:7]
+    geom, taps = case[5:], kh * kw
+    x, w, b, dy = (t.double() for t in G.conv_inputs(case, True))
+    y, dx, dw_tap, db = G.conv2d_ref(x, w, b, case[7:9], case[9:11], dy, relu)
+    cols, w_tap = G.im2col_tap_ref(x, *geom), G.conv_w_tap(w)
+    assert y.shape == dy.shape == (cols.shape[0], co) and w_tap.shape == (co, taps * C)
+    assert dx.shape == x.shape and dw_tap.shape == w_tap.shape and db.shape == (co,)
+    pre = cols @ w_tap.t() + b
+    assert 0 < int((pre == 0).sum()) < pre.numel() // 20            # ReLU'(0) = 0 is exercised, and does not dominate
+    d = dy * (pre > 0) if relu else dy
+    assert torch.equal(torch.relu(pre) if relu else pre, y)
+    assert torch.equal(G.col2im_tap_ref(d @ w_tap, x.shape, *geom), dx)
+    assert torch.equal(d.t() @ cols, dw_tap)
+    assert torch.equal(G.relayout_ref(dw_tap, co, C, taps, 0), d.t() @ G.im2col_ref(x, *geom))     # tap-major back to torch's (c, u, v)
+    assert torch.equal(d.sum(0), db)
+    w_tco = G.conv_w_tco(w)
+    assert w_tco.shape == (taps * co, C) and torch.equal(w_tco.view(kh, kw, co, C)[kh - 1, 0, 3], w[3, :, kh - 1, 0])
+    # exactness in float32, whatever the order of summation: the sum of the magnitudes of any result's terms is below 2^24
+    assert max(4 * taps * C + 3, 4 * taps * co, 4 * cols.shape[0]) < 2 ** 24
+    assert max(float(t.abs().max()) for t in (y, dx, dw_tap, db)) < 1024
+    y32 = G.conv2d_ref(x.float(), w.float(), b.float(), case[7:9], case[9:11], dy.float(), relu, torch.float32)
+    assert all(t.dtype == torch.float32 for t in y32)                # the yardstick really runs at float32
+
+
+def test_conv2d_ref_without_bias_and_on_normal_inputs():
+    case = G.IMPLICIT_GEOMS[3]
+    x, w, b, dy = G.conv_inputs(case, False)
+    assert x.dtype == torch.float32 and abs(float(w.std()) - 0.1) < 0.01 and abs(float(x.std()) - 1.0) < 0.05
+    y0, dx0, dw0, db0 = G.conv2d_ref(x, w, None, case[7:9], case[9:11], dy, False)
+    y1, dx1, dw1, db1 = G.conv2d_ref(x, w, b, case[7:9], case[9:11], dy, False)
+    assert y0.dtype == F64
+    torch.testing.assert_close(y0 + b.double(), y1, rtol=1e-12, atol=1e-12)
+    assert torch.equal(dx0, dx1) and torch.equal(dw0, dw1) and torch.equal(db0, db1) and torch.equal(db0, dy.double().sum(0))
+    assert not x.requires_grad and not w.requires_grad           # the caller's tensors stay as they are
 
 
 @pytest.mark.parametrize("B,H,W,C,k,s,p", [(2, 9, 11, 5, 3, 2, 1), (1, 4, 4, 4, 2, 2, 0), (2, 7, 5, 6, 3, 1, 1)])
