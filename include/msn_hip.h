@@ -867,6 +867,35 @@ size_t msn_regression_stats_workspace_bytes(int64_t N);
 int msn_regression_stats(const float* pred, const float* target, int64_t N, double* acc, void* ws, size_t ws_bytes,
                          msn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Linear probes on frozen embeddings (probes.py; csrc/probes.hip): the two fp64 reductions a probe fit needs.  An fp32
+ * value times an fp32 value is exact in fp64, so only the additions round; their order is a function of the shape alone
+ * (per-slab / per-block fp64 partials in `ws`, added in a fixed order by a finishing launch: sixteen -- four up to eight
+ * partials -- interleaved groups, each in slab / block order, then the groups in group order), so the results repeat
+ * bit for bit from run to run and from device to device.  Two launches per call, no fills, no float atomics.
+ *
+ * Gram: G (M, M) fp64 row-major, M = D + 1 + K, receives Z^T Z for Z = [X | 1 | Y] assembled on the fly (Z is never
+ * written): X (N, D) fp32 with row stride ldx >= D, Y (N, K) fp32 with row stride ldy >= K, or NULL with K = 0; both
+ * 4-byte aligned (every load is a 4-byte load: the bits do not depend on stride or alignment).  accumulate = 0 stores
+ * the result, accumulate = 1 adds it to what G holds.  G[i][j] and G[j][i] are written from the same sum.  One matrix so
+ * carries X^T X, the column sums, n, X^T Y, 1^T Y and Y^T Y.  1 <= D <= 1024, 0 <= K <= 16, N >= 1, else MSN_ERR_SHAPE.
+ * msn_probe_gram_slab_rows: the rows of one slab for that shape (the partial sums change hands at its multiples). */
+int64_t msn_probe_gram_slab_rows(int64_t N, int D, int K);
+size_t msn_probe_gram_workspace_bytes(int64_t N, int D, int K);
+int msn_probe_gram(const float* X, int64_t ldx, const float* Y, int64_t ldy, int64_t N, int D, int K, double* G,
+                   int accumulate, void* ws, size_t ws_bytes, msn_stream_t stream);
+/* Multinomial logistic regression, loss and gradient in one evaluation: y int64 (N), class_weight C doubles or NULL
+ * (= ones), W (C, D + 1) fp64 row-major with the intercept in the last column, z_r = W [x_r | 1];
+ *   out[0] = sum_r w[y_r] (lse(z_r) - z_r[y_r]),   out[1 + c (D + 1) + d] = sum_r w[y_r] (softmax(z_r) - e_{y_r})[c] [x_r | 1][d]
+ * (1 + C (D + 1) doubles).  Everything in fp64: logits by fma, exp / log of the device math library on max-subtracted
+ * logits.  A row whose target lies outside [0, C) contributes nothing.  No regularisation term: the host adds it.
+ * 2 <= C, 1 <= D <= 1024, C (D + 1) <= 16400 (W stays in LDS as doubles), N >= 1, else MSN_ERR_SHAPE.
+ * msn_logreg_block_rows: the rows one workgroup owns for that shape. */
+int64_t msn_logreg_block_rows(int64_t N, int D, int C);
+size_t msn_logreg_workspace_bytes(int64_t N, int D, int C);
+int msn_logreg_loss_grad(const float* X, int64_t ldx, const int64_t* y, const double* class_weight, int64_t N, int D, int C,
+                         const double* W, double* out, void* ws, size_t ws_bytes, msn_stream_t stream);
+
 /* feat[r] = (x[r]*m, t[r]*inv_norm*m, m, 0), m = mask[r]: the 4 input channels of the build-defined 1-D CNN
  * encoder for light curves / spectra (value, normalised time / wavelength, validity, pad). */
 int msn_series_features(const float* x, const float* t, const uint8_t* mask, int64_t rows, float inv_norm,

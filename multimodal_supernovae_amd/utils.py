@@ -37,3 +37,34 @@ def get_AUC(embs1, embs2):
     """Area under that curve (ref src/utils.py:414-426)."""
     thresholds, fraction_correct = get_ROC_data(embs1, embs2)
     return np.trapezoid(fraction_correct, thresholds) if hasattr(np, "trapezoid") else np.trapz(fraction_correct, thresholds)
+
+
+def get_linear_predictions(X, Y, X_val=None, Y_val=None, task="regression", **probe_kwargs):
+    """Fit a linear probe on the embeddings (X, Y) and return its predictions for X_val (for X when X_val is None) as a
+    tensor on the device: fp32 values for task="regression" (probes.LinearRegressionProbe), int32 classes for
+    task="classification" (probes.LogisticRegressionProbe); probe_kwargs go to the probe.  Named after the reference's helper
+    (SURVEY.md section 2 row 7); the reference's source is not available to this build, so this is the helper's role and not
+    a line-by-line port.  Y_val is accepted for the reference's call shape and is not used."""
+    from .probes import LinearRegressionProbe, LogisticRegressionProbe
+    if task == "regression":
+        probe = LinearRegressionProbe(**probe_kwargs).fit(X, Y)
+    elif task == "classification":
+        probe = LogisticRegressionProbe(**probe_kwargs).fit(X, Y)
+    else:
+        raise ValueError(f"get_linear_predictions: task must be 'regression' or 'classification' (got {task!r})")
+    return probe.predict(X if X_val is None else X_val)
+
+
+def linear_probe_metrics(X, Y, X_val, Y_val, task="regression", n_classes=None, **probe_kwargs):
+    """The metrics of a linear probe fitted on (X, Y) and evaluated on (X_val, Y_val), with the keys of the reference's
+    pickles: L1, L2, R2, OLF for task="regression" (RegressionMetrics), acc and the F1 scores for task="classification"
+    (ClassificationMetrics over n_classes, by default the largest class of Y and Y_val plus one)."""
+    from .models_finetune import ClassificationMetrics, RegressionMetrics
+    if task == "classification":
+        if n_classes is None:
+            n_classes = int(max(Y.max().item(), Y_val.max().item())) + 1
+        probe_kwargs = dict(probe_kwargs, n_classes=n_classes)
+    pred = get_linear_predictions(X, Y, X_val, Y_val, task=task, **probe_kwargs)
+    metrics = RegressionMetrics() if task == "regression" else ClassificationMetrics(n_classes)
+    metrics.update(pred, Y_val)
+    return metrics.compute()
