@@ -477,6 +477,34 @@ int msn_cls_attention_fwd(const float* q, int64_t ldq, const void* kv, int64_t l
 int msn_cls_attention_bwd(const float* q, int64_t ldq, const void* kv, int64_t ldkv, int kv_bf16, int B, int H, int T, int head_dim,
                           float scale, const float* out, int64_t ldo, const float* probs, const float* dout, int64_t ldd, float* dq,
                           int64_t lddq, void* dkv, int64_t lddkv, msn_stream_t stream);
+/* The same class-token attention WITHOUT keys and values (csrc/cls_pool.hip).  With one query per (sample, head) the key | value
+ * projection of every token folds into B-row products: score s[b,j,h] = scale (qt[b,h] . h1[b,j] + q[b,h] . bk_h) with
+ * qt[b,h] = Wk_h^T q[b,h], and the attention row a[b,h] = Wv_h m[b,h] + bv_h with m[b,h] = sum_j p[b,j,h] h1[b,j], h1 = LN1(x).
+ * What runs over every token is three streaming kernels, one workgroup per sample, a wave per token row:
+ *   fwd: reads x (B*T rows of e floats, row stride ldx) once; LayerNorm per row with msn_layernorm_fwd's arithmetic (h1 is never
+ *        stored); writes mean / rstd (B*T), the probabilities probs (B, H, T) and m (B, H, e).  qt: (B, H, e).  q (B rows, stride
+ *        ldq) and bk (e) give the per-(b, h) score constant; both NULL = 0 (it cancels in the softmax).
+ *   dqt: first half of the backward.  Reads x once, recomputes h1, and from dm[b,h] = Wv_h^T da[b,h] (B, H, e) and the forward's
+ *        m forms ds[b,h,j] = p (dm . h1 - dm . m) (B, H, T) and dqt[b,h] = scale sum_j ds h1[b,j] (B, H, e).
+ *   bwd: second half.  Reads x once more; dh1[b,j] = sum_h (p dm + scale ds qt), on the class row + dcls[b] (B rows, stride ldcls,
+ *        nullable: the gradient that reaches h1 through the query, dq Wq with dq = Wk_h dqt -- it depends on dqt, which is why
+ *        the backward is two launches with B-row products between them); LayerNorm backward of each dh1 row with
+ *        msn_layernorm_bwd's arithmetic, + dskip[b] (nullable: the skip connection) on the class row; dx (row stride lddx) is
+ *        written once.  dgamma / dbeta: per-workgroup partials in ws, summed in a fixed order (no atomics: two runs give the
+ *        same bits).
+ * Supported (msn_cls_pool_supported): e % 4 == 0, e <= 512, heads <= 8 dividing e, 1 <= T <= 256. */
+int msn_cls_pool_supported(int T, int e, int heads);
+int msn_cls_pool_fwd(const float* x, int64_t ldx, int B, int T, int e, int heads, const float* gamma, const float* beta, float eps,
+                     const float* qt, const float* q, int64_t ldq, const float* bk, float scale, float* mean, float* rstd,
+                     float* probs, float* m, msn_stream_t stream);
+int msn_cls_pool_dqt(const float* x, int64_t ldx, int B, int T, int e, int heads, const float* mean, const float* rstd,
+                     const float* gamma, const float* beta, const float* probs, const float* m, const float* dm, float scale,
+                     float* ds, float* dqt, msn_stream_t stream);
+size_t msn_cls_pool_bwd_workspace_bytes(int B, int e);
+int msn_cls_pool_bwd(const float* x, int64_t ldx, int B, int T, int e, int heads, const float* mean, const float* rstd,
+                     const float* gamma, const float* beta, const float* qt, const float* probs, const float* dm, const float* ds,
+                     float scale, const float* dcls, int64_t ldcls, const float* dskip, int64_t ldskip, float* dx, int64_t lddx,
+                     float* dgamma, float* dbeta, void* ws, size_t ws_bytes, msn_stream_t stream);
 /* Two implementations sit behind msn_attention_*: vector-ALU kernels (head widths up to 32, any length; the
  * reference-native 8-wide heads, widths that are not a multiple of 4, unaligned operands) and matrix-core
  * kernels (v_mfma_f32_16x16x4_f32; any length -- chunked beyond 128 tokens; every head width that is a

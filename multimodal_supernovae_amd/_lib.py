@@ -32,6 +32,14 @@ SIGNATURES = {
     "msn_cls_attention_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_f32, c_ptr, c_i64, c_ptr, c_ptr]),
     "msn_cls_attention_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_f32, c_ptr, c_i64, c_ptr, c_ptr,
                                       c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
+    "msn_cls_pool_supported": (c_int, [c_int, c_int, c_int]),
+    "msn_cls_pool_fwd": (c_int, [c_ptr, c_i64, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_f32, c_ptr, c_ptr, c_i64, c_ptr, c_f32,
+                                 c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "msn_cls_pool_dqt": (c_int, [c_ptr, c_i64, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f32,
+                                 c_ptr, c_ptr, c_ptr]),
+    "msn_cls_pool_bwd_workspace_bytes": (c_size, [c_int, c_int]),
+    "msn_cls_pool_bwd": (c_int, [c_ptr, c_i64, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                 c_f32, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "msn_cast_bf16_list": (c_int, [c_int, c_ptr, c_ptr]),
     "msn_device_count": (c_int, []),
     "msn_sgemm_workspace_bytes": (c_size, [c_int, c_int, c_i64, c_i64, c_i64]),

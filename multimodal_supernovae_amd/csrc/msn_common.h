@@ -48,6 +48,9 @@ int colsum_finish(float* part, int nparts, int N, float* out, hipStream_t st);
 int colsum16_finish(const float* part, int nparts, int N, float* out, hipStream_t st);
 // C[i / K4][i % K4] = sum_s slabs[s][i], i < n4, in split order (float4 units; C rows ldc4 apart): the split-reduction GEMMs
 int slab_sum(const float* slabs, int splits, int64_t n4, int K4, int64_t ldc4, float* C, hipStream_t st);
+// dgamma / dbeta of a LayerNorm backward from per-workgroup partials part = [nslabs][2][cols]: sum_slabs_kernel of rowops.hip
+// (sixteen slab groups, combined one after the other), for the kernels outside rowops.hip that publish the same layout
+int ln_partials_finish(const float* part, int nslabs, int cols, float* dgamma, float* dbeta, hipStream_t st);
 
 // ---- device helpers -------------------------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

@@ -445,6 +445,13 @@ __global__ __launch_bounds__(1024) void sum_slabs_kernel(const float* __restrict
     }
 }
 
+int ln_partials_finish(const float* part, int nslabs, int cols, float* dgamma, float* dbeta, hipStream_t st) {
+    hipLaunchKernelGGL(sum_slabs_kernel, dim3((unsigned)cdiv(2 * cols, 64)), dim3(1024), 0, st, part, nslabs, 2 * cols, dgamma, dbeta,
+                       cols, static_cast<float*>(nullptr));
+    MSN_LAUNCH_CHECK();
+    return MSN_OK;
+}
+
 // ------------------------------------------------------------------------------------ L2 normalise
 template <int LPR>
 __global__ __launch_bounds__(256) void l2n_fwd_kernel(const float* __restrict__ x, int64_t ldx, RowGeom g,

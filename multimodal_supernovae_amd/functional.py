@@ -783,13 +783,89 @@ def _cls_rows_backward_ln1(B, T, e, dq2, h1c, kv_backward, wqkv, x2, m1, r1, g1,
     return dx, dg1, db1, dwqkv, dbqkv
 
 
+CLS_POOL = True       # False (tests, A/B runs): the last block's keys | values of every token as an msn_sgemm product
+
+
+def _head_diag(full, B, heads, d):
+    """full (B heads, heads d): the (B, heads, d) view of its diagonal blocks full[(b, h), h d : (h + 1) d]."""
+    return full.as_strided((B, heads, d), (heads * heads * d, heads * d + d, 1))
+
+
+def _head_rows(v, w, heads):
+    """out[b, h, :] = sum_i v[b, h d + i] w[h d + i, :] -- W_h^T v[b, h] for the d-row blocks W_h of w (e, e): v (B, e) ->
+    (B, heads, e).  ONE product of B heads rows: v is spread over the diagonal blocks of a zero (B heads, e) matrix (six
+    times the multiply-adds of six per-head products of 64-deep sums, a sixth of the launches)."""
+    B, e = v.shape
+    d = e // heads
+    spread = torch.zeros((B * heads, e), dtype=torch.float32, device=v.device)
+    _head_diag(spread, B, heads, d).copy_(v.view(B, heads, d))
+    return sgemm(spread, w, OP_N, OP_N).view(B, heads, e)
+
+
+def _head_cols(t, w, heads, bias=None):
+    """out[b, h d + i] = w[h d + i, :] . t[b, h, :] (+ bias): t (B, heads, e) -> (B, e); the diagonal blocks of ONE product."""
+    B, _, e = t.shape
+    full = sgemm(t.view(B * heads, e), w, OP_N, OP_T, bias=bias)
+    return _head_diag(full, B, heads, e // heads).reshape(B, e)
+
+
+def _head_wgrad(dy, t, heads, dw, db):
+    """dw[h d + i, :] = sum_b dy[b, h d + i] t[b, h, :] into dw (e, e) contiguous, column sums of dy into db (e): the diagonal
+    blocks of ONE weight-gradient product dy^T (B, heads e)."""
+    B, e = dy.shape
+    d = e // heads
+    full = torch.empty((e, heads * e), dtype=torch.float32, device=dy.device)
+    ops.wgrad_bias(dy, t.view(B, heads * e), out=(full, db))
+    dw.view(heads, d, e).copy_(full.as_strided((heads, d, e), (d * heads * e + e, heads * e, 1)))
+
+
+def _cls_pool_forward(x3, heads, eps, scale, g1, b1, wqkv, bqkv):
+    """LN1 + class-token attention of the last block without keys | values (_PreNormLastBlock, CLS_POOL): x3 (B, T, e) contiguous
+    -> (attention rows a2 (B, e), what _cls_pool_backward needs: (m1, r1, h1c, q, qt, probs, m))."""
+    e = x3.shape[2]
+    h1c, _, _ = ops.layernorm_fwd(x3[:, 0, :], g1, b1, eps)               # class rows: the query needs them first
+    q = sgemm(h1c, wqkv[:e], OP_N, OP_T, bias=bqkv[:e])
+    qt = _head_rows(q, wqkv[e:2 * e], heads)                              # Wk_h^T q[b, h]
+    m1, r1, probs, m = ops.cls_pool_fwd(x3, g1, b1, eps, qt, q, bqkv[e:2 * e], scale)
+    a2 = _head_cols(m, wqkv[2 * e:], heads, bias=bqkv[2 * e:])            # Wv_h m[b, h] + bv_h
+    return a2, (m1, r1, h1c, q, qt, probs, m)
+
+
+def _cls_pool_backward(x3, heads, scale, g1, b1, wqkv, pooled, da, dx1):
+    """From the gradient da of the attention rows and dx1 (B, e) of the class rows' skip connection up to the block's input
+    -> (dx (B, T, e), dg1, db1, dwqkv, dbqkv, (dm, dqt, dq))."""
+    e = x3.shape[2]
+    m1, r1, h1c, q, qt, probs, m = pooled
+    dwqkv = torch.empty_like(wqkv)
+    dbqkv = torch.empty(3 * e, dtype=torch.float32, device=da.device)
+    dm = _head_rows(da, wqkv[2 * e:], heads)                              # Wv_h^T da[b, h]
+    _head_wgrad(da, m, heads, dwqkv[2 * e:], dbqkv[2 * e:])               # dWv_h = sum_b da (x) m, dbv = sum_b da
+    ds, dqt = ops.cls_pool_dqt(x3, m1, r1, g1, b1, probs, m, dm, scale)
+    dq = _head_cols(dqt, wqkv[e:2 * e], heads)                            # Wk_h dqt[b, h]
+    _head_wgrad(q, dqt, heads, dwqkv[e:2 * e], dbqkv[e:2 * e])            # dWk_h = sum_b q (x) dqt
+    dbqkv[e:2 * e].zero_()                                                # dbk = scale sum_b (sum_j ds) q = 0 exactly
+    ops.wgrad_bias(dq, h1c, out=(dwqkv[:e], dbqkv[:e]))
+    dcls = sgemm(dq, wqkv[:e], OP_N, OP_N)                                # the query branch reaches the class rows only
+    dx, dg1, db1 = ops.cls_pool_bwd(x3, m1, r1, g1, b1, qt, probs, dm, ds, scale, dcls, dx1)
+    return dx, dg1, db1, dwqkv, dbqkv, (dm, dqt, dq)
+
+
 @_remember_precision
 class _PreNormLastBlock(torch.autograd.Function):
     """The LAST block of the build-defined ViT, evaluated for the class token only.  The head reads token 0 of the last
     block's output and nothing else, so of that block only the class row of x + Attn(LN1(x)) and of the MLP is ever used
     -- keys and values still come from every token.  Output (B, e) == pre_norm_block(x)[:, 0]; every gradient is identical
     (the rows left out have exactly zero gradient in the full evaluation).  Saves, per step, the query / output
-    projections, the attention rows and the whole MLP of (T - 1) / T of the last block's tokens."""
+    projections, the attention rows and the whole MLP of (T - 1) / T of the last block's tokens.
+
+    CLS_POOL (default, where ops.cls_pool_supported): keys and values are never formed.  With one query per (sample, head)
+    the sums are RE-ASSOCIATED so that the key | value weights multiply B rows instead of B T (csrc/cls_pool.hip):
+    scores = scale (Wk_h^T q) . h1 instead of q . (Wk_h h1 + bk_h) (+ q . bk_h, a constant per row of the softmax), attention
+    row = Wv_h (sum_j p h1_j) + bv_h instead of sum_j p (Wv_h h1_j + bv_h), and the same the other way in the backward; LN1 and
+    its backward run inside the three streaming kernels (the backward is two: the query's gradient on the class rows depends on
+    dqt, a sum over every token), so neither LN1's output nor keys | values nor their gradients reach memory.  Same output and gradients up to fp32 rounding (tests/test_cls_pool_gpu.py: error against fp64 <= 1.5 x the
+    error of the route below); the key bias's gradient, scale sum_b (sum_j ds) q whose exact value is 0, is written as zeros
+    (the route below leaves its rounding error there).  CLS_POOL = False: this node as it was."""
 
     @staticmethod
     def forward(ctx, x, heads, eps, g1, b1, wqkv, bqkv, wo, bo, g2, b2, w1, c1, w2, c2):
@@ -797,6 +873,13 @@ class _PreNormLastBlock(torch.autograd.Function):
         x3 = _c(x)
         x2 = x3.view(B * T, e)
         scale = 1.0 / math.sqrt(e // heads)
+        ctx.pool = CLS_POOL and ops.cls_pool_supported(T, e, heads)
+        if ctx.pool:
+            a2, pooled = _cls_pool_forward(x3, heads, eps, scale, g1, b1, wqkv, bqkv)
+            x1, m2, r2, h2, pre, f, out = _cls_rows_forward(a2, x3[:, 0, :], eps, wo, bo, g2, b2, w1, c1, w2, c2)
+            ctx.dims = (B, T, e, heads, scale, None)
+            ctx.save_for_backward(x3, g1, b1, wqkv, wo, g2, w1, w2, a2, x1, m2, r2, h2, pre, f, *pooled)
+            return out
         h1, m1, r1 = ops.layernorm_fwd(x2, g1, b1, eps)
         kv = sgemm(h1, wqkv[e:], OP_N, OP_T, bias=bqkv[e:])                   # keys | values of every token
         h1c = h1.view(B, T, e)[:, 0, :]                                       # class rows (row stride T * e)
@@ -816,6 +899,8 @@ class _PreNormLastBlock(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         B, T, e, heads, scale, cls_kernels = ctx.dims
+        if ctx.pool:
+            return _PreNormLastBlock._pool_backward(ctx, _c(dy))
         (x2, g1, wqkv, wo, g2, w1, w2, m1, r1, h1, kv, q, a2, lse, x1, m2, r2, h2, pre, f) = ctx.saved_tensors
         d = _c(dy)
         dx1, da, tail_grads = _cls_rows_backward(d, wo, g2, w1, w2, a2, x1, m2, r2, h2, pre, f)
@@ -835,6 +920,14 @@ class _PreNormLastBlock(torch.autograd.Function):
 
         dx, dg1, db1, dwqkv, dbqkv = _cls_rows_backward_ln1(B, T, e, dq2, h1.view(B, T, e)[:, 0, :], kv_backward, wqkv, x2, m1, r1,
                                                             g1, dx1)
+        return (dx, None, None, dg1, db1, dwqkv, dbqkv, *tail_grads)
+
+    @staticmethod
+    def _pool_backward(ctx, d):
+        B, T, e, heads, scale, _ = ctx.dims
+        (x3, g1, b1, wqkv, wo, g2, w1, w2, a2, x1, m2, r2, h2, pre, f, *pooled) = ctx.saved_tensors
+        dx1, da, tail_grads = _cls_rows_backward(d, wo, g2, w1, w2, a2, x1, m2, r2, h2, pre, f)
+        dx, dg1, db1, dwqkv, dbqkv, _ = _cls_pool_backward(x3, heads, scale, g1, b1, wqkv, pooled, da, dx1)
         return (dx, None, None, dg1, db1, dwqkv, dbqkv, *tail_grads)
 
 

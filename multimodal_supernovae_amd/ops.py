@@ -1175,6 +1175,62 @@ def cls_attention_bwd(q, kv, T, heads, scale, out, probs, dout):
     return dq, dkv
 
 
+def cls_pool_supported(T, e, heads):
+    return bool(lib().msn_cls_pool_supported(int(T), int(e), int(heads)))
+
+
+def cls_pool_fwd(x, gamma, beta, eps, qt, q, bk, scale):
+    """The class-token attention of the ViT's last block with the key | value weights moved to the query's side
+    (csrc/cls_pool.hip): x (B, T, e) contiguous, qt (B, heads, e) = Wk_h^T q[b, h], q (B, e) and bk (e) for the score constant
+    -> (mean (B T), rstd (B T) of LN1, probabilities (B, heads, T), m (B, heads, e) = sum_j p h1[b, j]).  msn_cls_pool_fwd."""
+    B, T, e = x.shape
+    heads = qt.shape[1]
+    _f32c(x, "x"), _f32c(qt, "qt"), _f32c(q, "q")
+    assert x.is_contiguous() and qt.is_contiguous() and qt.shape == (B, heads, e) and q.stride(1) == 1 and bk.is_contiguous()
+    dev = x.device
+    mean = torch.empty(B * T, dtype=torch.float32, device=dev)
+    rstd = torch.empty(B * T, dtype=torch.float32, device=dev)
+    probs = torch.empty((B, heads, T), dtype=torch.float32, device=dev)
+    m = torch.empty((B, heads, e), dtype=torch.float32, device=dev)
+    check(lib().msn_cls_pool_fwd(ptr(x), e, B, T, e, heads, ptr(gamma), ptr(beta), eps, ptr(qt), ptr(q), q.stride(0), ptr(bk), scale,
+                                 ptr(mean), ptr(rstd), ptr(probs), ptr(m), stream_ptr()), "msn_cls_pool_fwd")
+    return mean, rstd, probs, m
+
+
+def cls_pool_dqt(x, mean, rstd, gamma, beta, probs, m, dm, scale):
+    """First half of the backward -> (ds (B, heads, T), dqt (B, heads, e) = scale sum_j ds h1[b, j]).  msn_cls_pool_dqt."""
+    B, T, e = x.shape
+    heads = m.shape[1]
+    _f32c(dm, "dm")
+    assert x.is_contiguous() and m.is_contiguous() and dm.is_contiguous() and dm.shape == (B, heads, e)
+    ds = torch.empty((B, heads, T), dtype=torch.float32, device=x.device)
+    dqt = torch.empty((B, heads, e), dtype=torch.float32, device=x.device)
+    check(lib().msn_cls_pool_dqt(ptr(x), e, B, T, e, heads, ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(probs), ptr(m), ptr(dm),
+                                 scale, ptr(ds), ptr(dqt), stream_ptr()), "msn_cls_pool_dqt")
+    return ds, dqt
+
+
+def cls_pool_bwd(x, mean, rstd, gamma, beta, qt, probs, dm, ds, scale, dcls, dskip):
+    """Second half: dcls (B, e) joins the class rows of LN1's output gradient (the query's branch), dskip (B, e) the class rows of
+    dx (the skip connection) -> (dx (B, T, e), dgamma, dbeta).  msn_cls_pool_bwd."""
+    B, T, e = x.shape
+    heads = qt.shape[1]
+    _f32c(dcls, "dcls"), _f32c(dskip, "dskip")
+    assert x.is_contiguous() and qt.is_contiguous() and dm.is_contiguous() and ds.is_contiguous()
+    assert dcls.shape == (B, e) and dskip.shape == (B, e) and dcls.stride(1) == 1 and dskip.stride(1) == 1
+    dev = x.device
+    dx = torch.empty((B, T, e), dtype=torch.float32, device=dev)
+    dg = torch.empty(e, dtype=torch.float32, device=dev)
+    db = torch.empty(e, dtype=torch.float32, device=dev)
+    L = lib()
+    nb = L.msn_cls_pool_bwd_workspace_bytes(B, e)
+    ws = _workspace(nb, dev)
+    check(L.msn_cls_pool_bwd(ptr(x), e, B, T, e, heads, ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(qt), ptr(probs), ptr(dm),
+                             ptr(ds), scale, ptr(dcls), dcls.stride(0), ptr(dskip), dskip.stride(0), ptr(dx), e, ptr(dg), ptr(db),
+                             ptr(ws), nb, stream_ptr()), "msn_cls_pool_bwd")
+    return dx, dg, db
+
+
 def attention_fwd_planes_supported(T, head_dim):
     return T <= 128 and head_dim % 16 == 0 and head_dim <= 64
 
