@@ -924,6 +924,43 @@ size_t msn_logreg_workspace_bytes(int64_t N, int D, int C);
 int msn_logreg_loss_grad(const float* X, int64_t ldx, const int64_t* y, const double* class_weight, int64_t N, int D, int C,
                          const double* W, double* out, void* ws, size_t ws_bytes, msn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Exact k-nearest-neighbour search and kNN prediction on frozen embeddings (probes.py; csrc/knn.hip).
+ *
+ * Search: for fp32 queries Q (Nq, D), row stride ldq >= D, and a fp32 training set X (Nx, D), row stride ldx >= D, both
+ * 4-byte aligned (every load is a 4-byte load), idx (Nq, k) int32 and dist2 (Nq, k) fp64, both dense, receive per query the
+ * k training rows of smallest squared Euclidean distance, ascending.
+ *   Membership is decided on |q|^2 + |x|^2 - 2 q.x in fp64 (dot products on the fp64 matrix cores; an fp32 value times an
+ *   fp32 value is exact in fp64, so only the additions round, in an order that is a function of D alone), under the key
+ *   (d2, index), lower index first: a strict total order, so the k winners do not depend on how the rows are cut into
+ *   tiles and slabs.  Two rows whose true distances differ by less than the expansion's error (about
+ *   (D + 4) 2^-52 (|q|^2 + |x|^2)) may change places at the k-th position; exact ties never do.
+ *   dist2 is then recomputed for the k winners as sum_c (q_c - x_c)^2 by fma over c = 0 .. D - 1 in fp64: non-negative, 0 for
+ *   identical rows, and its bits depend on the two rows and D only -- not on Nq, Nx, position, stride or alignment.  The k
+ *   are sorted by (that value, index).  A NaN distance sorts last among the real rows.
+ *   self_offset: -1 for none; otherwise the candidate j == i + self_offset is skipped for query i (leave-one-out when the
+ *   queries are the training rows X[self_offset : self_offset + Nq]), and k <= Nx - 1 is required.
+ *   Per-slab lists of k keys per query sit in `ws` (msn_knn_workspace_bytes = 12 Nq slabs k bytes, rounded up to 8); the
+ *   Nq x Nx distances are never written to memory.  Two launches, no atomics, no fills: the same bits on every run.
+ *   1 <= D <= 1024, 1 <= k <= 64, k <= Nx (Nx - 1 with self_offset >= 0), Nx < 2^31, Nq >= 1, else MSN_ERR_SHAPE before any launch.
+ * msn_knn_slab_rows: the training rows one workgroup scans for that shape (the per-slab lists change hands at its multiples). */
+int64_t msn_knn_slab_rows(int64_t Nq, int64_t Nx, int D, int k);
+size_t msn_knn_workspace_bytes(int64_t Nq, int64_t Nx, int D, int k);
+int msn_knn_search(const float* Q, int64_t ldq, int64_t Nq, const float* X, int64_t ldx, int64_t Nx, int D, int k,
+                   int64_t self_offset, int* idx, double* dist2, void* ws, size_t ws_bytes, msn_stream_t stream);
+/* Prediction from a search's (idx, dist2), one launch each.  weights = 0: every neighbour weighs 1; weights = 1: 1 / sqrt(dist2),
+ * and where any of a query's k distances is 0 its zero-distance neighbours weigh 1 and the others 0 (scikit-learn's rule).
+ * Sums are fp64 and run in neighbour order t = 0 .. k - 1.
+ * Regression: Y (Nx, K) fp32, row stride ldy, 1 <= K <= 16; out (Nq, K) fp32, row stride ldo, = sum_t w_t y_t / sum_t w_t,
+ * rounded once to fp32 (uniform weights: the fp64 mean of the k targets). */
+int msn_knn_predict_regression(const int* idx, const double* dist2, int64_t Nq, int k, const float* Y, int64_t ldy, int K,
+                               int weights, float* out, int64_t ldo, msn_stream_t stream);
+/* Classification: y (Nx) int64 labels, 1 <= C <= 1024 classes; classes (Nq) int32 = the class of the largest vote (fp64 sums
+ * of the weights), the lowest class on equal votes; proba_or_null (Nq, C) fp32 dense = vote / sum of the votes (0 where no
+ * neighbour carries a label in range).  A label outside [0, C) is not an error here: it counts for no class. */
+int msn_knn_predict_classes(const int* idx, const double* dist2, int64_t Nq, int k, const int64_t* y, int C, int weights,
+                            int* classes, float* proba_or_null, msn_stream_t stream);
+
 /* feat[r] = (x[r]*m, t[r]*inv_norm*m, m, 0), m = mask[r]: the 4 input channels of the build-defined 1-D CNN
  * encoder for light curves / spectra (value, normalised time / wavelength, validity, pad). */
 int msn_series_features(const float* x, const float* t, const uint8_t* mask, int64_t rows, float inv_norm,

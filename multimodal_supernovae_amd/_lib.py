@@ -142,6 +142,11 @@ SIGNATURES = {
     "msn_logreg_block_rows": (c_i64, [c_i64, c_int, c_int]),
     "msn_logreg_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
     "msn_logreg_loss_grad": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "msn_knn_slab_rows": (c_i64, [c_i64, c_i64, c_int, c_int]),
+    "msn_knn_workspace_bytes": (c_size, [c_i64, c_i64, c_int, c_int]),
+    "msn_knn_search": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "msn_knn_predict_regression": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_int, c_ptr, c_i64, c_ptr]),
+    "msn_knn_predict_classes": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr]),
     "msn_series_features": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_f32, c_ptr, c_ptr]),
     "msn_relu_mask": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
     "msn_im2col": (c_int, [c_ptr] + [c_int] * 10 + [c_ptr, c_ptr]),

@@ -21,15 +21,9 @@
 #include <algorithm>
 #include <math.h>
 
-#include "msn_common.h"
+#include "mfma_f64.h"
 
 namespace msn {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f64x4 mfma_f64(double a, double b, f64x4 c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 
 // ------------------------------------------------------------------------------------------------------ Gram
 constexpr int kGramTile = 64;             // edge of a workgroup's tile of G

@@ -9,9 +9,14 @@ checked against numpy fp64 restatements in tests/test_probes_cpu.py and tests/te
                              device (msn_logreg_loss_grad): per evaluation W goes up, 1 + C (D + 1) doubles come down
     solve_normal_equations, lbfgs
                              the host halves, pure numpy fp64: importable and testable without a GPU
+    knn_search, KNeighborsRegressorProbe, KNeighborsClassifierProbe
+                             exact k-nearest-neighbour search in fp64 on the device (csrc/knn.hip: msn_knn_search) and the
+                             weighted mean / vote over the neighbours (msn_knn_predict_*); nothing is copied to the host
+    knn_reference, knn_predict_reference
+                             their numpy fp64 restatements, importable without a GPU
 
 No scipy or scikit-learn at run time.  The classes issue no collective: with several ranks, all-reduce `probe.gram`
-before `solve()`.
+before `solve()`, and gather the embeddings before a kNN probe.
 """
 from collections import namedtuple
 
@@ -368,3 +373,253 @@ class LogisticRegressionProbe:
         """Class per row, int32 (first maximal index, as torch.argmax)."""
         from .models_finetune import argmax_rows
         return argmax_rows(self.decision_function(X))
+
+
+# ------------------------------------------------------------------------------------------------ host: kNN restated
+def _weights_code(weights, who):
+    if weights not in ("uniform", "distance"):
+        raise ValueError(f"{who}: weights must be 'uniform' or 'distance' (got {weights!r})")
+    return 1 if weights == "distance" else 0
+
+
+def knn_reference(Q, X, k, self_offset=-1):
+    """numpy fp64 restatement of msn_knn_search: (idx int32 (Nq, k), dist2 fp64 (Nq, k)).  Distances in the direct form
+    sum_c (q_c - x_c)^2; order by np.argsort(kind="stable"), so the lower index comes first among equal distances; with
+    self_offset >= 0 the row i + self_offset is no candidate of query i."""
+    Q = np.asarray(Q, dtype=np.float64)
+    X = np.asarray(X, dtype=np.float64)
+    k, self_offset = int(k), int(self_offset)
+    if Q.ndim != 2 or X.ndim != 2 or Q.shape[1] != X.shape[1]:
+        raise ValueError(f"knn_reference: Q (Nq, D) and X (Nx, D) needed (got {Q.shape} and {X.shape})")
+    if not 1 <= k <= len(X) - (1 if self_offset >= 0 else 0):
+        raise ValueError(f"knn_reference: k = {k} outside 1..{len(X) - (1 if self_offset >= 0 else 0)}")
+    idx = np.empty((len(Q), k), dtype=np.int32)
+    dist2 = np.empty((len(Q), k), dtype=np.float64)
+    for i, q in enumerate(Q):
+        d = ((X - q) ** 2).sum(axis=1)
+        order = np.argsort(d, kind="stable")
+        if self_offset >= 0:
+            order = order[order != i + self_offset]
+        idx[i] = order[:k]
+        dist2[i] = d[order[:k]]
+    return idx, dist2
+
+
+def knn_predict_reference(idx, dist2, targets, weights="uniform", task="regression", n_classes=None):
+    """numpy fp64 restatement of the kNN prediction kernels over a search's (idx, dist2).  Weights: 1 (uniform) or
+    1 / sqrt(dist2) (distance); a query with a zero distance among its k gives its zero-distance neighbours weight 1 and the
+    others 0 (scikit-learn's rule).  Sums run in neighbour order.
+    task="regression": targets (Nx,) or (Nx, K) -> fp64 predictions (Nq,) or (Nq, K), sum w y / sum w.
+    task="classification": targets (Nx,) ints -> (classes int32 (Nq,), votes fp64 (Nq, n_classes)); the lowest class wins
+    equal votes; a label outside [0, n_classes) counts for no class."""
+    code = _weights_code(weights, "knn_predict_reference")
+    idx = np.asarray(idx).astype(np.int64)
+    dist2 = np.asarray(dist2, dtype=np.float64)
+    nq, k = idx.shape
+    if code:
+        zero = dist2 == 0.0
+        with np.errstate(divide="ignore"):
+            w = np.where(zero.any(axis=1, keepdims=True), zero.astype(np.float64), 1.0 / np.sqrt(dist2))
+    else:
+        w = np.ones((nq, k))
+    if task == "regression":
+        Y = np.asarray(targets, dtype=np.float64)
+        flat = Y.ndim == 1
+        Y = Y.reshape(len(Y), -1)
+        num = np.zeros((nq, Y.shape[1]))
+        den = np.zeros(nq)
+        for t in range(k):
+            num += w[:, t, None] * Y[idx[:, t]]
+            den += w[:, t]
+        out = num / den[:, None]
+        return out[:, 0] if flat else out
+    if task != "classification":
+        raise ValueError(f"knn_predict_reference: task must be 'regression' or 'classification' (got {task!r})")
+    y = np.asarray(targets).astype(np.int64)
+    C = int(n_classes) if n_classes is not None else int(y.max()) + 1
+    votes = np.zeros((nq, C))
+    rows = np.arange(nq)
+    for t in range(k):
+        lab = y[idx[:, t]]
+        ok = (lab >= 0) & (lab < C)
+        votes[rows[ok], lab[ok]] += w[ok, t]
+    return votes.argmax(axis=1).astype(np.int32), votes
+
+
+# ----------------------------------------------------------------------------------------------------- device: kNN
+KNN_MAX_K = 64
+KNN_MAX_CLASSES = 1024
+
+
+def _knn_metric(metric, who):
+    if metric not in ("euclidean", "cosine"):
+        raise ValueError(f"{who}: metric must be 'euclidean' or 'cosine' (got {metric!r})")
+    return metric
+
+
+def _unit_rows(X):
+    from . import ops
+    return ops.l2norm_fwd(X.contiguous())[0]
+
+
+def _knn_search_sq(Q, X, k, self_offset):
+    """(idx int32 (Nq, k), dist2 fp64 (Nq, k)) of msn_knn_search over checked device tensors.  Enqueue only."""
+    if Q.device != X.device:
+        raise _lib.MsnHipError("knn_search: queries and training set must live on the same GPU")
+    if Q.shape[1] != X.shape[1]:
+        raise ValueError(f"knn_search: queries have {Q.shape[1]} columns, the training set {X.shape[1]}")
+    (Nq, D), Nx = Q.shape, X.shape[0]
+    idx = torch.empty((Nq, k), dtype=torch.int32, device=Q.device)
+    dist2 = torch.empty((Nq, k), dtype=torch.float64, device=Q.device)
+    L = lib()
+    ws = _ws(L.msn_knn_workspace_bytes(Nq, Nx, D, k), Q.device)
+    check(L.msn_knn_search(ptr(Q), _ld(Q), Nq, ptr(X), _ld(X), Nx, D, k, self_offset, ptr(idx), ptr(dist2), ptr(ws),
+                           ws.numel() * 8, stream_ptr()), "msn_knn_search")
+    return idx, dist2
+
+
+def _self_offset(exclude_self):
+    if exclude_self is False or exclude_self is None:
+        return -1
+    if exclude_self is True:
+        return 0
+    if int(exclude_self) < 0:
+        raise ValueError(f"knn_search: exclude_self must be False or the row offset of the queries (got {exclude_self!r})")
+    return int(exclude_self)
+
+
+def knn_search(Q, X, k, metric="euclidean", exclude_self=False, return_squared=False):
+    """The k nearest rows of X (Nx, D) for every row of Q (Nq, D), exactly: (idx int32 (Nq, k), dist fp64 (Nq, k)), ascending,
+    ties by the lower index (msn_knn_search).  metric="euclidean" returns sqrt(d^2) as scikit-learn does; "cosine"
+    L2-normalises both sides first (ops.l2norm_fwd, which takes D a multiple of 4) and returns 1 - cos = d^2 / 2.  return_squared=True returns the kernel's
+    d^2 untouched (of the normalised rows for "cosine").  exclude_self: False, or the offset o of the queries in the training
+    set (True = 0): query i never finds row i + o -- leave-one-out for Q = X[o : o + n].  Enqueue only."""
+    _knn_metric(metric, "knn_search")
+    same = Q is X
+    Q = _embeddings(Q, "knn_search")
+    X = Q if same else _embeddings(X, "knn_search")
+    if metric == "cosine":
+        Q = _unit_rows(Q)
+        X = Q if same else _unit_rows(X)
+    idx, d2 = _knn_search_sq(Q, X, int(k), _self_offset(exclude_self))
+    if return_squared:
+        return idx, d2
+    return idx, (d2 * 0.5 if metric == "cosine" else d2.sqrt())
+
+
+class _KNeighborsProbe:
+    """What the two kNN probes share: the training set kept on the device (unit rows for metric="cosine") and the search."""
+
+    def __init__(self, n_neighbors=5, weights="uniform", metric="euclidean"):
+        who = type(self).__name__
+        if not 1 <= int(n_neighbors) <= KNN_MAX_K:
+            raise ValueError(f"{who}: n_neighbors must be in 1..{KNN_MAX_K} (got {n_neighbors})")
+        self.n_neighbors, self.weights, self.metric = int(n_neighbors), weights, _knn_metric(metric, who)
+        self._wcode = _weights_code(weights, who)
+        self._X = self._t = None
+
+    def _fit_x(self, X):
+        X = _embeddings(X, f"{type(self).__name__}.fit")        # a reference: contiguous input is not copied
+        if X.shape[1] > MAX_D:
+            raise _lib.MsnHipError(f"{type(self).__name__}: D <= {MAX_D} (got {X.shape[1]})")
+        self._X = _unit_rows(X) if self.metric == "cosine" else X
+        return X
+
+    def _targets_on(self, X, Y):
+        if not isinstance(Y, torch.Tensor) or Y.device != X.device:
+            raise _lib.MsnHipError(f"{type(self).__name__}.fit: targets must live on the GPU next to the embeddings; "
+                                   "there is no CPU path")
+        if Y.shape[0] != X.shape[0]:
+            raise ValueError(f"{type(self).__name__}.fit: {X.shape[0]} rows of embeddings, {Y.shape[0]} targets")
+        return Y.detach()
+
+    def _search(self, X, k):
+        """(idx, d^2) for the rows of X, or leave-one-out over the training set for X = None."""
+        if self._X is None:
+            raise ValueError(f"{type(self).__name__}: not fitted")
+        if X is None:
+            return _knn_search_sq(self._X, self._X, k, 0)
+        Q = _embeddings(X, f"{type(self).__name__}")
+        return _knn_search_sq(_unit_rows(Q) if self.metric == "cosine" else Q, self._X, k, -1)
+
+    def kneighbors(self, X=None, n_neighbors=None, return_distance=True):
+        """scikit-learn's call: (distances fp64 (Nq, k), indices int32 (Nq, k)), or the indices alone with
+        return_distance=False.  X = None searches the training set itself, every row without itself."""
+        idx, d2 = self._search(X, self.n_neighbors if n_neighbors is None else int(n_neighbors))
+        if not return_distance:
+            return idx
+        return (d2 * 0.5 if self.metric == "cosine" else d2.sqrt()), idx
+
+    def _neighbours(self, X):
+        """(idx, the squared distance the prediction kernels weigh by) at n_neighbors."""
+        idx, d2 = self._search(X, self.n_neighbors)
+        if self.metric == "cosine" and self._wcode:
+            d2 = (d2 * 0.5).square()                         # the kernels weigh by 1 / sqrt: the distance here is 1 - cos
+        return idx, d2
+
+
+class KNeighborsRegressorProbe(_KNeighborsProbe):
+    """KNeighborsRegressor on embeddings: exact search (msn_knn_search), then the weighted mean of the neighbours' targets in
+    fp64, rounded once to fp32 (msn_knn_predict_regression).  predict() / kneighbors() without X are leave-one-out over the
+    training set.  Approximate search, other metrics, k > 64, radius_neighbors and sample weights are not built."""
+
+    def fit(self, X, Y):
+        X = self._fit_x(X)
+        Y = self._targets_on(X, Y)
+        self._flat = Y.dim() == 1
+        Y2 = Y.to(torch.float32)
+        Y2 = Y2.reshape(-1, 1) if self._flat else Y2
+        if Y2.dim() != 2 or not 1 <= Y2.shape[1] <= MAX_K:
+            raise ValueError(f"KNeighborsRegressorProbe: 1 to {MAX_K} target columns (got {tuple(Y.shape)})")
+        if (Y2.stride(1) != 1 and Y2.shape[1] > 1) or Y2.stride(0) < Y2.shape[1]:
+            Y2 = Y2.contiguous()
+        self._t = Y2
+        return self
+
+    def predict(self, X=None):
+        idx, d2 = self._neighbours(X)
+        Nq, k = idx.shape
+        K = self._t.shape[1]
+        out = torch.empty((Nq, K), dtype=torch.float32, device=idx.device)
+        check(lib().msn_knn_predict_regression(ptr(idx), ptr(d2), Nq, k, ptr(self._t), _ld(self._t), K, self._wcode, ptr(out), K,
+                                               stream_ptr()), "msn_knn_predict_regression")
+        return out[:, 0] if self._flat else out
+
+
+class KNeighborsClassifierProbe(_KNeighborsProbe):
+    """KNeighborsClassifier on embeddings: exact search, then the weighted vote in fp64 (msn_knn_predict_classes); the lowest
+    class wins equal votes, as scikit-learn's mode does.  predict returns int32 classes, like LogisticRegressionProbe."""
+
+    def __init__(self, n_neighbors=5, weights="uniform", metric="euclidean", n_classes=None):
+        super().__init__(n_neighbors, weights, metric)
+        self.n_classes = n_classes
+
+    def fit(self, X, y):
+        X = self._fit_x(X)
+        y = self._targets_on(X, y)
+        if y.dim() != 1:
+            raise ValueError(f"KNeighborsClassifierProbe.fit: labels must have shape ({X.shape[0]},) (got {tuple(y.shape)})")
+        y = y.to(torch.int64).contiguous()
+        lo, hi = int(y.min().item()), int(y.max().item())
+        nc = int(self.n_classes) if self.n_classes is not None else hi + 1
+        if lo < 0 or hi >= nc or not 1 <= nc <= KNN_MAX_CLASSES:
+            raise _lib.MsnHipError(f"KNeighborsClassifierProbe: labels must lie in [0, n_classes) with n_classes <= "
+                                   f"{KNN_MAX_CLASSES} (got labels {lo}..{hi}, n_classes = {nc})")
+        self._t, self._nc = y, nc
+        return self
+
+    def _vote(self, X, want_proba):
+        idx, d2 = self._neighbours(X)
+        Nq, k = idx.shape
+        classes = torch.empty(Nq, dtype=torch.int32, device=idx.device)
+        proba = torch.empty((Nq, self._nc), dtype=torch.float32, device=idx.device) if want_proba else None
+        check(lib().msn_knn_predict_classes(ptr(idx), ptr(d2), Nq, k, ptr(self._t), self._nc, self._wcode, ptr(classes),
+                                            ptr(proba), stream_ptr()), "msn_knn_predict_classes")
+        return classes, proba
+
+    def predict(self, X=None):
+        return self._vote(X, False)[0]
+
+    def predict_proba(self, X=None):
+        """(Nq, n_classes) fp32: each class's share of the votes."""
+        return self._vote(X, True)[1]

@@ -68,3 +68,34 @@ def linear_probe_metrics(X, Y, X_val, Y_val, task="regression", n_classes=None, 
     metrics = RegressionMetrics() if task == "regression" else ClassificationMetrics(n_classes)
     metrics.update(pred, Y_val)
     return metrics.compute()
+
+
+def get_knn_predictions(X, Y, X_val=None, Y_val=None, k=5, task="regression", **probe_kwargs):
+    """Fit a k-nearest-neighbour probe on the embeddings (X, Y) and return its predictions for X_val as a tensor on the
+    device: fp32 values for task="regression" (probes.KNeighborsRegressorProbe), int32 classes for task="classification"
+    (probes.KNeighborsClassifierProbe); probe_kwargs (weights, metric, n_classes) go to the probe.  With X_val = None the
+    training set is predicted leave-one-out: no row is its own neighbour.  The kNN counterpart of get_linear_predictions;
+    Y_val is accepted for the reference's call shape and is not used."""
+    from .probes import KNeighborsClassifierProbe, KNeighborsRegressorProbe
+    if task == "regression":
+        probe = KNeighborsRegressorProbe(n_neighbors=k, **probe_kwargs).fit(X, Y)
+    elif task == "classification":
+        probe = KNeighborsClassifierProbe(n_neighbors=k, **probe_kwargs).fit(X, Y)
+    else:
+        raise ValueError(f"get_knn_predictions: task must be 'regression' or 'classification' (got {task!r})")
+    return probe.predict(X_val)
+
+
+def knn_probe_metrics(X, Y, X_val, Y_val, k=5, task="regression", n_classes=None, **probe_kwargs):
+    """The metrics of a kNN probe fitted on (X, Y) and evaluated on (X_val, Y_val), with the keys of linear_probe_metrics:
+    L1, L2, R2, OLF for task="regression", acc and the F1 scores for task="classification" (over n_classes, by default the
+    largest class of Y and Y_val plus one)."""
+    from .models_finetune import ClassificationMetrics, RegressionMetrics
+    if task == "classification":
+        if n_classes is None:
+            n_classes = int(max(Y.max().item(), Y_val.max().item())) + 1
+        probe_kwargs = dict(probe_kwargs, n_classes=n_classes)
+    pred = get_knn_predictions(X, Y, X_val, Y_val, k=k, task=task, **probe_kwargs)
+    metrics = RegressionMetrics() if task == "regression" else ClassificationMetrics(n_classes)
+    metrics.update(pred, Y_val)
+    return metrics.compute()
