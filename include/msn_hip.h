@@ -961,6 +961,51 @@ int msn_knn_predict_regression(const int* idx, const double* dist2, int64_t Nq, 
 int msn_knn_predict_classes(const int* idx, const double* dist2, int64_t Nq, int k, const int64_t* y, int C, int weights,
                             int* classes, float* proba_or_null, msn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Threshold-free classification metrics (metrics.py; csrc/rank_metrics.hip): one-vs-rest AUROC, average precision, binned
+ * ROC / precision-recall curves and top-k accuracy from integer counts.  Shared by the four entry points: S (N, C) fp32
+ * scores with row stride ld >= C, 4-byte aligned (every load of S is a 4-byte load: the bits do not depend on stride or
+ * alignment); y int64 (N); a row whose target lies outside [0, C) -- -100 is the usual such value -- is ignored everywhere:
+ * neither a positive nor a negative of any class.  Comparisons are IEEE fp32 compares: -0.0 == 0.0, infinities are ordered,
+ * and a NaN score compares false both ways (it lies above nothing and at-or-above nothing, itself included: a row whose own
+ * score is NaN has p_ge = 0 and turns its class's ap_sum into nan; under msn_threshold_counts it reaches no threshold; under
+ * msn_topk_ranks a NaN target score gives rank 0).  1 <= N < 2^31, 1 <= C <= 1024, 1 <= T <= 1024, else MSN_ERR_SHAPE before
+ * any launch.
+ *
+ * Pair counts: for every valid row i with c = y_i and s = S[i, c], over all valid rows j,
+ *   counts[i] = {n_gt, n_ge, p_ge} = {#(y_j != c, S[j, c] > s), #(y_j != c, S[j, c] >= s), #(y_j == c, S[j, c] >= s)}
+ * (int32 (N, 3); p_ge counts i itself; ignored rows get zeros), and per class
+ *   istats[c] = {P_c, Nneg_c, U2_c} (int64 (C, 3)), U2_c = sum_{y_i = c} (2 Nneg_c - n_gt[i] - n_ge[i]),
+ *   ap_sum[c] = sum_{y_i = c} p_ge[i] / (p_ge[i] + n_ge[i]) (fp64 (C); each quotient rounded once),
+ * so that AUROC_c = U2_c / (2 P_c Nneg_c) (Mann-Whitney, ties at one half) and AP_c = ap_sum[c] / P_c (all positives at one
+ * score share one precision: scikit-learn's rule) on the host.  O(N^2) compares; per-slab int32 partials sit in `ws`
+ * (msn_rank_counts_workspace_bytes = 12 N slabs bytes) and a second launch finishes: no atomics on memory, no fills, no
+ * flags.  counts and istats are integers, so they do not depend on how the rows are cut; ap_sum is added in an order that is
+ * a function of N alone (thread t of 1024 adds its rows t, t + 1024, ... in order, 0.0 for a row of another class; then the
+ * fixed-order block combine).  Everything repeats bit for bit. */
+size_t msn_rank_counts_workspace_bytes(int64_t N, int C);
+int msn_rank_counts(const float* S, int64_t ld, const int64_t* y, int64_t N, int C, int* counts, int64_t* istats,
+                    double* ap_sum, void* ws, size_t ws_bytes, msn_stream_t stream);
+/* Binned curves: thr T ascending fp32 thresholds (DEVICE); acc int64 (C, T, 2) and tot int64 (C, 2), caller-owned DEVICE
+ * accumulators over calls (as msn_confusion_matrix's cm):
+ *   acc[c, t, 0] += #(i valid, y_i == c, S[i, c] >= thr[t])      acc[c, t, 1] += #(i valid, y_i != c, S[i, c] >= thr[t])
+ *   tot[c] += {P_c, Nneg_c}
+ * One launch; integer adds only (per-workgroup histogram in LDS over the number of thresholds <= s, suffix sums, one add per
+ * non-zero cell), so the result does not depend on their order. */
+int msn_threshold_counts(const float* S, int64_t ld, const int64_t* y, int64_t N, int C, const float* thr, int T,
+                         int64_t* acc, int64_t* tot, msn_stream_t stream);
+/* rank[i] = #(c' : S[i, c'] > S[i, y_i], or S[i, c'] == S[i, y_i] and c' < y_i) per valid row -- among equal scores the
+ * lower class comes first, the arg-max rule of msn_cross_entropy_fwd -- into rank_or_null (int32 (N), -1 for ignored rows),
+ * and hist[rank[i]] += 1 into a caller-owned int64 (C) DEVICE accumulator: top-k accuracy for every k is a prefix sum of hist.
+ * One launch, integer adds only. */
+int msn_topk_ranks(const float* S, int64_t ld, const int64_t* y, int64_t N, int C, int* rank_or_null, int64_t* hist,
+                   msn_stream_t stream);
+/* out[i, c] = x[i, c] - logsumexp(x[i, :]) in fp32, x (N, C) row stride ldx, out row stride ldo, one launch: logits as
+ * log-probabilities for ranking (per column monotone in the softmax, across rows).  Evaluated as (x - m) - log1p(t) with m
+ * the row maximum and t the sum of exp(x_c - m) over every column but the first maximal one (expf / log1pf of the device
+ * library): no rounding at the logits' magnitude.  A row's bits depend on the row and C only.  out must not overlap x. */
+int msn_log_softmax_rows(const float* x, int64_t ldx, int64_t N, int C, float* out, int64_t ldo, msn_stream_t stream);
+
 /* feat[r] = (x[r]*m, t[r]*inv_norm*m, m, 0), m = mask[r]: the 4 input channels of the build-defined 1-D CNN
  * encoder for light curves / spectra (value, normalised time / wavelength, validity, pad). */
 int msn_series_features(const float* x, const float* t, const uint8_t* mask, int64_t rows, float inv_norm,

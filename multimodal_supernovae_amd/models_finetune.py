@@ -209,11 +209,13 @@ class RegressionMetrics:
 class ClipMLP(nn.Module):
     """MLP head on the concatenated embeddings of a (pretrained) LightCurveImageCLIP, trained for classification
     (cross-entropy against batch[8]) or redshift regression (MSE against batch[7]); Lightning hooks as plain methods,
-    driven by trainer.Trainer / GraphedTrainStep.  state_dict: clip_model.*, mlp.layers.{0,3,6,...}.*, class_weights."""
+    driven by trainer.Trainer / GraphedTrainStep.  state_dict: clip_model.*, mlp.layers.{0,3,6,...}.*, class_weights.
+    ranking_metrics=True (classification only) also feeds the validation logits to a metrics.RankingMetrics and logs
+    auroc_val, ap_val (macro one-vs-rest AUROC / average precision) and top2_acc_val beside f1_val, f1_micro_val and acc_val; without it the logged keys are those three and val_loss."""
 
     def __init__(self, clip_model, learning_rate=1e-3, regression=False, classification=False, n_classes=5, hidden_dim=128,
                  num_layers=2, dropout=0.0, freeze_backbone=False, class_weights=None, optimizer_kwargs=None,
-                 optimizer="radam"):
+                 optimizer="radam", ranking_metrics=False):
         super().__init__()
         if bool(regression) == bool(classification):
             raise ValueError("ClipMLP needs exactly one of regression=True / classification=True")
@@ -246,6 +248,10 @@ class ClipMLP(nn.Module):
             self.clip_model.eval()
         self.group = None
         self.metrics = ClassificationMetrics(self.n_classes) if classification else RegressionMetrics()
+        self.ranking = None                   # opt-in: threshold-free metrics of the logits (metrics.RankingMetrics)
+        if ranking_metrics and classification:
+            from .metrics import RankingMetrics
+            self.ranking = RankingMetrics(self.n_classes, normalize="log_softmax", top_k=(1, 2))
         self._val_batches = 0
         self._ones = {}
         self.logged = {}
@@ -302,16 +308,20 @@ class ClipMLP(nn.Module):
                                     kind="loss_denominator_all_reduce")
         return _AllReduceSum.apply(loss * (n_local / n_global), self.group)
 
-    def _loss(self, batch, sharded):
-        """-> (loss, prediction, target): class per row (int32) / redshift per row."""
+    def _loss_out(self, batch, sharded):
+        """-> (loss, prediction, target, head output): class per row (int32) / redshift per row; logits / (B, 1) predictions."""
         out = self(*batch)
         if self.classification:
             target = batch[8].to(torch.int64).reshape(-1)
             loss, pred = _cross_entropy(out, target, self.class_weights, self.group, sharded)
-            return loss, pred, target
+            return loss, pred, target, out
         target = batch[7].to(torch.float32).reshape(-1)
         pred = out.squeeze(1)
-        return self._mse(pred, target, sharded), pred, target
+        return self._mse(pred, target, sharded), pred, target, out
+
+    def _loss(self, batch, sharded):
+        """-> (loss, prediction, target)."""
+        return self._loss_out(batch, sharded)[:3]
 
     def training_step(self, batch, batch_idx):
         loss, _, _ = self._loss(batch, D.world_size(self.group) > 1)
@@ -320,12 +330,16 @@ class ClipMLP(nn.Module):
 
     def on_validation_start(self):
         self.metrics.reset()
+        if self.ranking is not None:
+            self.ranking.reset()
         self._val_batches = 0
 
     def validation_step(self, batch, batch_idx):
         """Per shard, as the Trainer validates: no collective inside the loop, no host synchronisation."""
-        loss, pred, target = self._loss(batch, False)
+        loss, pred, target, out = self._loss_out(batch, False)
         self.metrics.update(pred.detach(), target)
+        if self.ranking is not None:
+            self.ranking.update(out.detach(), target)
         self._val_batches += 1
         self.log("val_loss", loss, on_epoch=True, on_step=False, prog_bar=True, logger=True)
         return loss
@@ -342,12 +356,19 @@ class ClipMLP(nn.Module):
                 if self.regression and self.metrics.sums is None:
                     self.metrics.sums = torch.zeros(6, dtype=torch.float64, device=dev)
             self.metrics.all_reduce(self.group)
+            if self.ranking is not None:
+                self.ranking.all_reduce(self.group, device=next(self.mlp.parameters()).device)
         res = self.metrics.compute()
         kw = dict(on_epoch=True, on_step=False, prog_bar=True, logger=True)
         if self.classification:
             self.log("f1_val", res["f1_macro"], **kw)
             self.log("f1_micro_val", res["f1_micro"], **kw)
             self.log("acc_val", res["acc"], **kw)
+            if self.ranking is not None:
+                rk = self.ranking.compute()
+                self.log("auroc_val", rk["auroc_macro"], **kw)
+                self.log("ap_val", rk["ap_macro"], **kw)
+                self.log("top2_acc_val", rk["top2_acc"], **kw)
         else:
             for k in ("L1", "L2", "R2", "OLF"):
                 self.log(f"{k}_val", res[k], **kw)

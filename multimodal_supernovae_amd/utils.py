@@ -55,15 +55,33 @@ def get_linear_predictions(X, Y, X_val=None, Y_val=None, task="regression", **pr
     return probe.predict(X if X_val is None else X_val)
 
 
-def linear_probe_metrics(X, Y, X_val, Y_val, task="regression", n_classes=None, **probe_kwargs):
+def _ranking_keys(scores, Y_val):
+    """auroc_macro, ap_macro and their per-class lists of (N, C) scores on the device (metrics.rank_counts: exact)."""
+    from . import metrics as M
+    _, istats, ap_sum = M.rank_counts(scores, Y_val.to(torch.int64))
+    istats, ap_sum = istats.cpu(), ap_sum.cpu()
+    return {"auroc_macro": M.auroc_from_stats(istats, "macro"), "ap_macro": M.average_precision_from_stats(istats, ap_sum, "macro"),
+            "auroc_per_class": [float(v) for v in M.auroc_from_stats(istats, None)],
+            "ap_per_class": [float(v) for v in M.average_precision_from_stats(istats, ap_sum, None)]}
+
+
+def linear_probe_metrics(X, Y, X_val, Y_val, task="regression", n_classes=None, ranking=False, **probe_kwargs):
     """The metrics of a linear probe fitted on (X, Y) and evaluated on (X_val, Y_val), with the keys of the reference's
     pickles: L1, L2, R2, OLF for task="regression" (RegressionMetrics), acc and the F1 scores for task="classification"
-    (ClassificationMetrics over n_classes, by default the largest class of Y and Y_val plus one)."""
+    (ClassificationMetrics over n_classes, by default the largest class of Y and Y_val plus one).  ranking=True adds, for
+    classification, auroc_macro, ap_macro, auroc_per_class and ap_per_class of the probe's decision_function."""
     from .models_finetune import ClassificationMetrics, RegressionMetrics
     if task == "classification":
         if n_classes is None:
             n_classes = int(max(Y.max().item(), Y_val.max().item())) + 1
         probe_kwargs = dict(probe_kwargs, n_classes=n_classes)
+    if ranking and task == "classification":
+        from .models_finetune import argmax_rows
+        from .probes import LogisticRegressionProbe
+        scores = LogisticRegressionProbe(**probe_kwargs).fit(X, Y).decision_function(X_val)
+        metrics = ClassificationMetrics(n_classes)
+        metrics.update(argmax_rows(scores), Y_val)
+        return dict(metrics.compute(), **_ranking_keys(scores, Y_val))
     pred = get_linear_predictions(X, Y, X_val, Y_val, task=task, **probe_kwargs)
     metrics = RegressionMetrics() if task == "regression" else ClassificationMetrics(n_classes)
     metrics.update(pred, Y_val)
@@ -86,15 +104,22 @@ def get_knn_predictions(X, Y, X_val=None, Y_val=None, k=5, task="regression", **
     return probe.predict(X_val)
 
 
-def knn_probe_metrics(X, Y, X_val, Y_val, k=5, task="regression", n_classes=None, **probe_kwargs):
+def knn_probe_metrics(X, Y, X_val, Y_val, k=5, task="regression", n_classes=None, ranking=False, **probe_kwargs):
     """The metrics of a kNN probe fitted on (X, Y) and evaluated on (X_val, Y_val), with the keys of linear_probe_metrics:
     L1, L2, R2, OLF for task="regression", acc and the F1 scores for task="classification" (over n_classes, by default the
-    largest class of Y and Y_val plus one)."""
+    largest class of Y and Y_val plus one).  ranking=True adds, for classification, auroc_macro, ap_macro, auroc_per_class and
+    ap_per_class of the probe's predict_proba (vote shares: coarse scores with many ties, which the metrics count at one half)."""
     from .models_finetune import ClassificationMetrics, RegressionMetrics
     if task == "classification":
         if n_classes is None:
             n_classes = int(max(Y.max().item(), Y_val.max().item())) + 1
         probe_kwargs = dict(probe_kwargs, n_classes=n_classes)
+    if ranking and task == "classification":
+        from .probes import KNeighborsClassifierProbe
+        probe = KNeighborsClassifierProbe(n_neighbors=k, **probe_kwargs).fit(X, Y)
+        metrics = ClassificationMetrics(n_classes)
+        metrics.update(probe.predict(X_val), Y_val)
+        return dict(metrics.compute(), **_ranking_keys(probe.predict_proba(X_val), Y_val))
     pred = get_knn_predictions(X, Y, X_val, Y_val, k=k, task=task, **probe_kwargs)
     metrics = RegressionMetrics() if task == "regression" else ClassificationMetrics(n_classes)
     metrics.update(pred, Y_val)
