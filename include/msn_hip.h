@@ -1006,6 +1006,53 @@ int msn_topk_ranks(const float* S, int64_t ld, const int64_t* y, int64_t N, int 
  * library): no rounding at the logits' magnitude.  A row's bits depend on the row and C only.  out must not overlap x. */
 int msn_log_softmax_rows(const float* x, int64_t ldx, int64_t N, int C, float* out, int64_t ldo, msn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Calibration of classifier probabilities (calibration.py; csrc/calibration.hip): expected calibration error, reliability
+ * diagram and Brier score from integer counts, and the objective of temperature scaling (Guo et al. 2017).  Shared by the
+ * entry points, as above: S / P (N, C) fp32 with row stride ld >= C, 4-byte aligned (every load is a 4-byte load: the bits do
+ * not depend on stride or alignment); y int64 (N); a row whose target lies outside [0, C) is ignored everywhere.
+ * 1 <= N < 2^31, 1 <= C <= 1024, 1 <= B <= 1024, beta finite and > 0, else MSN_ERR_SHAPE before any launch.  No float atomics,
+ * no fills, no flags; everything repeats bit for bit.
+ *
+ * out[i, :] = softmax(beta x[i, :]), the sibling of msn_log_softmax_rows (beta = 1 / T applies a fitted temperature in the same
+ * launch): evaluated in fp64 -- t = beta (double)x, m the row maximum, e = exp(t - m), the sum of e in column order, e / sum --
+ * and rounded to fp32 once.  A row's bits depend on the row, C and beta only.  A row that holds a NaN or +inf comes out all
+ * NaN.  out must not overlap x. */
+int msn_softmax_rows(const float* x, int64_t ldx, int64_t N, int C, double beta, float* out, int64_t ldo, msn_stream_t stream);
+/* Binned calibration statistics of probabilities P, all integers.  acc int64 (slots, B, 3), slots = 1 (classwise = 0) or 1 + C,
+ * and tot int64 (3): caller-owned DEVICE accumulators over calls (as msn_threshold_counts has them).
+ * A row with a target in range is VALID when every P[i, c] lies in [0, 1] (a NaN does not; -0.0 does) and the fp64 sum of the
+ * row, added in column order, lies within 2^-10 of 1; otherwise it is a BAD row and counts nowhere except tot[1].
+ * Fixed point: q(p) = rint((double)p 2^32), ties to even -- the product is exact, so q is an integer in [0, 2^32] that depends
+ * on the fp32 bits of p only -- and the bin of p is min(B - 1, (q(p) B) >> 32): integer arithmetic, edges k / B, p = 1 in the
+ * last bin.  Slot 0 is the top label: conf = P[i, a], a the first maximal column (the arg-max rule of msn_cross_entropy_fwd),
+ * hit = (a == y_i); slot 1 + c (classwise): conf = P[i, c], hit = (y_i == c).  Per valid row and slot, b the bin of conf:
+ *   acc[s, b, 0] += 1      acc[s, b, 1] += hit      acc[s, b, 2] += q(conf)
+ *   tot[0] += #valid       tot[1] += #bad           tot[2] += rint(brier_i 2^30),  brier_i = sum_c (P[i, c] - [y_i == c])^2
+ * with brier_i formed in fp64 in column order, product and add rounded apart (d = (double)p - t; s = s + d d, no contraction).
+ * The sum rule bounds brier_i by about 2.002 (< 2^32 in units of 2^-30), q <= 2^32 and N < 2^31: every accumulated sum stays
+ * below 2^63.  Being integers, the outputs do not depend on the order of the adds or on how an epoch is cut into batches or
+ * ranks, and a SUM all-reduce is exact; the quantisation moves ECE by at most 2^-33.  One launch: per-workgroup histogram in
+ * LDS (count, hits, 64-bit sum of q) over a group of slots, one 64-bit integer add per non-zero cell; classwise = 0 reads and
+ * bins for slot 0 only. */
+int msn_calibration_counts(const float* P, int64_t ld, const int64_t* y, int64_t N, int C, int B, int classwise, int64_t* acc,
+                           int64_t* tot, msn_stream_t stream);
+/* The objective of temperature scaling and its first two derivatives in beta = 1 / T, fp64:
+ *   out = double[5] = {n_valid, sum nll_i, sum g_i, sum h_i, n_bad}  (DEVICE; overwritten, not accumulated)
+ * over the rows with a target in range; one that holds a NaN or an infinite logit is BAD: it goes to n_bad and nowhere else.
+ * Per valid row, with d_c = (double)x_c - max_c x_c and u = beta d:  p = softmax(u),
+ *   nll_i = log(sum_c exp(u_c)) - u_y      g_i = sum_c p_c (x_c - x_y) (= E_p[x] - x_y; exact differences and products, a pair sum)
+ *   h_i = sum_c p_c (d_c - mu)^2, mu = g_i + d_y (= Var_p[x], the two-pass form: never negative).
+ * The sums over rows run in an order that is a function of N alone -- row i belongs to thread i % 256 of workgroup
+ * (i / 256) % min(ceil(N / 256), 512), a thread adds its rows in ascending order, a workgroup combines its threads by the xor
+ * tree and then wave by wave, per-workgroup partials in `ws` (msn_temperature_nll_workspace_bytes = 64 bytes per workgroup),
+ * and a finishing launch adds them the same way -- and each is carried as a pair (sum, error of the sum: two-sum) that is
+ * rounded once at the end, so the three sums are the correctly rounded sums of the rows' terms up to 2^-100.  The bits depend
+ * on the rows, N, C and beta only. */
+size_t msn_temperature_nll_workspace_bytes(int64_t N);
+int msn_temperature_nll(const float* S, int64_t ld, const int64_t* y, int64_t N, int C, double beta, double* out, void* ws,
+                        size_t ws_bytes, msn_stream_t stream);
+
 /* feat[r] = (x[r]*m, t[r]*inv_norm*m, m, 0), m = mask[r]: the 4 input channels of the build-defined 1-D CNN
  * encoder for light curves / spectra (value, normalised time / wavelength, validity, pad). */
 int msn_series_features(const float* x, const float* t, const uint8_t* mask, int64_t rows, float inv_norm,

@@ -152,6 +152,10 @@ SIGNATURES = {
     "msn_threshold_counts": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),
     "msn_topk_ranks": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr]),
     "msn_log_softmax_rows": (c_int, [c_ptr, c_i64, c_i64, c_int, c_ptr, c_i64, c_ptr]),
+    "msn_softmax_rows": (c_int, [c_ptr, c_i64, c_i64, c_int, c_f64, c_ptr, c_i64, c_ptr]),
+    "msn_calibration_counts": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
+    "msn_temperature_nll_workspace_bytes": (c_size, [c_i64]),
+    "msn_temperature_nll": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_f64, c_ptr, c_ptr, c_size, c_ptr]),
     "msn_series_features": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_f32, c_ptr, c_ptr]),
     "msn_relu_mask": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
     "msn_im2col": (c_int, [c_ptr] + [c_int] * 10 + [c_ptr, c_ptr]),

@@ -211,11 +211,13 @@ class ClipMLP(nn.Module):
     (cross-entropy against batch[8]) or redshift regression (MSE against batch[7]); Lightning hooks as plain methods,
     driven by trainer.Trainer / GraphedTrainStep.  state_dict: clip_model.*, mlp.layers.{0,3,6,...}.*, class_weights.
     ranking_metrics=True (classification only) also feeds the validation logits to a metrics.RankingMetrics and logs
-    auroc_val, ap_val (macro one-vs-rest AUROC / average precision) and top2_acc_val beside f1_val, f1_micro_val and acc_val; without it the logged keys are those three and val_loss."""
+    auroc_val, ap_val (macro one-vs-rest AUROC / average precision) and top2_acc_val beside f1_val, f1_micro_val and acc_val; without it the logged keys are those three and val_loss.
+    calibration_metrics=True (classification only) also feeds them to a calibration.CalibrationMetrics (softmax of the logits,
+    15 bins) and logs ece_val and brier_val (top-label expected calibration error, multi-class Brier score)."""
 
     def __init__(self, clip_model, learning_rate=1e-3, regression=False, classification=False, n_classes=5, hidden_dim=128,
                  num_layers=2, dropout=0.0, freeze_backbone=False, class_weights=None, optimizer_kwargs=None,
-                 optimizer="radam", ranking_metrics=False):
+                 optimizer="radam", ranking_metrics=False, calibration_metrics=False):
         super().__init__()
         if bool(regression) == bool(classification):
             raise ValueError("ClipMLP needs exactly one of regression=True / classification=True")
@@ -252,6 +254,10 @@ class ClipMLP(nn.Module):
         if ranking_metrics and classification:
             from .metrics import RankingMetrics
             self.ranking = RankingMetrics(self.n_classes, normalize="log_softmax", top_k=(1, 2))
+        self.calibration = None               # opt-in: calibration of softmax(logits) (calibration.CalibrationMetrics)
+        if calibration_metrics and classification:
+            from .calibration import CalibrationMetrics
+            self.calibration = CalibrationMetrics(self.n_classes, normalize="softmax")
         self._val_batches = 0
         self._ones = {}
         self.logged = {}
@@ -332,6 +338,8 @@ class ClipMLP(nn.Module):
         self.metrics.reset()
         if self.ranking is not None:
             self.ranking.reset()
+        if self.calibration is not None:
+            self.calibration.reset()
         self._val_batches = 0
 
     def validation_step(self, batch, batch_idx):
@@ -340,6 +348,8 @@ class ClipMLP(nn.Module):
         self.metrics.update(pred.detach(), target)
         if self.ranking is not None:
             self.ranking.update(out.detach(), target)
+        if self.calibration is not None:
+            self.calibration.update(out.detach(), target)
         self._val_batches += 1
         self.log("val_loss", loss, on_epoch=True, on_step=False, prog_bar=True, logger=True)
         return loss
@@ -358,6 +368,8 @@ class ClipMLP(nn.Module):
             self.metrics.all_reduce(self.group)
             if self.ranking is not None:
                 self.ranking.all_reduce(self.group, device=next(self.mlp.parameters()).device)
+            if self.calibration is not None:
+                self.calibration.all_reduce(self.group, device=next(self.mlp.parameters()).device)
         res = self.metrics.compute()
         kw = dict(on_epoch=True, on_step=False, prog_bar=True, logger=True)
         if self.classification:
@@ -369,6 +381,10 @@ class ClipMLP(nn.Module):
                 self.log("auroc_val", rk["auroc_macro"], **kw)
                 self.log("ap_val", rk["ap_macro"], **kw)
                 self.log("top2_acc_val", rk["top2_acc"], **kw)
+            if self.calibration is not None:
+                cal = self.calibration.compute()
+                self.log("ece_val", cal["ece"], **kw)
+                self.log("brier_val", cal["brier"], **kw)
         else:
             for k in ("L1", "L2", "R2", "OLF"):
                 self.log(f"{k}_val", res[k], **kw)

@@ -65,23 +65,45 @@ def _ranking_keys(scores, Y_val):
             "ap_per_class": [float(v) for v in M.average_precision_from_stats(istats, ap_sum, None)]}
 
 
-def linear_probe_metrics(X, Y, X_val, Y_val, task="regression", n_classes=None, ranking=False, **probe_kwargs):
+def _calibration_keys(probs, Y_val):
+    """ece, mce and brier of (N, C) probabilities on the device (calibration.calibration_counts: 15 bins, integer counts)."""
+    from . import calibration as K
+    acc, tot = K.calibration_counts(probs, Y_val.to(torch.int64))
+    acc, tot = acc.cpu(), tot.cpu()
+    return {"ece": K.ece_from_counts(acc, "l1"), "mce": K.ece_from_counts(acc, "max"), "brier": K.brier_from_counts(tot)}
+
+
+def _no_calibration_of_regression(calibration, task, who):
+    if calibration and task != "classification":
+        raise ValueError(f"{who}: calibration=True belongs to task='classification' (got {task!r})")
+
+
+def linear_probe_metrics(X, Y, X_val, Y_val, task="regression", n_classes=None, ranking=False, calibration=False,
+                         **probe_kwargs):
     """The metrics of a linear probe fitted on (X, Y) and evaluated on (X_val, Y_val), with the keys of the reference's
     pickles: L1, L2, R2, OLF for task="regression" (RegressionMetrics), acc and the F1 scores for task="classification"
     (ClassificationMetrics over n_classes, by default the largest class of Y and Y_val plus one).  ranking=True adds, for
-    classification, auroc_macro, ap_macro, auroc_per_class and ap_per_class of the probe's decision_function."""
+    classification, auroc_macro, ap_macro, auroc_per_class and ap_per_class of the probe's decision_function.
+    calibration=True adds, for classification, ece, mce and brier of the softmax of the decision_function (regression refuses it)."""
     from .models_finetune import ClassificationMetrics, RegressionMetrics
+    _no_calibration_of_regression(calibration, task, "linear_probe_metrics")
     if task == "classification":
         if n_classes is None:
             n_classes = int(max(Y.max().item(), Y_val.max().item())) + 1
         probe_kwargs = dict(probe_kwargs, n_classes=n_classes)
-    if ranking and task == "classification":
+    if (ranking or calibration) and task == "classification":
         from .models_finetune import argmax_rows
         from .probes import LogisticRegressionProbe
         scores = LogisticRegressionProbe(**probe_kwargs).fit(X, Y).decision_function(X_val)
         metrics = ClassificationMetrics(n_classes)
         metrics.update(argmax_rows(scores), Y_val)
-        return dict(metrics.compute(), **_ranking_keys(scores, Y_val))
+        res = metrics.compute()
+        if ranking:
+            res.update(_ranking_keys(scores, Y_val))
+        if calibration:
+            from .calibration import softmax_rows
+            res.update(_calibration_keys(softmax_rows(scores), Y_val))
+        return res
     pred = get_linear_predictions(X, Y, X_val, Y_val, task=task, **probe_kwargs)
     metrics = RegressionMetrics() if task == "regression" else ClassificationMetrics(n_classes)
     metrics.update(pred, Y_val)
@@ -104,22 +126,31 @@ def get_knn_predictions(X, Y, X_val=None, Y_val=None, k=5, task="regression", **
     return probe.predict(X_val)
 
 
-def knn_probe_metrics(X, Y, X_val, Y_val, k=5, task="regression", n_classes=None, ranking=False, **probe_kwargs):
+def knn_probe_metrics(X, Y, X_val, Y_val, k=5, task="regression", n_classes=None, ranking=False, calibration=False,
+                      **probe_kwargs):
     """The metrics of a kNN probe fitted on (X, Y) and evaluated on (X_val, Y_val), with the keys of linear_probe_metrics:
     L1, L2, R2, OLF for task="regression", acc and the F1 scores for task="classification" (over n_classes, by default the
     largest class of Y and Y_val plus one).  ranking=True adds, for classification, auroc_macro, ap_macro, auroc_per_class and
-    ap_per_class of the probe's predict_proba (vote shares: coarse scores with many ties, which the metrics count at one half)."""
+    ap_per_class of the probe's predict_proba (vote shares: coarse scores with many ties, which the metrics count at one half).
+    calibration=True adds, for classification, ece, mce and brier of predict_proba (regression refuses it); a row that no
+    labelled neighbour votes for sums to 0 and is a bad row of calibration.py: it is in none of the three."""
     from .models_finetune import ClassificationMetrics, RegressionMetrics
+    _no_calibration_of_regression(calibration, task, "knn_probe_metrics")
     if task == "classification":
         if n_classes is None:
             n_classes = int(max(Y.max().item(), Y_val.max().item())) + 1
         probe_kwargs = dict(probe_kwargs, n_classes=n_classes)
-    if ranking and task == "classification":
+    if (ranking or calibration) and task == "classification":
         from .probes import KNeighborsClassifierProbe
         probe = KNeighborsClassifierProbe(n_neighbors=k, **probe_kwargs).fit(X, Y)
         metrics = ClassificationMetrics(n_classes)
         metrics.update(probe.predict(X_val), Y_val)
-        return dict(metrics.compute(), **_ranking_keys(probe.predict_proba(X_val), Y_val))
+        res, proba = metrics.compute(), probe.predict_proba(X_val)
+        if ranking:
+            res.update(_ranking_keys(proba, Y_val))
+        if calibration:
+            res.update(_calibration_keys(proba, Y_val))
+        return res
     pred = get_knn_predictions(X, Y, X_val, Y_val, k=k, task=task, **probe_kwargs)
     metrics = RegressionMetrics() if task == "regression" else ClassificationMetrics(n_classes)
     metrics.update(pred, Y_val)
