@@ -29,7 +29,9 @@ import torch
 from . import _lib
 from . import distributed as D
 from ._lib import check, lib, ptr, stream_ptr
-from .metrics import IGNORE, MAX_CLASSES, _accumulator, _checked, _ld, _np, _ref_inputs, _scores_on_gpu  # noqa: F401 -- IGNORE is part of the interface
+from ._device_args import (EpochCounts, accumulator, ld, reference_inputs, rows_on_gpu, scores_and_targets, to_numpy,
+                           workspace)
+from .metrics import IGNORE, MAX_CLASSES  # noqa: F401 -- part of the interface
 
 MAX_BINS = 1024
 Q_ONE = 1 << 32                # the fixed-point unit of a confidence
@@ -68,7 +70,7 @@ def calibration_counts_reference(P, y, n_bins=15, classwise=False, n_classes=Non
     """numpy restatement of msn_calibration_counts for one call from zero: (acc int64 (slots, B, 3), tot int64 (3)) with
     acc[s, b] = {rows, hits, sum of q(conf)} of slot s (0: the top label at its first maximal column; 1 + c: class c) in bin b
     over the valid rows, tot = {#valid, #bad, sum of rint(brier_i 2^30)}."""
-    P, y, C, in_range = _ref_inputs(P, y, n_classes, "calibration_counts_reference")
+    P, y, C, in_range = reference_inputs(P, y, n_classes, "calibration_counts_reference")
     B = int(n_bins)
     if not 1 <= B <= MAX_BINS:
         raise ValueError(f"calibration_counts_reference: 1 to {MAX_BINS} bins (got {n_bins})")
@@ -113,7 +115,7 @@ def temperature_nll_reference(S, y, temperature=1.0, beta=None, n_classes=None, 
     terms are formed in `dtype` -- d = x - max x, u = beta d, nll = log(sum exp u) - u_y, mu = sum(e d) / sum e, g = mu - d_y,
     h = sum(e (d - mu)^2) / sum e -- and added by math.fsum (fp64: the correctly rounded sum) or in `dtype` (longdouble: the
     reference of the accuracy tests)."""
-    S, y, C, in_range = _ref_inputs(S, y, n_classes, "temperature_nll_reference")
+    S, y, C, in_range = reference_inputs(S, y, n_classes, "temperature_nll_reference")
     b = dtype(_beta(temperature, beta, "temperature_nll_reference"))
     finite = np.isfinite(S).all(axis=1)
     rows = np.nonzero(in_range & finite)[0]
@@ -181,7 +183,7 @@ def fit_temperature_reference(logits, target, max_iter=50, tol=1e-8, bounds=(1e-
 
 # ---------------------------------------------------------------------------------------------- host: the metrics
 def _slots(acc, who):
-    a = _np(acc, np.int64)
+    a = to_numpy(acc, np.int64)
     if a.ndim == 2:
         a = a[None]
     if a.ndim != 3 or a.shape[2] != 3:
@@ -228,7 +230,7 @@ def classwise_ece_from_counts(acc, average="macro"):
 def brier_from_counts(tot):
     """Multi-class Brier score mean_i sum_c (p_ic - [y_i = c])^2 from tot = {n, n_bad, sum of rint(brier_i 2^30)}; nan without
     rows.  (Twice scikit-learn's brier_score_loss for two classes.)"""
-    n, _, s = (int(v) for v in _np(tot, np.int64).reshape(3))
+    n, _, s = (int(v) for v in to_numpy(tot, np.int64).reshape(3))
     return s / (n * BRIER_ONE) if n else float("nan")
 
 
@@ -246,10 +248,10 @@ def softmax_rows(logits, temperature=1.0, beta=None):
     """softmax(logits / temperature) over the rows of float32 (N, C) logits in one launch (msn_softmax_rows: evaluated in fp64,
     rounded to fp32 once), a new dense tensor.  Enqueue only."""
     b = _beta(temperature, beta, "softmax_rows")
-    S = _scores_on_gpu(logits, "softmax_rows")
+    S = rows_on_gpu(logits, "softmax_rows", "scores", MAX_CLASSES)
     N, C = S.shape
     out = torch.empty((N, C), dtype=torch.float32, device=S.device)
-    check(lib().msn_softmax_rows(ptr(S), _ld(S), N, C, b, ptr(out), C, stream_ptr()), "msn_softmax_rows")
+    check(lib().msn_softmax_rows(ptr(S), ld(S), N, C, b, ptr(out), C, stream_ptr()), "msn_softmax_rows")
     return out
 
 
@@ -257,14 +259,14 @@ def calibration_counts(probs, target, n_bins=15, classwise=False, acc=None, tot=
     """(acc int64 (slots, n_bins, 3), tot int64 (3)) of msn_calibration_counts for float32 (N, C) probabilities on the device,
     slots = 1 + C with classwise; acc / tot given are added to (the accumulators of a validation epoch), else they start from
     zero.  Enqueue only."""
-    P, y = _checked(probs, target, "calibration_counts")
+    P, y = scores_and_targets(probs, target, "calibration_counts")
     N, C = P.shape
     B = int(n_bins)
     if not 1 <= B <= MAX_BINS:
         raise _lib.MsnHipError(f"calibration_counts: 1 to {MAX_BINS} bins (got {n_bins})")
-    acc = _accumulator(acc, (1 + C if classwise else 1, B, 3), P.device, "calibration_counts")
-    tot = _accumulator(tot, (3,), P.device, "calibration_counts")
-    check(lib().msn_calibration_counts(ptr(P), _ld(P), ptr(y), N, C, B, int(bool(classwise)), ptr(acc), ptr(tot), stream_ptr()),
+    acc = accumulator(acc, (1 + C if classwise else 1, B, 3), P.device, "calibration_counts")
+    tot = accumulator(tot, (3,), P.device, "calibration_counts")
+    check(lib().msn_calibration_counts(ptr(P), ld(P), ptr(y), N, C, B, int(bool(classwise)), ptr(acc), ptr(tot), stream_ptr()),
           "msn_calibration_counts")
     return acc, tot
 
@@ -273,23 +275,25 @@ def temperature_nll(logits, target, temperature=1.0, beta=None):
     """{n_valid, sum nll, sum d nll / d beta, sum d2 nll / d beta2, n_bad} of msn_temperature_nll at beta = 1 / temperature: five
     doubles on the device.  Enqueue only."""
     b = _beta(temperature, beta, "temperature_nll")
-    S, y = _checked(logits, target, "temperature_nll")
+    S, y = scores_and_targets(logits, target, "temperature_nll")
     N, C = S.shape
     out = torch.empty(5, dtype=torch.float64, device=S.device)
     L = lib()
-    ws = torch.empty(L.msn_temperature_nll_workspace_bytes(N) // 8, dtype=torch.float64, device=S.device)
-    check(L.msn_temperature_nll(ptr(S), _ld(S), ptr(y), N, C, b, ptr(out), ptr(ws), ws.numel() * 8, stream_ptr()),
+    ws = workspace(L.msn_temperature_nll_workspace_bytes(N), S.device)
+    check(L.msn_temperature_nll(ptr(S), ld(S), ptr(y), N, C, b, ptr(out), ptr(ws), ws.numel(), stream_ptr()),
           "msn_temperature_nll")
     return out
 
 
-class CalibrationMetrics:
+class CalibrationMetrics(EpochCounts):
     """ECE, MCE, Brier score and the reliability diagram over the batches of a validation epoch, in the shape of
     metrics.RankingMetrics in its binned mode: reset, update(scores, target), all_reduce(group), compute().
 
     update is one msn_calibration_counts launch into int64 accumulators (after one msn_softmax_rows launch with
     normalize="softmax", which turns logits into softmax(logits / temperature)); all_reduce their SUM, which is exact; compute
     the one host copy.  classwise=True also bins every class's own probability (classwise ECE)."""
+
+    _counts = ("acc", "tot")
 
     def __init__(self, n_classes, n_bins=15, classwise=False, normalize=None, temperature=1.0):
         self.n_classes, self.n_bins = int(n_classes), int(n_bins)
@@ -306,11 +310,6 @@ class CalibrationMetrics:
         self.classwise, self.normalize = bool(classwise), normalize
         self.acc = self.tot = None
 
-    def reset(self):
-        for t in (self.acc, self.tot):
-            if t is not None:
-                t.zero_()
-
     def _buffers(self, device):
         if self.acc is None or self.acc.device != device:
             slots = 1 + self.n_classes if self.classwise else 1
@@ -324,23 +323,13 @@ class CalibrationMetrics:
             return
         if isinstance(target, torch.Tensor):
             target = target.to(torch.int64)
-        S, y = _checked(scores, target, "CalibrationMetrics.update")
+        S, y = scores_and_targets(scores, target, "CalibrationMetrics.update")
         if S.shape[1] != self.n_classes:
             raise ValueError(f"CalibrationMetrics.update: {S.shape[1]} score columns for {self.n_classes} classes")
         if self.normalize == "softmax":
             S = softmax_rows(S, self.temperature)
         self._buffers(S.device)
         calibration_counts(S, y, self.n_bins, self.classwise, acc=self.acc, tot=self.tot)
-
-    def all_reduce(self, group=None, device=None):
-        """Every rank enters, also one whose shard was empty (pass its device then): the SUM of the integer accumulators."""
-        if D.world_size(group) == 1:
-            return
-        device = self.acc.device if self.acc is not None else torch.device(device if device is not None
-                                                                           else f"cuda:{torch.cuda.current_device()}")
-        self._buffers(device)
-        D.all_reduce_sum(self.acc, group, kind="metric_all_reduce")
-        D.all_reduce_sum(self.tot, group, kind="metric_all_reduce")
 
     def compute(self):
         """The one host copy: {ece, mce, brier, n, n_bad, bin_confidence, bin_accuracy, bin_count} and, classwise,
@@ -381,7 +370,7 @@ class TemperatureScaling:
     def fit(self, logits, target, group=None):
         if isinstance(target, torch.Tensor):
             target = target.to(torch.int64)
-        S, y = _checked(logits, target, "TemperatureScaling.fit")
+        S, y = scores_and_targets(logits, target, "TemperatureScaling.fit")
         world = D.world_size(group)
 
         def evaluate(beta):

@@ -22,8 +22,6 @@ namespace msn {
 
 constexpr int kCalThreads = 256;
 constexpr int kCalWaveRows = kCalThreads / kWave;   // rows in flight per workgroup in the wave form
-constexpr int kCalNarrowC = 16;                     // up to here a lane owns a row
-constexpr int kCalMaxC = 1024;
 constexpr int kCalMaxB = 1024;
 constexpr int kCalCells = 2048;                     // histogram cells of one workgroup: max(1, kCalCells / B) slots
 constexpr int kNllMaxBlocks = 512;
@@ -31,36 +29,6 @@ constexpr int kNllPartial = 8;                      // {n_valid, n_bad, nll, nll
 constexpr double kTwo32 = 4294967296.0;
 constexpr double kTwo30 = 1073741824.0;
 constexpr double kSumSlack = 0.0009765625;          // 2^-10
-
-__device__ __forceinline__ long long cal_wave_sum_i64(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ void cal_add_i64(int64_t* p, long long v) {
-    atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-// what one lane of a wave wrote to the wave's own LDS slice is read by the others: order the wave's LDS accesses (one wave runs
-// its DS instructions in order; this keeps the compiler from moving them across)
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // The build contracts products into adds (-ffp-contract=fast, which no pragma switches off): a product that must be rounded
 // on its own passes through here -- no instruction, but the compiler cannot look through it.
@@ -82,24 +50,23 @@ __device__ __forceinline__ void pair_add(double& s, double& e, double bs, double
 template <bool WAVE>
 __global__ __launch_bounds__(kCalThreads) void softmax_rows_kernel(const float* __restrict__ x, int64_t ldx, int64_t N, int C,
                                                                    double beta, float* __restrict__ out, int64_t ldo) {
-    __shared__ double ex[WAVE ? kCalWaveRows * kCalMaxC : 1];
+    __shared__ double ex[WAVE ? kCalWaveRows * kMaxClasses : 1];
     const int lane = threadIdx.x & 63;
-    const int64_t unit = WAVE ? (int64_t)blockIdx.x * kCalWaveRows + (threadIdx.x >> 6) : (int64_t)blockIdx.x * kCalThreads + threadIdx.x;
-    const int64_t step = (int64_t)gridDim.x * (WAVE ? kCalWaveRows : kCalThreads);
-    for (int64_t i = unit; i < N; i += step) {
+    const RowWalk<WAVE, kCalThreads> walk{};
+    for (int64_t i = walk.unit; i < N; i += walk.step) {
         const float* row = x + i * ldx;
         float* o = out + i * ldo;
         if constexpr (WAVE) {
-            double* e = ex + (threadIdx.x >> 6) * kCalMaxC;       // this wave's own slice
+            double* e = ex + (threadIdx.x >> 6) * kMaxClasses;       // this wave's own slice
             double m = -INFINITY;
             for (int k = lane; k < C; k += kWave) m = fmax(m, beta * (double)row[k]);
-            m = wave_max_f64(m);
+            m = wave_max(m);
             for (int k = lane; k < C; k += kWave) e[k] = exp(beta * (double)row[k] - m);
-            wave_sync();
+            wave_fence();
             double s = 0.0;
             for (int k = 0; k < C; ++k) s += e[k];                // column order; every lane the same chain
             for (int k = lane; k < C; k += kWave) o[k] = (float)(e[k] / s);
-            wave_sync();                                          // the slice is reused by the wave's next row
+            wave_fence();                                          // the slice is reused by the wave's next row
         } else {
             double m = beta * (double)row[0];
             for (int k = 1; k < C; ++k) m = fmax(m, beta * (double)row[k]);
@@ -141,7 +108,7 @@ __global__ __launch_bounds__(kCalThreads) void calibration_counts_kernel(const f
     __shared__ int h_cnt[kCalCells], h_hit[kCalCells];
     __shared__ unsigned long long h_sum[kCalCells];
     __shared__ unsigned long long t_sum[3];
-    __shared__ float rows[WAVE ? kCalWaveRows * kCalMaxC : 1];
+    __shared__ float rows[WAVE ? kCalWaveRows * kMaxClasses : 1];
     const int s0 = blockIdx.y * spw, s1 = std::min(slots, s0 + spw), cells = (s1 - s0) * B;
     for (int e = threadIdx.x; e < cells; e += kCalThreads) {
         h_cnt[e] = 0;
@@ -151,19 +118,18 @@ __global__ __launch_bounds__(kCalThreads) void calibration_counts_kernel(const f
     if (threadIdx.x < 3) t_sum[threadIdx.x] = 0ull;
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    const int64_t unit = WAVE ? (int64_t)blockIdx.x * kCalWaveRows + (threadIdx.x >> 6) : (int64_t)blockIdx.x * kCalThreads + threadIdx.x;
-    const int64_t step = (int64_t)gridDim.x * (WAVE ? kCalWaveRows : kCalThreads);
+    const RowWalk<WAVE, kCalThreads> walk{};
     long long n_valid = 0, n_bad = 0, brier_q = 0;
-    for (int64_t i = unit; i < N; i += step) {
+    for (int64_t i = walk.unit; i < N; i += walk.step) {
         const int64_t yl = y[i];
         if (yl < 0 || yl >= C) continue;                          // uniform over the wave in the wave form
         const int yi = (int)yl;
         const float* row = P + i * ld;
         if constexpr (WAVE) {
-            float* r = rows + (threadIdx.x >> 6) * kCalMaxC;
-            wave_sync();                                          // the row before has been read
+            float* r = rows + (threadIdx.x >> 6) * kMaxClasses;
+            wave_fence();                                          // the row before has been read
             for (int k = lane; k < C; k += kWave) r[k] = row[k];
-            wave_sync();
+            wave_fence();
             row = r;
         }
         int a;
@@ -186,9 +152,9 @@ __global__ __launch_bounds__(kCalThreads) void calibration_counts_kernel(const f
         }
     }
     if (blockIdx.y == 0) {
-        n_valid = cal_wave_sum_i64(n_valid);
-        n_bad = cal_wave_sum_i64(n_bad);
-        brier_q = cal_wave_sum_i64(brier_q);
+        n_valid = wave_sum(n_valid);
+        n_bad = wave_sum(n_bad);
+        brier_q = wave_sum(brier_q);
         if (lane == 0) {
             atomicAdd(&t_sum[0], (unsigned long long)n_valid);
             atomicAdd(&t_sum[1], (unsigned long long)n_bad);
@@ -200,16 +166,44 @@ __global__ __launch_bounds__(kCalThreads) void calibration_counts_kernel(const f
         const int n = h_cnt[e];
         if (!n) continue;
         int64_t* cell = acc + ((int64_t)s0 * B + e) * 3;
-        cal_add_i64(cell, n);
-        if (h_hit[e]) cal_add_i64(cell + 1, h_hit[e]);
-        if (h_sum[e]) cal_add_i64(cell + 2, (long long)h_sum[e]);
+        atomic_add_i64(cell, n);
+        if (h_hit[e]) atomic_add_i64(cell + 1, h_hit[e]);
+        if (h_sum[e]) atomic_add_i64(cell + 2, (long long)h_sum[e]);
     }
-    if (blockIdx.y == 0 && threadIdx.x < 3 && t_sum[threadIdx.x]) cal_add_i64(tot + threadIdx.x, (long long)t_sum[threadIdx.x]);
+    if (blockIdx.y == 0 && threadIdx.x < 3 && t_sum[threadIdx.x]) atomic_add_i64(tot + threadIdx.x, (long long)t_sum[threadIdx.x]);
 }
 
 // ------------------------------------------------------------------------------------------------- temperature objective
 // a function of N alone
 static inline int nll_blocks(int64_t N) { return (int)std::min<int64_t>(cdiv(N, kCalThreads), kNllMaxBlocks); }
+
+// The block's sum of acc = {two plain counts, three (sum, error) pairs}, left in thread 0: xor tree inside each wave, then the
+// waves in wave order.
+__device__ __forceinline__ void nll_block_sum(double (&acc)[kNllPartial], double (&red)[kNllPartial][kCalThreads / kWave]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        acc[0] += __shfl_xor(acc[0], o, 64);
+        acc[1] += __shfl_xor(acc[1], o, 64);
+#pragma unroll
+        for (int q = 2; q < kNllPartial; q += 2) {
+            const double bs = __shfl_xor(acc[q], o, 64), be = __shfl_xor(acc[q + 1], o, 64);
+            pair_add(acc[q], acc[q + 1], bs, be);
+        }
+    }
+    if (lane == 0)
+#pragma unroll
+        for (int q = 0; q < kNllPartial; ++q) red[q][wave] = acc[q];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kCalThreads / kWave; ++w) {
+            acc[0] += red[0][w];
+            acc[1] += red[1][w];
+#pragma unroll
+            for (int q = 2; q < kNllPartial; q += 2) pair_add(acc[q], acc[q + 1], red[q][w], red[q + 1][w]);
+        }
+    }
+}
 
 // Row i belongs to thread i % 256 of workgroup (i / 256) % gridDim.x in BOTH forms -- in the wave form wave w of the workgroup
 // evaluates the rows base + 64 w + j, j = 0 .. 63, one after the other and lane j keeps row j's terms -- so every thread adds the
@@ -256,7 +250,7 @@ __global__ __launch_bounds__(kCalThreads) void temperature_nll_kernel(const floa
                     pair_add(gs, ge, p, fma(e, w, -p));
                 }
                 if constexpr (WAVE) {
-                    z = wave_sum_f64(z);
+                    z = wave_sum(z);
 #pragma unroll
                     for (int o = 32; o > 0; o >>= 1) {
                         const double bs = __shfl_xor(gs, o, 64), be = __shfl_xor(ge, o, 64);
@@ -270,7 +264,7 @@ __global__ __launch_bounds__(kCalThreads) void temperature_nll_kernel(const floa
                     const double d = (double)row[k] - xa, e = exp(beta * d), t = d - mu;
                     zv += e * (t * t);
                 }
-                if constexpr (WAVE) zv = wave_sum_f64(zv);
+                if constexpr (WAVE) zv = wave_sum(zv);
                 nll = log(z) - beta * dy;
                 h = zv / z;
             }
@@ -283,28 +277,8 @@ __global__ __launch_bounds__(kCalThreads) void temperature_nll_kernel(const floa
             }
         }
     }
-    // the workgroup's partial: xor tree inside each wave, then the waves in wave order
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        acc[0] += __shfl_xor(acc[0], o, 64);
-        acc[1] += __shfl_xor(acc[1], o, 64);
-#pragma unroll
-        for (int q = 2; q < kNllPartial; q += 2) {
-            const double bs = __shfl_xor(acc[q], o, 64), be = __shfl_xor(acc[q + 1], o, 64);
-            pair_add(acc[q], acc[q + 1], bs, be);
-        }
-    }
-    if (lane == 0)
-#pragma unroll
-        for (int q = 0; q < kNllPartial; ++q) red[q][wave] = acc[q];
-    __syncthreads();
+    nll_block_sum(acc, red);                                      // the workgroup's partial
     if (threadIdx.x == 0) {
-        for (int w = 1; w < kCalThreads / kWave; ++w) {
-            acc[0] += red[0][w];
-            acc[1] += red[1][w];
-#pragma unroll
-            for (int q = 2; q < kNllPartial; q += 2) pair_add(acc[q], acc[q + 1], red[q][w], red[q + 1][w]);
-        }
 #pragma unroll
         for (int q = 0; q < kNllPartial; ++q) part[(int64_t)blockIdx.x * kNllPartial + q] = acc[q];
     }
@@ -314,7 +288,6 @@ __global__ __launch_bounds__(kCalThreads) void temperature_nll_kernel(const floa
 __global__ __launch_bounds__(kCalThreads) void temperature_nll_finish_kernel(const double* __restrict__ part, int blocks,
                                                                              double* __restrict__ out) {
     __shared__ double red[kNllPartial][kCalThreads / kWave];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double acc[kNllPartial] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int b = threadIdx.x; b < blocks; b += kCalThreads) {
         const double* p = part + (int64_t)b * kNllPartial;
@@ -323,27 +296,8 @@ __global__ __launch_bounds__(kCalThreads) void temperature_nll_finish_kernel(con
 #pragma unroll
         for (int q = 2; q < kNllPartial; q += 2) pair_add(acc[q], acc[q + 1], p[q], p[q + 1]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        acc[0] += __shfl_xor(acc[0], o, 64);
-        acc[1] += __shfl_xor(acc[1], o, 64);
-#pragma unroll
-        for (int q = 2; q < kNllPartial; q += 2) {
-            const double bs = __shfl_xor(acc[q], o, 64), be = __shfl_xor(acc[q + 1], o, 64);
-            pair_add(acc[q], acc[q + 1], bs, be);
-        }
-    }
-    if (lane == 0)
-#pragma unroll
-        for (int q = 0; q < kNllPartial; ++q) red[q][wave] = acc[q];
-    __syncthreads();
+    nll_block_sum(acc, red);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < kCalThreads / kWave; ++w) {
-            acc[0] += red[0][w];
-            acc[1] += red[1][w];
-#pragma unroll
-            for (int q = 2; q < kNllPartial; q += 2) pair_add(acc[q], acc[q + 1], red[q][w], red[q + 1][w]);
-        }
         out[0] = acc[0];
         out[1] = acc[2] + acc[3];                                 // the one rounding of each sum
         out[2] = acc[4] + acc[5];
@@ -356,24 +310,17 @@ __global__ __launch_bounds__(kCalThreads) void temperature_nll_finish_kernel(con
 
 using namespace msn;
 
-#define CAL_REQUIRE_SHAPE(who, N, C, ld)                                                                             \
-    do {                                                                                                             \
-        MSN_REQUIRE((N) >= 1 && (N) < ((int64_t)1 << 31), who ": N must be in 1..2^31 - 1 (got %lld)", (long long)(N)); \
-        MSN_REQUIRE((C) >= 1 && (C) <= kCalMaxC, who ": C must be in 1..1024 (got %d)", (C));                          \
-        MSN_REQUIRE((ld) >= (C), who ": row stride %lld below C = %d", (long long)(ld), (C));                           \
-    } while (0)
-
 #define CAL_REQUIRE_BETA(who, beta) \
     MSN_REQUIRE((beta) > 0.0 && (beta) < INFINITY, who ": beta must be finite and > 0 (got %g)", (beta))
 
 extern "C" int msn_softmax_rows(const float* x, int64_t ldx, int64_t N, int C, double beta, float* out, int64_t ldo,
                                 msn_stream_t stream) {
     MSN_REQUIRE(x && out, "msn_softmax_rows: null pointer");
-    CAL_REQUIRE_SHAPE("msn_softmax_rows", N, C, ldx);
+    MSN_REQUIRE_ROWS("msn_softmax_rows", N, C, ldx);
     MSN_REQUIRE(ldo >= C, "msn_softmax_rows: output row stride %lld below C = %d", (long long)ldo, C);
     CAL_REQUIRE_BETA("msn_softmax_rows", beta);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (C <= kCalNarrowC) {
+    if (C <= kNarrowC) {
         const int blocks = (int)std::min<int64_t>(cdiv(N, kCalThreads), 4096);
         hipLaunchKernelGGL(softmax_rows_kernel<false>, dim3(blocks), dim3(kCalThreads), 0, st, x, ldx, N, C, beta, out, ldo);
     } else {
@@ -387,13 +334,13 @@ extern "C" int msn_softmax_rows(const float* x, int64_t ldx, int64_t N, int C, d
 extern "C" int msn_calibration_counts(const float* P, int64_t ld, const int64_t* y, int64_t N, int C, int B, int classwise,
                                       int64_t* acc, int64_t* tot, msn_stream_t stream) {
     MSN_REQUIRE(P && y && acc && tot, "msn_calibration_counts: null pointer");
-    CAL_REQUIRE_SHAPE("msn_calibration_counts", N, C, ld);
+    MSN_REQUIRE_ROWS("msn_calibration_counts", N, C, ld);
     MSN_REQUIRE(B >= 1 && B <= kCalMaxB, "msn_calibration_counts: B must be in 1..1024 (got %d)", B);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int slots = classwise ? 1 + C : 1;
     const int spw = std::max(1, kCalCells / B);                   // slots of one workgroup
     const int groups = (int)cdiv(slots, spw);
-    if (C <= kCalNarrowC) {
+    if (C <= kNarrowC) {
         const int blocks = (int)std::min<int64_t>(cdiv(N, kCalThreads), 256);
         hipLaunchKernelGGL(calibration_counts_kernel<false>, dim3(blocks, groups), dim3(kCalThreads), 0, st, P, ld, y, N, C, B,
                            slots, spw, acc, tot);
@@ -414,14 +361,14 @@ extern "C" size_t msn_temperature_nll_workspace_bytes(int64_t N) {
 extern "C" int msn_temperature_nll(const float* S, int64_t ld, const int64_t* y, int64_t N, int C, double beta, double* out,
                                    void* ws, size_t ws_bytes, msn_stream_t stream) {
     MSN_REQUIRE(S && y && out, "msn_temperature_nll: null pointer");
-    CAL_REQUIRE_SHAPE("msn_temperature_nll", N, C, ld);
+    MSN_REQUIRE_ROWS("msn_temperature_nll", N, C, ld);
     CAL_REQUIRE_BETA("msn_temperature_nll", beta);
     const size_t need = msn_temperature_nll_workspace_bytes(N);
     MSN_REQUIRE(ws && ws_bytes >= need, "msn_temperature_nll: workspace of %zu bytes needed, %zu given", need, ws_bytes);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int blocks = nll_blocks(N);
     double* part = static_cast<double*>(ws);
-    if (C <= kCalNarrowC)
+    if (C <= kNarrowC)
         hipLaunchKernelGGL(temperature_nll_kernel<false>, dim3(blocks), dim3(kCalThreads), 0, st, S, ld, y, N, C, beta, part);
     else
         hipLaunchKernelGGL(temperature_nll_kernel<true>, dim3(blocks), dim3(kCalThreads), 0, st, S, ld, y, N, C, beta, part);

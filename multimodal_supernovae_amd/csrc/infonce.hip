@@ -155,9 +155,7 @@ __global__ __launch_bounds__(256) void nce_fwd_kernel(const NceArgs p) {
 __device__ __forceinline__ double wave_sum_strided(const double* __restrict__ v, int n, int stride, int lane) {
     double acc = 0.0;
     for (int k = lane; k < n; k += 64) acc += v[(int64_t)k * stride];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    return acc;
+    return wave_sum(acc);
 }
 
 // Merge key splits -> LSE per local row and direction; this rank's share of the loss.  One workgroup: a thread owns

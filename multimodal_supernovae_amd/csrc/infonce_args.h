@@ -46,13 +46,6 @@ struct NceArgs {
 
 __device__ __forceinline__ int row_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
-// A wave re-uses its LDS key buffer: LDS operations of one wave execute in order, this only pins the compiler.
-__device__ __forceinline__ void wave_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ float4 load4_guarded(const float* p, int c0, int D, bool vec_ok) {
     if (vec_ok && c0 + 3 < D) return *reinterpret_cast<const float4*>(p);
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);

@@ -36,7 +36,6 @@ constexpr int kKnnBlocks = 512;           // workgroups aimed at (a constant of 
 constexpr int kKnnMaxD = 1024;
 constexpr int kKnnMaxK = 64;
 constexpr int kKnnMaxTargets = 16;
-constexpr int kKnnMaxClasses = 1024;
 constexpr int kKnnStage = 2 * kKnnTile * kKnnLd;      // doubles of the two staged tiles
 static_assert(kKnnTile * kKnnDsLd <= kKnnStage, "the distance tile must fit where the staged tiles were");
 
@@ -345,11 +344,11 @@ __global__ __launch_bounds__(256) void knn_regress_kernel(const int* __restrict_
 __global__ __launch_bounds__(256) void knn_classes_kernel(const int* __restrict__ idx, const double* __restrict__ dist2, int64_t Nq,
                                                           int k, const int64_t* __restrict__ y, int C, int weights,
                                                           int* __restrict__ classes, float* __restrict__ proba) {
-    __shared__ double votes_all[4 * kKnnMaxClasses];
+    __shared__ double votes_all[4 * kMaxClasses];
     __shared__ double totals[4];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t q = (int64_t)blockIdx.x * 4 + w;
-    double* votes = votes_all + w * kKnnMaxClasses;
+    double* votes = votes_all + w * kMaxClasses;
     for (int cc = lane; cc < C; cc += 64) votes[cc] = 0.0;
     __syncthreads();
     if (lane == 0 && q < Nq) {
@@ -474,7 +473,7 @@ extern "C" int msn_knn_predict_classes(const int* idx, const double* dist2, int6
                                        int* classes, float* proba_or_null, msn_stream_t stream) {
     MSN_REQUIRE(Nq >= 1, "msn_knn_predict_classes: Nq must be at least 1 (got %lld)", (long long)Nq);
     MSN_REQUIRE(k >= 1 && k <= kKnnMaxK, "msn_knn_predict_classes: k must be in 1..%d (got %d)", kKnnMaxK, k);
-    MSN_REQUIRE(C >= 1 && C <= kKnnMaxClasses, "msn_knn_predict_classes: C must be in 1..%d (got %d)", kKnnMaxClasses, C);
+    MSN_REQUIRE(C >= 1 && C <= kMaxClasses, "msn_knn_predict_classes: C must be in 1..%d (got %d)", kMaxClasses, C);
     MSN_REQUIRE(weights == 0 || weights == 1, "msn_knn_predict_classes: weights must be 0 (uniform) or 1 (distance), got %d", weights);
     MSN_REQUIRE(idx && dist2 && y && classes, "msn_knn_predict_classes: null pointer");
     MSN_REQUIRE(((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(classes) | reinterpret_cast<uintptr_t>(proba_or_null)) &

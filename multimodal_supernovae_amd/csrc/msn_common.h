@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/msn_hip.h"
 
 namespace msn {
@@ -141,16 +143,57 @@ __device__ __forceinline__ float strided_sum_seq8(bool active, const float* p, L
     }
     return s;
 }
-__device__ __forceinline__ float wave_sum(float v) {
+// ---- wave reductions: xor-shuffle tree, offsets 32, 16, ..., 1; every lane gets the result -----
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+    static_assert(std::is_same_v<T, float> || std::is_same_v<T, double> || std::is_same_v<T, int> || std::is_same_v<T, long long>,
+                  "wave_sum: float, double, int or long long (no silent conversion of anything else)");
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
-__device__ __forceinline__ float wave_max(float v) {
+__device__ __forceinline__ float lane_max(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double lane_max(double a, double b) { return fmax(a, b); }
+__device__ __forceinline__ int lane_max(int a, int b) { return max(a, b); }
+__device__ __forceinline__ long long lane_max(long long a, long long b) { return max(a, b); }
+template <class T>                  // the four types of lane_max
+__device__ __forceinline__ T wave_max(T v) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    for (int o = 32; o > 0; o >>= 1) v = lane_max(v, __shfl_xor(v, o, 64));
     return v;
 }
+
+// A wave re-uses its own LDS slice: LDS operations of one wave execute in order, this only pins the compiler.
+__device__ __forceinline__ void wave_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Integer adds commute: the order of these atomics changes no bit.
+__device__ __forceinline__ void atomic_add_i64(int64_t* p, long long v) {
+    atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
+}
+
+// ---- rows of classifier scores (supervised.hip, rank_metrics.hip, calibration.hip, knn.hip) ----
+constexpr int kNarrowC = 16;        // up to here a lane owns a row; beyond, a wave owns a row
+constexpr int kMaxClasses = 1024;
+
+// The rows of one thread (WAVE: of its wave) in a grid of THREADS-wide workgroups: unit, unit + step, ...
+template <bool WAVE, int THREADS>
+struct RowWalk {
+    const int64_t unit = WAVE ? (int64_t)blockIdx.x * (THREADS / kWave) + (threadIdx.x >> 6) : (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    const int64_t step = (int64_t)gridDim.x * (WAVE ? THREADS / kWave : THREADS);
+};
+
+// N rows of C scores, `ld` floats apart, as every entry point of rank_metrics.hip and calibration.hip takes them.  (supervised.hip
+// spells its checks out: N has no upper limit there, C starts at 2, and the texts differ.)
+#define MSN_REQUIRE_ROWS(who, N, C, ld)                                                                              \
+    do {                                                                                                             \
+        MSN_REQUIRE((N) >= 1 && (N) < ((int64_t)1 << 31), who ": N must be in 1..2^31 - 1 (got %lld)", (long long)(N)); \
+        MSN_REQUIRE((C) >= 1 && (C) <= ::msn::kMaxClasses, who ": C must be in 1..1024 (got %d)", (C));                \
+        MSN_REQUIRE((ld) >= (C), who ": row stride %lld below C = %d", (long long)(ld), (C));                           \
+    } while (0)
 
 // Block-wide sum through LDS; `red` holds >= blockDim.x/64 floats. Every thread gets the result.
 __device__ __forceinline__ float block_sum(float v, float* red) {
@@ -185,6 +228,30 @@ __device__ __forceinline__ double block_combine(double v, double* red) {
     double t = red[0];
     for (int i = 1; i < THREADS / kWave; ++i) t = norm_combine<P>(t, red[i]);
     return t;
+}
+
+// Sums of K doubles over a block of blockDim.x threads, `red` holding K doubles per wave: the order of block_combine, which
+// also takes the NaN-keeping max.  (Kept apart: here a barrier also precedes the write of `red`, so the caller may reuse it.)
+template <int K>
+__device__ __forceinline__ void block_sum_f64(double (&v)[K], double* red) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);      // (through wave_sum the K chains are scheduled differently)
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    __syncthreads();
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) red[w * K + k] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double t = red[k];
+        for (int i = 1; i < nw; ++i) t += red[i * K + k];
+        v[k] = t;
+    }
 }
 
 // Exact (erf) GELU, as torch.nn.GELU() default, and its derivative.

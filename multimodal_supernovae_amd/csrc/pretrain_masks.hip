@@ -22,12 +22,6 @@ __device__ __forceinline__ uint64_t mix(uint64_t seed, uint64_t c) {
     return x;
 }
 
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // seed_base != NULL: the seed is seed_base[0] + seed (dropout_kernel's convention)
 __global__ __launch_bounds__(PM_THREADS) void pretrain_masks_kernel(const uint8_t* __restrict__ pad, const float* __restrict__ x,
                                                                     int64_t B, int T, int nbands, double f_mask, int mode,
@@ -49,7 +43,7 @@ __global__ __launch_bounds__(PM_THREADS) void pretrain_masks_kernel(const uint8_
             for (int k = wave; k < nbands; k += PM_THREADS / kWave) {       // one wave counts one band
                 int n = 0;
                 for (int j = lane; j < band; j += kWave) n += pad_s[band * k + j];
-                n = wave_sum_int(n);
+                n = wave_sum(n);
                 const int h = (int)floor((double)n * f_mask);
                 const int start = band * k + (int)__umul64hi(mix(seed, (uint64_t)i * (uint64_t)nbands + (uint64_t)k),
                                                              (uint64_t)(n - h + 1));
@@ -79,7 +73,7 @@ __global__ __launch_bounds__(PM_THREADS) void pretrain_masks_kernel(const uint8_
                 n += pad_s[j];
                 key_s[j] = mix(seed, (uint64_t)row + (uint64_t)j);
             }
-            n = wave_sum_int(n);
+            n = wave_sum(n);
             if (lane == 0) red[wave] = n;
             __syncthreads();                       // the keys and the waves' counts are in LDS
             n = 0;

@@ -321,8 +321,7 @@ __global__ __launch_bounds__(kLrThreads) void logreg_kernel(const float* __restr
     }
     // ---- the block's partial: the loss in slot 0, then the gradient in W's layout
     double* out = part + (int64_t)blockIdx.x * stride;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) loss += __shfl_xor(loss, o, 64);
+    loss = wave_sum(loss);
     __syncthreads();
     if (lane == 0) red[w] = loss;
     __syncthreads();

@@ -23,10 +23,8 @@ namespace msn {
 
 constexpr int kRankThreads = 256;          // rows i of one workgroup
 constexpr int kRankChunk = 128;            // rows j staged in LDS at a time
-constexpr int kRankNarrowC = 16;           // up to here whole rows are staged
 constexpr int kRankMaxSlabs = 16;          // cuts of the j range (per-slab int32 partials in ws)
 constexpr int kRankFinishThreads = 1024;
-constexpr int kRankMaxC = 1024;
 constexpr int kRankMaxT = 1024;
 constexpr int kRankWaveRows = kRankThreads / kWave;
 
@@ -43,16 +41,6 @@ static inline RankPlan rank_plan(int64_t N) {
     return {(int)blocks_i, (int)cdiv(nchunks, slab_chunks), slab_chunks * kRankChunk};
 }
 
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ void add_i64(int64_t* p, long long v) {
-    atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
-}
-
 // part[slab][i] = {n_gt, n_ge, p_ge} of row i against the rows j of the slab; rows with a target outside [0, C) write nothing.
 // NARROW: grid (blocks_i, slabs), a lane's class is its row's.  Otherwise grid (blocks_i, slabs, C): only the rows of class
 // blockIdx.z count here, and a workgroup without one leaves.
@@ -60,7 +48,7 @@ template <bool NARROW>
 __global__ __launch_bounds__(kRankThreads) void rank_counts_kernel(const float* __restrict__ S, int64_t ld,
                                                                    const int64_t* __restrict__ y, int64_t N, int C,
                                                                    int64_t slab_rows, int* __restrict__ part) {
-    __shared__ float tile[NARROW ? kRankChunk * kRankNarrowC : kRankChunk];
+    __shared__ float tile[NARROW ? kRankChunk * kNarrowC : kRankChunk];
     __shared__ int cls[kRankChunk];
     const int64_t i = (int64_t)blockIdx.x * kRankThreads + threadIdx.x;
     int c = -1;
@@ -152,9 +140,9 @@ __global__ __launch_bounds__(kRankFinishThreads) void rank_finish_kernel(const i
     }
     __syncthreads();                                      // isum is zero
     ap = block_combine<1, kRankFinishThreads>(ap, red);
-    P = wave_sum_i64(P);
-    V = wave_sum_i64(V);
-    G = wave_sum_i64(G);
+    P = wave_sum(P);
+    V = wave_sum(V);
+    G = wave_sum(G);
     if ((threadIdx.x & 63) == 0) {
         atomicAdd(&isum[0], (unsigned long long)P);
         atomicAdd(&isum[1], (unsigned long long)V);
@@ -216,8 +204,8 @@ __global__ __launch_bounds__(kRankThreads) void threshold_counts_kernel(const fl
         r0 += hist[2 * b];
         r1 += hist[2 * b + 1];
         int64_t* cell = acc + ((int64_t)c * T + (b - 1)) * 2;
-        if (r0) add_i64(cell, r0);
-        if (r1) add_i64(cell + 1, r1);
+        if (r0) atomic_add_i64(cell, r0);
+        if (r1) atomic_add_i64(cell + 1, r1);
     }
     if (threadIdx.x == 0) {
         int p = 0, q = 0;
@@ -225,8 +213,8 @@ __global__ __launch_bounds__(kRankThreads) void threshold_counts_kernel(const fl
             p += seg[2 * k];
             q += seg[2 * k + 1];
         }
-        if (p) add_i64(tot + 2 * c, p);
-        if (q) add_i64(tot + 2 * c + 1, q);
+        if (p) atomic_add_i64(tot + 2 * c, p);
+        if (q) atomic_add_i64(tot + 2 * c + 1, q);
     }
 }
 
@@ -235,13 +223,12 @@ template <bool WAVE>
 __global__ __launch_bounds__(kRankThreads) void topk_ranks_kernel(const float* __restrict__ S, int64_t ld,
                                                                   const int64_t* __restrict__ y, int64_t N, int C,
                                                                   int* __restrict__ rank, int64_t* __restrict__ hist) {
-    __shared__ int lh[kRankMaxC];
+    __shared__ int lh[kMaxClasses];
     for (int k = threadIdx.x; k < C; k += kRankThreads) lh[k] = 0;
     __syncthreads();
     const int lane = threadIdx.x & 63;
-    const int64_t unit = WAVE ? (int64_t)blockIdx.x * kRankWaveRows + (threadIdx.x >> 6) : (int64_t)blockIdx.x * kRankThreads + threadIdx.x;
-    const int64_t step = (int64_t)gridDim.x * (WAVE ? kRankWaveRows : kRankThreads);
-    for (int64_t i = unit; i < N; i += step) {
+    const RowWalk<WAVE, kRankThreads> walk{};
+    for (int64_t i = walk.unit; i < N; i += walk.step) {
         const int64_t yi = y[i];
         int r = -1;
         if (yi >= 0 && yi < C) {                          // uniform over the wave in the wave form
@@ -253,8 +240,7 @@ __global__ __launch_bounds__(kRankThreads) void topk_ranks_kernel(const float* _
                     const float v = row[k];
                     r += (v > s || (v == s && k < yi)) ? 1 : 0;
                 }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) r += __shfl_xor(r, o, 64);
+                r = wave_sum(r);
             } else {
                 for (int k = 0; k < C; ++k) {
                     const float v = row[k];
@@ -268,7 +254,7 @@ __global__ __launch_bounds__(kRankThreads) void topk_ranks_kernel(const float* _
     __syncthreads();
     for (int k = threadIdx.x; k < C; k += kRankThreads) {
         const int n = lh[k];
-        if (n) add_i64(hist + k, n);
+        if (n) atomic_add_i64(hist + k, n);
     }
 }
 
@@ -278,9 +264,8 @@ template <bool WAVE>
 __global__ __launch_bounds__(kRankThreads) void log_softmax_rows_kernel(const float* __restrict__ x, int64_t ldx, int64_t N,
                                                                         int C, float* __restrict__ out, int64_t ldo) {
     const int lane = threadIdx.x & 63;
-    const int64_t unit = WAVE ? (int64_t)blockIdx.x * kRankWaveRows + (threadIdx.x >> 6) : (int64_t)blockIdx.x * kRankThreads + threadIdx.x;
-    const int64_t step = (int64_t)gridDim.x * (WAVE ? kRankWaveRows : kRankThreads);
-    for (int64_t i = unit; i < N; i += step) {
+    const RowWalk<WAVE, kRankThreads> walk{};
+    for (int64_t i = walk.unit; i < N; i += walk.step) {
         const float* row = x + i * ldx;
         float* o = out + i * ldo;
         if constexpr (WAVE) {
@@ -325,18 +310,11 @@ __global__ __launch_bounds__(kRankThreads) void log_softmax_rows_kernel(const fl
     }
 }
 
-static inline bool rank_shape_ok(int64_t N, int C) { return N >= 1 && N < ((int64_t)1 << 31) && C >= 1 && C <= kRankMaxC; }
+static inline bool rank_shape_ok(int64_t N, int C) { return N >= 1 && N < ((int64_t)1 << 31) && C >= 1 && C <= kMaxClasses; }
 
 }  // namespace msn
 
 using namespace msn;
-
-#define RANK_REQUIRE_SHAPE(who, N, C, ld)                                                                            \
-    do {                                                                                                             \
-        MSN_REQUIRE((N) >= 1 && (N) < ((int64_t)1 << 31), who ": N must be in 1..2^31 - 1 (got %lld)", (long long)(N)); \
-        MSN_REQUIRE((C) >= 1 && (C) <= kRankMaxC, who ": C must be in 1..1024 (got %d)", (C));                          \
-        MSN_REQUIRE((ld) >= (C), who ": row stride %lld below C = %d", (long long)(ld), (C));                           \
-    } while (0)
 
 extern "C" size_t msn_rank_counts_workspace_bytes(int64_t N, int C) {
     if (!rank_shape_ok(N, C)) return 0;
@@ -346,13 +324,13 @@ extern "C" size_t msn_rank_counts_workspace_bytes(int64_t N, int C) {
 extern "C" int msn_rank_counts(const float* S, int64_t ld, const int64_t* y, int64_t N, int C, int* counts, int64_t* istats,
                                double* ap_sum, void* ws, size_t ws_bytes, msn_stream_t stream) {
     MSN_REQUIRE(S && y && counts && istats && ap_sum, "msn_rank_counts: null pointer");
-    RANK_REQUIRE_SHAPE("msn_rank_counts", N, C, ld);
+    MSN_REQUIRE_ROWS("msn_rank_counts", N, C, ld);
     const size_t need = msn_rank_counts_workspace_bytes(N, C);
     MSN_REQUIRE(ws && ws_bytes >= need, "msn_rank_counts: workspace of %zu bytes needed, %zu given", need, ws_bytes);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const RankPlan P = rank_plan(N);
     int* part = static_cast<int*>(ws);
-    if (C <= kRankNarrowC)
+    if (C <= kNarrowC)
         hipLaunchKernelGGL(rank_counts_kernel<true>, dim3(P.blocks_i, P.slabs), dim3(kRankThreads), 0, st, S, ld, y, N, C,
                            P.slab_rows, part);
     else
@@ -367,7 +345,7 @@ extern "C" int msn_rank_counts(const float* S, int64_t ld, const int64_t* y, int
 extern "C" int msn_threshold_counts(const float* S, int64_t ld, const int64_t* y, int64_t N, int C, const float* thr, int T,
                                     int64_t* acc, int64_t* tot, msn_stream_t stream) {
     MSN_REQUIRE(S && y && thr && acc && tot, "msn_threshold_counts: null pointer");
-    RANK_REQUIRE_SHAPE("msn_threshold_counts", N, C, ld);
+    MSN_REQUIRE_ROWS("msn_threshold_counts", N, C, ld);
     MSN_REQUIRE(T >= 1 && T <= kRankMaxT, "msn_threshold_counts: T must be in 1..1024 (got %d)", T);
     const int blocks = (int)std::min<int64_t>(cdiv(N, 4 * kRankThreads), 64);
     hipLaunchKernelGGL(threshold_counts_kernel, dim3(blocks, C), dim3(kRankThreads), 0, static_cast<hipStream_t>(stream), S, ld,
@@ -379,9 +357,9 @@ extern "C" int msn_threshold_counts(const float* S, int64_t ld, const int64_t* y
 extern "C" int msn_topk_ranks(const float* S, int64_t ld, const int64_t* y, int64_t N, int C, int* rank_or_null, int64_t* hist,
                               msn_stream_t stream) {
     MSN_REQUIRE(S && y && hist, "msn_topk_ranks: null pointer");
-    RANK_REQUIRE_SHAPE("msn_topk_ranks", N, C, ld);
+    MSN_REQUIRE_ROWS("msn_topk_ranks", N, C, ld);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (C <= kRankNarrowC) {
+    if (C <= kNarrowC) {
         const int blocks = (int)std::min<int64_t>(cdiv(N, kRankThreads), 1024);
         hipLaunchKernelGGL(topk_ranks_kernel<false>, dim3(blocks), dim3(kRankThreads), 0, st, S, ld, y, N, C, rank_or_null, hist);
     } else {
@@ -394,10 +372,10 @@ extern "C" int msn_topk_ranks(const float* S, int64_t ld, const int64_t* y, int6
 
 extern "C" int msn_log_softmax_rows(const float* x, int64_t ldx, int64_t N, int C, float* out, int64_t ldo, msn_stream_t stream) {
     MSN_REQUIRE(x && out, "msn_log_softmax_rows: null pointer");
-    RANK_REQUIRE_SHAPE("msn_log_softmax_rows", N, C, ldx);
+    MSN_REQUIRE_ROWS("msn_log_softmax_rows", N, C, ldx);
     MSN_REQUIRE(ldo >= C, "msn_log_softmax_rows: output row stride %lld below C = %d", (long long)ldo, C);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (C <= kRankNarrowC) {
+    if (C <= kNarrowC) {
         const int blocks = (int)std::min<int64_t>(cdiv(N, kRankThreads), 4096);
         hipLaunchKernelGGL(log_softmax_rows_kernel<false>, dim3(blocks), dim3(kRankThreads), 0, st, x, ldx, N, C, out, ldo);
     } else {

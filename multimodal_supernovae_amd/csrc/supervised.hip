@@ -29,7 +29,6 @@ namespace msn {
 constexpr int kSupThreads = 256;
 constexpr int kSupMaxThreads = 1024;       // the single-workgroup form
 constexpr int kSupMaxBlocks = 2048;        // partials the finishing block reads
-constexpr int kLaneRowMaxC = 16;           // up to here a lane owns whole rows
 constexpr int64_t kLaneOneBlockRows = 4096;   // lane-per-row: rows a single workgroup takes (4 per lane)
 constexpr int64_t kWaveOneBlockRows = 64;     // wave-per-row: rows a single workgroup takes (4 per wave)
 constexpr int kCmLdsMaxC = 64;             // C * C * 4 <= 16 KB: the histogram is privatised per workgroup in LDS
@@ -38,29 +37,6 @@ struct RowStat {
     float m, t;   // row maximum; sum of exp(x_c - m) over every c but the arg-max
     int a;        // first maximal index
 };
-
-// Sums of K doubles over the block in a fixed order: xor-shuffle tree inside each wave, then the waves in wave order.
-template <int K>
-__device__ __forceinline__ void block_sum_f64(double (&v)[K], double* red) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) red[w * K + k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double t = red[k];
-        for (int i = 1; i < nw; ++i) t += red[i * K + k];
-        v[k] = t;
-    }
-}
 
 // Does (m2, a2) beat (m, a) as a row's arg-max?  torch.argmax's order: a NaN beats every number, the first index wins a tie.
 __device__ __forceinline__ bool argmax_better(float m2, int a2, float m, int a) {
@@ -321,7 +297,7 @@ static inline int round_up_wave(int64_t n) { return (int)std::min<int64_t>(kSupM
 
 // cross-entropy, either direction: one workgroup while it can take every row, 256-thread blocks beyond that
 static inline SupLaunch ce_launch(int64_t N, int C) {
-    if (C <= kLaneRowMaxC) {
+    if (C <= kNarrowC) {
         if (N <= kLaneOneBlockRows) return {1, round_up_wave(N)};
         return {(int)std::min<int64_t>(cdiv(N, kSupThreads), kSupMaxBlocks), kSupThreads};
     }
@@ -339,7 +315,7 @@ static inline SupLaunch stats_launch(int64_t N) {
 using namespace msn;
 
 extern "C" size_t msn_cross_entropy_workspace_bytes(int64_t N, int C) {
-    if (N < 1 || C < 2 || C > 1024) return 0;
+    if (N < 1 || C < 2 || C > kMaxClasses) return 0;
     const SupLaunch L = ce_launch(N, C);
     return L.blocks > 1 ? (size_t)L.blocks * 2 * sizeof(double) : 0;
 }
@@ -349,7 +325,7 @@ extern "C" int msn_cross_entropy_fwd(const float* logits, int64_t ld, const int6
                                      size_t ws_bytes, msn_stream_t stream) {
     MSN_REQUIRE(logits && target && lse && pred && out, "msn_cross_entropy_fwd: null pointer");
     MSN_REQUIRE(N >= 1, "msn_cross_entropy_fwd: N must be at least 1 (got %lld)", (long long)N);
-    MSN_REQUIRE(C >= 2 && C <= 1024, "msn_cross_entropy_fwd: C must be in 2..1024 (got %d)", C);
+    MSN_REQUIRE(C >= 2 && C <= kMaxClasses, "msn_cross_entropy_fwd: C must be in 2..1024 (got %d)", C);
     MSN_REQUIRE(ld >= C, "msn_cross_entropy_fwd: row stride %lld below C = %d", (long long)ld, C);
     const size_t need = msn_cross_entropy_workspace_bytes(N, C);
     MSN_REQUIRE(need == 0 || (ws && ws_bytes >= need), "msn_cross_entropy_fwd: workspace of %zu bytes needed, %zu given", need,
@@ -358,7 +334,7 @@ extern "C" int msn_cross_entropy_fwd(const float* logits, int64_t ld, const int6
     const SupLaunch L = ce_launch(N, C);
     double* part = static_cast<double*>(ws);
     const dim3 grid(L.blocks), block(L.threads);
-    if (C <= kLaneRowMaxC)
+    if (C <= kNarrowC)
         hipLaunchKernelGGL(ce_fwd_lane_kernel, grid, block, 0, st, logits, ld, target, weight, N, C, denom_in, lse, pred, out, part);
     else if (C <= 64)
         hipLaunchKernelGGL(ce_fwd_wave_kernel<1>, grid, block, 0, st, logits, ld, target, weight, N, C, denom_in, lse, pred, out, part);
@@ -378,12 +354,12 @@ extern "C" int msn_cross_entropy_bwd(const float* logits, int64_t ld, const int6
                                      msn_stream_t stream) {
     MSN_REQUIRE(logits && target && denom && grad_out && dlogits, "msn_cross_entropy_bwd: null pointer");
     MSN_REQUIRE(N >= 1, "msn_cross_entropy_bwd: N must be at least 1 (got %lld)", (long long)N);
-    MSN_REQUIRE(C >= 2 && C <= 1024, "msn_cross_entropy_bwd: C must be in 2..1024 (got %d)", C);
+    MSN_REQUIRE(C >= 2 && C <= kMaxClasses, "msn_cross_entropy_bwd: C must be in 2..1024 (got %d)", C);
     MSN_REQUIRE(ld >= C && lddx >= C, "msn_cross_entropy_bwd: row stride below C = %d", C);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const SupLaunch L = ce_launch(N, C);
     const dim3 grid(L.blocks), block(L.threads);
-    if (C <= kLaneRowMaxC)
+    if (C <= kNarrowC)
         hipLaunchKernelGGL(ce_bwd_lane_kernel, grid, block, 0, st, logits, ld, target, weight, N, C, denom, grad_out, dlogits, lddx);
     else if (C <= 64)
         hipLaunchKernelGGL(ce_bwd_wave_kernel<1>, grid, block, 0, st, logits, ld, target, weight, N, C, denom, grad_out, dlogits, lddx);
@@ -398,7 +374,7 @@ extern "C" int msn_cross_entropy_bwd(const float* logits, int64_t ld, const int6
 extern "C" int msn_confusion_matrix(const int64_t* target, const int* pred, int64_t N, int C, int* cm, msn_stream_t stream) {
     MSN_REQUIRE(target && pred && cm, "msn_confusion_matrix: null pointer");
     MSN_REQUIRE(N >= 1, "msn_confusion_matrix: N must be at least 1 (got %lld)", (long long)N);
-    MSN_REQUIRE(C >= 2 && C <= 1024, "msn_confusion_matrix: C must be in 2..1024 (got %d)", C);
+    MSN_REQUIRE(C >= 2 && C <= kMaxClasses, "msn_confusion_matrix: C must be in 2..1024 (got %d)", C);
     const int use_lds = C <= kCmLdsMaxC;
     const int blocks = (int)std::min<int64_t>(cdiv(N, 4 * kSupThreads), 256);
     hipLaunchKernelGGL(confusion_kernel, dim3(blocks), dim3(kSupThreads), use_lds ? (size_t)C * C * sizeof(int) : 0,

@@ -26,31 +26,21 @@ import torch
 
 from . import _lib
 from . import distributed as D
+from ._device_args import (MAX_CLASSES, EpochCounts, accumulator, ld, reference_inputs, rows_on_gpu, scores_and_targets,
+                           to_numpy, workspace)
 from ._lib import check, lib, ptr, stream_ptr
 
-MAX_CLASSES = 1024
 MAX_THRESHOLDS = 1024
 IGNORE = -100
 
 
 # ------------------------------------------------------------------------------------------------- host: restatements
-def _ref_inputs(S, y, n_classes, who):
-    S = np.asarray(S, dtype=np.float32)
-    y = np.asarray(y).astype(np.int64)
-    if S.ndim != 2 or y.shape != (S.shape[0],):
-        raise ValueError(f"{who}: scores (N, C) and targets (N,) needed (got {S.shape} and {y.shape})")
-    C = S.shape[1] if n_classes is None else int(n_classes)
-    if C != S.shape[1]:
-        raise ValueError(f"{who}: {S.shape[1]} score columns for {C} classes")
-    return S, y, C, (y >= 0) & (y < C)
-
-
 def rank_counts_reference(S, y, n_classes=None):
     """numpy restatement of msn_rank_counts: (counts int32 (N, 3) = {n_gt, n_ge, p_ge}, istats int64 (C, 3) = {P, Nneg, U2},
     ap_sum fp64 (C)).  Compares are fp32 compares (a NaN is false both ways); every quotient p_ge / (p_ge + n_ge) is rounded
     once and a class's quotients are added by math.fsum (the correctly rounded sum: the kernel's fixed order lies within
     P_c 2^-52 ap_sum of it)."""
-    S, y, C, valid = _ref_inputs(S, y, n_classes, "rank_counts_reference")
+    S, y, C, valid = reference_inputs(S, y, n_classes, "rank_counts_reference")
     N = len(y)
     counts = np.zeros((N, 3), dtype=np.int32)
     istats = np.zeros((C, 3), dtype=np.int64)
@@ -75,7 +65,7 @@ def rank_counts_reference(S, y, n_classes=None):
 def threshold_counts_reference(S, y, thresholds, n_classes=None):
     """numpy restatement of msn_threshold_counts for one call from zero: (acc int64 (C, T, 2), tot int64 (C, 2)) with
     acc[c, t] = {#(y = c, S[:, c] >= thr[t]), #(y != c, S[:, c] >= thr[t])} over the valid rows, tot[c] = {P_c, Nneg_c}."""
-    S, y, C, valid = _ref_inputs(S, y, n_classes, "threshold_counts_reference")
+    S, y, C, valid = reference_inputs(S, y, n_classes, "threshold_counts_reference")
     thr = np.asarray(thresholds, dtype=np.float32).reshape(-1)
     acc = np.zeros((C, len(thr), 2), dtype=np.int64)
     tot = np.zeros((C, 2), dtype=np.int64)
@@ -90,7 +80,7 @@ def threshold_counts_reference(S, y, thresholds, n_classes=None):
 def topk_ranks_reference(S, y, n_classes=None):
     """numpy restatement of msn_topk_ranks: (rank int32 (N), -1 for ignored rows; hist int64 (C)).  rank = the classes scoring
     above the target class, plus the lower classes scoring the same."""
-    S, y, C, valid = _ref_inputs(S, y, n_classes, "topk_ranks_reference")
+    S, y, C, valid = reference_inputs(S, y, n_classes, "topk_ranks_reference")
     rank = np.full(len(y), -1, dtype=np.int32)
     rows = np.nonzero(valid)[0]
     s = S[rows, y[rows]][:, None]
@@ -100,10 +90,6 @@ def topk_ranks_reference(S, y, n_classes=None):
 
 
 # ---------------------------------------------------------------------------------------------- host: the metrics
-def _np(a, dtype):
-    return np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a, dtype=dtype)
-
-
 def _average(per_class, weights, average, who):
     """Mean of the defined (non-nan) entries: plain ("macro") or weighted by the classes' positives ("weighted"); None gives
     the per-class array.  nan when no class is defined -- the rule of the macro F1 of classification_metrics."""
@@ -121,7 +107,7 @@ def _average(per_class, weights, average, who):
 
 
 def _per_class_auroc(istats):
-    st = _np(istats, np.int64).reshape(-1, 3)
+    st = to_numpy(istats, np.int64).reshape(-1, 3)
     out = np.full(len(st), np.nan)
     for c, (P, Nneg, U2) in enumerate(st.tolist()):
         if P > 0 and Nneg > 0:
@@ -137,8 +123,8 @@ def auroc_from_stats(istats, average="macro"):
 
 
 def _per_class_ap(istats, ap_sum):
-    st = _np(istats, np.int64).reshape(-1, 3)
-    s = _np(ap_sum, np.float64).reshape(-1)
+    st = to_numpy(istats, np.int64).reshape(-1, 3)
+    s = to_numpy(ap_sum, np.float64).reshape(-1)
     out = np.full(len(st), np.nan)
     ok = st[:, 0] > 0
     out[ok] = s[ok] / st[ok, 0]
@@ -154,7 +140,7 @@ def average_precision_from_stats(istats, ap_sum, average="macro"):
 
 def topk_accuracy(hist, k):
     """Share of the counted rows whose target class is among the k best-scored: sum(hist[:k]) / sum(hist); nan without rows."""
-    h = _np(hist, np.int64).reshape(-1)
+    h = to_numpy(hist, np.int64).reshape(-1)
     if not 1 <= int(k) <= len(h):
         raise ValueError(f"topk_accuracy: k must be in 1..{len(h)} (got {k})")
     total = int(h.sum())
@@ -162,7 +148,7 @@ def topk_accuracy(hist, k):
 
 
 def _binned(acc, tot):
-    acc, tot = _np(acc, np.int64), _np(tot, np.int64)
+    acc, tot = to_numpy(acc, np.int64), to_numpy(tot, np.int64)
     if acc.ndim != 3 or acc.shape[2] != 2 or tot.shape != (acc.shape[0], 2):
         raise ValueError(f"binned curves: acc (C, T, 2) and tot (C, 2) needed (got {acc.shape} and {tot.shape})")
     return acc.astype(np.float64), tot.astype(np.float64)
@@ -197,7 +183,7 @@ def binned_auroc(acc, tot, average="macro"):
     x = np.concatenate([np.ones((C, 1)), fpr, np.zeros((C, 1))], axis=1)
     y = np.concatenate([np.ones((C, 1)), tpr, np.zeros((C, 1))], axis=1)
     per = ((x[:, :-1] - x[:, 1:]) * (y[:, :-1] + y[:, 1:])).sum(axis=1) * 0.5
-    return _average(per, _np(tot, np.int64)[:, 0], average, "binned_auroc")
+    return _average(per, to_numpy(tot, np.int64)[:, 0], average, "binned_auroc")
 
 
 def binned_average_precision(acc, tot, average="macro"):
@@ -206,71 +192,28 @@ def binned_average_precision(acc, tot, average="macro"):
     precision, recall = precision_recall_curve_binned(acc, tot)
     r = np.concatenate([recall, np.zeros((recall.shape[0], 1))], axis=1)
     per = ((r[:, :-1] - r[:, 1:]) * precision).sum(axis=1)
-    return _average(per, _np(tot, np.int64)[:, 0], average, "binned_average_precision")
+    return _average(per, to_numpy(tot, np.int64)[:, 0], average, "binned_average_precision")
 
 
 # ------------------------------------------------------------------------------------------------------ device halves
-def _ld(t):
-    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
-
-
-def _scores_on_gpu(scores, who):
-    """float32 (N, C) scores on the GPU as the kernels read them: any row stride >= C is kept, anything else is made dense."""
-    if not isinstance(scores, torch.Tensor) or scores.dim() != 2 or scores.dtype != torch.float32:
-        raise ValueError(f"{who}: scores must be a float32 (N, C) tensor (got {getattr(scores, 'dtype', type(scores).__name__)} "
-                         f"{tuple(getattr(scores, 'shape', ()))})")
-    if scores.device.type != "cuda":
-        raise _lib.MsnHipError(f"{who}: scores must live on the GPU (got {scores.device}); there is no CPU path")
-    _lib.require_gpu()
-    N, C = scores.shape
-    if N == 0:
-        raise ValueError(f"{who}: no rows")
-    if not 1 <= C <= MAX_CLASSES:
-        raise _lib.MsnHipError(f"{who}: 1 to {MAX_CLASSES} classes (got {C})")
-    scores = scores.detach()
-    if (scores.stride(1) != 1 and C > 1) or scores.stride(0) < C:
-        scores = scores.contiguous()
-    return scores
-
-
-def _checked(scores, target, who):
-    """Scores float32 (N, C) and targets int64 (N) on one GPU."""
-    S = _scores_on_gpu(scores, who)
-    N = S.shape[0]
-    if not isinstance(target, torch.Tensor) or target.shape != (N,) or target.dtype != torch.int64:
-        raise ValueError(f"{who}: targets must be an int64 tensor of shape ({N},) (got {getattr(target, 'dtype', type(target).__name__)} "
-                         f"{tuple(getattr(target, 'shape', ()))})")
-    if target.device != S.device:
-        raise _lib.MsnHipError(f"{who}: targets must live on the GPU next to the scores (got {target.device}); there is no CPU path")
-    return S, target.detach().contiguous()
-
-
 def rank_counts(scores, target):
     """(counts int32 (N, 3), istats int64 (C, 3), ap_sum fp64 (C)) of msn_rank_counts, all on the device.  Enqueue only."""
-    S, y = _checked(scores, target, "rank_counts")
+    S, y = scores_and_targets(scores, target, "rank_counts")
     N, C = S.shape
     counts = torch.empty((N, 3), dtype=torch.int32, device=S.device)
     istats = torch.empty((C, 3), dtype=torch.int64, device=S.device)
     ap_sum = torch.empty(C, dtype=torch.float64, device=S.device)
     L = lib()
-    ws = torch.empty(L.msn_rank_counts_workspace_bytes(N, C) // 4, dtype=torch.int32, device=S.device)
-    check(L.msn_rank_counts(ptr(S), _ld(S), ptr(y), N, C, ptr(counts), ptr(istats), ptr(ap_sum), ptr(ws), ws.numel() * 4,
+    ws = workspace(L.msn_rank_counts_workspace_bytes(N, C), S.device)
+    check(L.msn_rank_counts(ptr(S), ld(S), ptr(y), N, C, ptr(counts), ptr(istats), ptr(ap_sum), ptr(ws), ws.numel(),
                             stream_ptr()), "msn_rank_counts")
     return counts, istats, ap_sum
-
-
-def _accumulator(t, shape, device, who):
-    if t is None:
-        return torch.zeros(shape, dtype=torch.int64, device=device)
-    if t.shape != shape or t.dtype != torch.int64 or t.device != device or not t.is_contiguous():
-        raise ValueError(f"{who}: the accumulator must be a contiguous int64 {tuple(shape)} tensor on {device}")
-    return t
 
 
 def threshold_counts(scores, target, thresholds, acc=None, tot=None):
     """(acc int64 (C, T, 2), tot int64 (C, 2)) of msn_threshold_counts for ascending float32 thresholds (T) on the device; acc /
     tot given are added to (the accumulators of a validation epoch), else they start from zero.  Enqueue only."""
-    S, y = _checked(scores, target, "threshold_counts")
+    S, y = scores_and_targets(scores, target, "threshold_counts")
     N, C = S.shape
     if not isinstance(thresholds, torch.Tensor) or thresholds.dim() != 1 or thresholds.dtype != torch.float32:
         raise ValueError("threshold_counts: thresholds must be a float32 (T,) tensor")
@@ -280,29 +223,29 @@ def threshold_counts(scores, target, thresholds, acc=None, tot=None):
     if not 1 <= T <= MAX_THRESHOLDS:
         raise _lib.MsnHipError(f"threshold_counts: 1 to {MAX_THRESHOLDS} thresholds (got {T})")
     thr = thresholds.detach().contiguous()
-    acc = _accumulator(acc, (C, T, 2), S.device, "threshold_counts")
-    tot = _accumulator(tot, (C, 2), S.device, "threshold_counts")
-    check(lib().msn_threshold_counts(ptr(S), _ld(S), ptr(y), N, C, ptr(thr), T, ptr(acc), ptr(tot), stream_ptr()),
+    acc = accumulator(acc, (C, T, 2), S.device, "threshold_counts")
+    tot = accumulator(tot, (C, 2), S.device, "threshold_counts")
+    check(lib().msn_threshold_counts(ptr(S), ld(S), ptr(y), N, C, ptr(thr), T, ptr(acc), ptr(tot), stream_ptr()),
           "msn_threshold_counts")
     return acc, tot
 
 
 def topk_ranks(scores, target, hist=None, return_ranks=True):
     """(rank int32 (N) or None, hist int64 (C)) of msn_topk_ranks; a hist given is added to.  Enqueue only."""
-    S, y = _checked(scores, target, "topk_ranks")
+    S, y = scores_and_targets(scores, target, "topk_ranks")
     N, C = S.shape
     rank = torch.empty(N, dtype=torch.int32, device=S.device) if return_ranks else None
-    hist = _accumulator(hist, (C,), S.device, "topk_ranks")
-    check(lib().msn_topk_ranks(ptr(S), _ld(S), ptr(y), N, C, ptr(rank), ptr(hist), stream_ptr()), "msn_topk_ranks")
+    hist = accumulator(hist, (C,), S.device, "topk_ranks")
+    check(lib().msn_topk_ranks(ptr(S), ld(S), ptr(y), N, C, ptr(rank), ptr(hist), stream_ptr()), "msn_topk_ranks")
     return rank, hist
 
 
 def log_softmax_rows(logits):
     """log_softmax over the rows of float32 (N, C) logits in one launch (msn_log_softmax_rows), a new dense tensor."""
-    S = _scores_on_gpu(logits, "log_softmax_rows")
+    S = rows_on_gpu(logits, "log_softmax_rows", "scores", MAX_CLASSES)
     N, C = S.shape
     out = torch.empty((N, C), dtype=torch.float32, device=S.device)
-    check(lib().msn_log_softmax_rows(ptr(S), _ld(S), N, C, ptr(out), C, stream_ptr()), "msn_log_softmax_rows")
+    check(lib().msn_log_softmax_rows(ptr(S), ld(S), N, C, ptr(out), C, stream_ptr()), "msn_log_softmax_rows")
     return out
 
 
@@ -338,7 +281,7 @@ def binary_average_precision(scores, target):
     return float(average_precision_from_stats(istats.cpu(), ap_sum.cpu(), None)[1])
 
 
-class RankingMetrics:
+class RankingMetrics(EpochCounts):
     """AUROC, average precision and top-k accuracy over the batches of a validation epoch, in the shape of
     ClassificationMetrics: reset, update(scores, target), all_reduce(group), compute().
 
@@ -347,6 +290,8 @@ class RankingMetrics:
     in fp32) or a float32 tensor is the binned mode: update is one msn_threshold_counts launch into int64 accumulators,
     all_reduce their SUM, compute the one host copy; the thresholds are in the units of the scores as they are ranked (after
     `normalize`).  The top-k histogram accumulates in both modes.  normalize="log_softmax" ranks logits as log-probabilities."""
+
+    _counts = ("hist", "acc", "tot")                            # acc and tot in the binned mode only
 
     def __init__(self, n_classes, thresholds=None, top_k=(1,), normalize=None):
         self.n_classes = int(n_classes)
@@ -376,9 +321,7 @@ class RankingMetrics:
     def reset(self):
         self._scores, self._targets, self._gathered = [], [], False
         self.istats = self.ap_sum = None                       # the exact mode's last pair count, on the device
-        for t in (self.hist, self.acc, self.tot):
-            if t is not None:
-                t.zero_()
+        super().reset()
 
     def _buffers(self, device):
         C = self.n_classes
@@ -395,7 +338,7 @@ class RankingMetrics:
             return
         if isinstance(target, torch.Tensor):
             target = target.to(torch.int64)
-        S, y = _checked(scores, target, "RankingMetrics.update")
+        S, y = scores_and_targets(scores, target, "RankingMetrics.update")
         if S.shape[1] != self.n_classes:
             raise ValueError(f"RankingMetrics.update: {S.shape[1]} score columns for {self.n_classes} classes")
         if self.normalize == "log_softmax":
@@ -421,17 +364,8 @@ class RankingMetrics:
         """Every rank enters, also one whose shard was empty (pass its device then).  Binned: SUM of the accumulators.  Exact:
         all ranks gather all rows -- all_gather_rows wants equal blocks, so a shard is padded to the largest with rows of target
         -100, which count nowhere."""
-        if D.world_size(group) == 1:
-            return
-        device = self.hist.device if self.hist is not None else torch.device(device if device is not None
-                                                                             else f"cuda:{torch.cuda.current_device()}")
-        self._buffers(device)
-        D.all_reduce_sum(self.hist, group, kind="metric_all_reduce")
-        if self.binned:
-            D.all_reduce_sum(self.acc, group, kind="metric_all_reduce")
-            D.all_reduce_sum(self.tot, group, kind="metric_all_reduce")
-            return
-        if self._gathered:
+        device = self._all_reduce_counts(group, device)
+        if device is None or self.binned or self._gathered:
             return
         S, y = self._local(device)
         sizes = D.all_gather_rows(torch.tensor([S.shape[0]], dtype=torch.int64, device=device), group, kind="metric_all_gather")

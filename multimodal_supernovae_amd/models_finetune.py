@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import distributed as D
+from ._device_args import workspace
 from ._lib import check, lib, ptr, stream_ptr
 from .loss import _AllReduceSum
 from .models_multimodal import MLP
@@ -26,10 +27,6 @@ from .models_pretraining import masked_mse
 from .ops import _f32c
 
 _TOWER_ORDER = ("host_galaxy", "lightcurve", "spectral")      # LightCurveImageCLIP.forward's fixed order (img, lc, sp)
-
-
-def _ws(nbytes, device):
-    return torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=device)
 
 
 # ------------------------------------------------------------------------------------------- cross-entropy
@@ -61,7 +58,7 @@ class _CrossEntropy(torch.autograd.Function):
         pred = torch.empty(N, dtype=torch.int32, device=dev)
         out = torch.empty(3, dtype=torch.float32, device=dev)              # {loss, denominator, numerator}
         nb = L.msn_cross_entropy_workspace_bytes(N, C)
-        ws = _ws(nb, dev) if nb else None                                  # the shapes of training take one workgroup: no scratch
+        ws = workspace(nb, dev) if nb else None                            # the shapes of training take one workgroup: no scratch
         check(L.msn_cross_entropy_fwd(ptr(logits), logits.stride(0), ptr(target), ptr(weight), N, C, ptr(None), ptr(lse),
                                       ptr(pred), ptr(out), ptr(ws), nb, stream_ptr()), "msn_cross_entropy_fwd")
         if sharded:
@@ -164,6 +161,8 @@ class ClassificationMetrics:
               "msn_confusion_matrix")
 
     def all_reduce(self, group=None):
+        # NOTE: a rank that accumulated nothing skips the collective here and in RegressionMetrics (every rank of a validation
+        # epoch has rows); _device_args.EpochCounts enters it on every rank.  Kept apart: joining them changes behaviour.
         if self.cm is not None and D.world_size(group) > 1:
             D.all_reduce_sum(self.cm, group, kind="metric_all_reduce")
 
@@ -193,7 +192,7 @@ class RegressionMetrics:
         if self.sums is None or self.sums.device != pred.device:
             self.sums = torch.zeros(6, dtype=torch.float64, device=pred.device)
         nb = lib().msn_regression_stats_workspace_bytes(pred.numel())
-        ws = _ws(nb, pred.device) if nb else None
+        ws = workspace(nb, pred.device) if nb else None
         check(lib().msn_regression_stats(ptr(pred), ptr(target), pred.numel(), ptr(self.sums), ptr(ws), nb, stream_ptr()),
               "msn_regression_stats")
 

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._device_args import ld, rows_on_gpu, workspace
 from ._lib import check, lib, ptr, stream_ptr
 
 MAX_D = 1024            # the widths the contrastive kernels take
@@ -167,25 +168,6 @@ def logistic_objective(X, y, W, C=1.0, class_weight=None, fit_intercept=True):
 
 
 # ----------------------------------------------------------------------------------------------------- device halves
-def _embeddings(X, who):
-    _lib.require_gpu()
-    if not isinstance(X, torch.Tensor) or X.device.type != "cuda":
-        raise _lib.MsnHipError(f"{who}: embeddings must live on the GPU (got {getattr(X, 'device', type(X).__name__)}); "
-                               "there is no CPU path")
-    if X.dim() != 2 or X.dtype != torch.float32:
-        raise ValueError(f"{who}: embeddings must be float32 (N, D) (got {X.dtype} {tuple(X.shape)})")
-    X = X.detach()
-    if X.shape[0] == 0:
-        raise ValueError(f"{who}: no rows")
-    if (X.stride(1) != 1 and X.shape[1] > 1) or X.stride(0) < X.shape[1]:
-        X = X.contiguous()
-    return X
-
-
-def _ld(t):
-    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
-
-
 def _f32_on(a, device):
     """A host fp64 array as a fresh fp32 device tensor with canonical strides (a (1, D) numpy array may carry any row stride)."""
     t = torch.empty(a.shape, dtype=torch.float32, device=device)
@@ -193,14 +175,10 @@ def _f32_on(a, device):
     return t
 
 
-def _ws(nbytes, device):
-    return torch.empty(max(int(nbytes), 8) // 8 + 1, dtype=torch.float64, device=device)
-
-
 def probe_gram(X, Y=None, out=None, accumulate=False):
     """G = Z^T Z (fp64, (D + 1 + K)^2) for Z = [X | 1 | Y] in one call of msn_probe_gram; with `out` and accumulate=True the
     product is added to what `out` holds.  Enqueue only: no allocation beyond the scratch, no synchronisation."""
-    X = _embeddings(X, "probe_gram")
+    X = rows_on_gpu(X, "probe_gram", "embeddings")
     N, D = X.shape
     K = 0
     if Y is not None:
@@ -222,16 +200,16 @@ def probe_gram(X, Y=None, out=None, accumulate=False):
         raise ValueError(f"probe_gram: out must be a contiguous float64 ({M}, {M}) matrix on {X.device}")
     L = lib()
     nb = L.msn_probe_gram_workspace_bytes(N, D, K)
-    ws = _ws(nb, X.device)
-    check(L.msn_probe_gram(ptr(X), _ld(X), ptr(Y if K else None), _ld(Y) if K else 0, N, D, K, ptr(out), 1 if accumulate else 0,
-                           ptr(ws), ws.numel() * 8, stream_ptr()), "msn_probe_gram")
+    ws = workspace(nb, X.device)
+    check(L.msn_probe_gram(ptr(X), ld(X), ptr(Y if K else None), ld(Y) if K else 0, N, D, K, ptr(out), 1 if accumulate else 0,
+                           ptr(ws), ws.numel(), stream_ptr()), "msn_probe_gram")
     return out
 
 
 def logreg_loss_grad(X, y, W, class_weight=None, out=None):
     """out (1 + C (D + 1) doubles on the device) = {loss, gradient} of the unregularised multinomial logistic objective at
     W (C, D + 1) fp64 (msn_logreg_loss_grad).  Enqueue only."""
-    X = _embeddings(X, "logreg_loss_grad")
+    X = rows_on_gpu(X, "logreg_loss_grad", "embeddings")
     N, D = X.shape
     if W.dim() != 2 or W.shape[1] != D + 1 or W.dtype != torch.float64 or W.device != X.device or not W.is_contiguous():
         raise ValueError(f"logreg_loss_grad: W must be a contiguous float64 (C, {D + 1}) matrix on {X.device}")
@@ -246,8 +224,8 @@ def logreg_loss_grad(X, y, W, class_weight=None, out=None):
         out = torch.empty(1 + C * (D + 1), dtype=torch.float64, device=X.device)
     L = lib()
     nb = L.msn_logreg_workspace_bytes(N, D, C)
-    ws = _ws(nb, X.device)
-    check(L.msn_logreg_loss_grad(ptr(X), _ld(X), ptr(y), ptr(class_weight), N, D, C, ptr(W), ptr(out), ptr(ws), ws.numel() * 8,
+    ws = workspace(nb, X.device)
+    check(L.msn_logreg_loss_grad(ptr(X), ld(X), ptr(y), ptr(class_weight), N, D, C, ptr(W), ptr(out), ptr(ws), ws.numel(),
                                  stream_ptr()), "msn_logreg_loss_grad")
     return out
 
@@ -268,7 +246,7 @@ class LinearRegressionProbe:
         self._shape = self._w = self._b = None
 
     def partial_fit(self, X, Y):
-        X = _embeddings(X, "LinearRegressionProbe.partial_fit")
+        X = rows_on_gpu(X, "LinearRegressionProbe.partial_fit", "embeddings")
         if not isinstance(Y, torch.Tensor) or Y.device != X.device:
             raise _lib.MsnHipError("LinearRegressionProbe.partial_fit: targets must live on the GPU next to the embeddings; "
                                    "there is no CPU path")
@@ -302,7 +280,7 @@ class LinearRegressionProbe:
         if self._w is None:
             self.solve()
         from .functional import linear
-        X = _embeddings(X, "LinearRegressionProbe.predict")
+        X = rows_on_gpu(X, "LinearRegressionProbe.predict", "embeddings")
         with torch.no_grad():
             out = linear(X.contiguous(), self._w, self._b)
         return out[:, 0] if self._shape[2] else out
@@ -322,7 +300,7 @@ class LogisticRegressionProbe:
         self._w = self._b = None
 
     def fit(self, X, y):
-        X = _embeddings(X, "LogisticRegressionProbe.fit")
+        X = rows_on_gpu(X, "LogisticRegressionProbe.fit", "embeddings")
         if not isinstance(y, torch.Tensor) or y.device != X.device:
             raise _lib.MsnHipError("LogisticRegressionProbe.fit: targets must live on the GPU next to the embeddings; "
                                    "there is no CPU path")
@@ -365,7 +343,7 @@ class LogisticRegressionProbe:
         if self._w is None:
             raise ValueError("LogisticRegressionProbe: not fitted")
         from .functional import linear
-        X = _embeddings(X, "LogisticRegressionProbe.decision_function")
+        X = rows_on_gpu(X, "LogisticRegressionProbe.decision_function", "embeddings")
         with torch.no_grad():
             return linear(X.contiguous(), self._w, self._b)
 
@@ -472,9 +450,9 @@ def _knn_search_sq(Q, X, k, self_offset):
     idx = torch.empty((Nq, k), dtype=torch.int32, device=Q.device)
     dist2 = torch.empty((Nq, k), dtype=torch.float64, device=Q.device)
     L = lib()
-    ws = _ws(L.msn_knn_workspace_bytes(Nq, Nx, D, k), Q.device)
-    check(L.msn_knn_search(ptr(Q), _ld(Q), Nq, ptr(X), _ld(X), Nx, D, k, self_offset, ptr(idx), ptr(dist2), ptr(ws),
-                           ws.numel() * 8, stream_ptr()), "msn_knn_search")
+    ws = workspace(L.msn_knn_workspace_bytes(Nq, Nx, D, k), Q.device)
+    check(L.msn_knn_search(ptr(Q), ld(Q), Nq, ptr(X), ld(X), Nx, D, k, self_offset, ptr(idx), ptr(dist2), ptr(ws),
+                           ws.numel(), stream_ptr()), "msn_knn_search")
     return idx, dist2
 
 
@@ -496,8 +474,8 @@ def knn_search(Q, X, k, metric="euclidean", exclude_self=False, return_squared=F
     set (True = 0): query i never finds row i + o -- leave-one-out for Q = X[o : o + n].  Enqueue only."""
     _knn_metric(metric, "knn_search")
     same = Q is X
-    Q = _embeddings(Q, "knn_search")
-    X = Q if same else _embeddings(X, "knn_search")
+    Q = rows_on_gpu(Q, "knn_search", "embeddings")
+    X = Q if same else rows_on_gpu(X, "knn_search", "embeddings")
     if metric == "cosine":
         Q = _unit_rows(Q)
         X = Q if same else _unit_rows(X)
@@ -519,7 +497,7 @@ class _KNeighborsProbe:
         self._X = self._t = None
 
     def _fit_x(self, X):
-        X = _embeddings(X, f"{type(self).__name__}.fit")        # a reference: contiguous input is not copied
+        X = rows_on_gpu(X, f"{type(self).__name__}.fit", "embeddings")        # a reference: contiguous input is not copied
         if X.shape[1] > MAX_D:
             raise _lib.MsnHipError(f"{type(self).__name__}: D <= {MAX_D} (got {X.shape[1]})")
         self._X = _unit_rows(X) if self.metric == "cosine" else X
@@ -539,7 +517,7 @@ class _KNeighborsProbe:
             raise ValueError(f"{type(self).__name__}: not fitted")
         if X is None:
             return _knn_search_sq(self._X, self._X, k, 0)
-        Q = _embeddings(X, f"{type(self).__name__}")
+        Q = rows_on_gpu(X, f"{type(self).__name__}", "embeddings")
         return _knn_search_sq(_unit_rows(Q) if self.metric == "cosine" else Q, self._X, k, -1)
 
     def kneighbors(self, X=None, n_neighbors=None, return_distance=True):
@@ -581,7 +559,7 @@ class KNeighborsRegressorProbe(_KNeighborsProbe):
         Nq, k = idx.shape
         K = self._t.shape[1]
         out = torch.empty((Nq, K), dtype=torch.float32, device=idx.device)
-        check(lib().msn_knn_predict_regression(ptr(idx), ptr(d2), Nq, k, ptr(self._t), _ld(self._t), K, self._wcode, ptr(out), K,
+        check(lib().msn_knn_predict_regression(ptr(idx), ptr(d2), Nq, k, ptr(self._t), ld(self._t), K, self._wcode, ptr(out), K,
                                                stream_ptr()), "msn_knn_predict_regression")
         return out[:, 0] if self._flat else out
 
