@@ -962,6 +962,38 @@ int msn_knn_predict_classes(const int* idx, const double* dist2, int64_t Nq, int
                             int* classes, float* proba_or_null, msn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Pair sums over embeddings (embedding_metrics.py; csrc/embedding_metrics.hip): what alignment and uniformity are made of.
+ *
+ * Potential: X (Nx, D) and Y (Ny, D) fp32, row strides ldx, ldy >= D, 4-byte aligned (every load is a 4-byte load: the bits do
+ *   not depend on stride or alignment).  out (2 doubles) receives out[0] = sum_S exp(-t d2_ij) and out[1] = sum_S d2_ij with
+ *   d2_ij = max(0, |x_i|^2 + |y_j|^2 - 2 x_i.y_j) in fp64, over the pair set S of `mode`:
+ *     0  all Nx Ny pairs;   1  the same without i == j (Nx == Ny);   2  the unordered pairs i < j within X (Y == NULL, Ny == 0,
+ *     Nx >= 2): only the tile pairs on or above the diagonal are computed.
+ *   d2 is formed as msn_knn_search forms it: 64 x 64 tiles of dot products on the fp64 matrix instruction, norms by fma chains
+ *   over the same staged columns, D never split and padded with zeros, so every d2 depends on the two rows and D alone.  exp is
+ *   the device library's fp64 exp.  A row past Nx / Ny is never a pair.  The Nx x Ny matrix is never written.
+ *   Sums: tile pairs are numbered row by row; workgroup b owns the pairs b per .. (b + 1) per - 1, per = ceil(pairs / 1024),
+ *   blocks = ceil(pairs / per), pairs = ceil(Nx / 64) ceil(Ny / 64) (mode 2: T (T + 1) / 2, T = ceil(Nx / 64)).  A lane adds its
+ *   16 pairs per tile in tile order, the workgroup's 256 lanes are reduced (xor tree, then the four waves in order) into one
+ *   partial pair in `ws` (16 blocks bytes), and one finishing workgroup adds partial u, u + 256, ... in thread u and reduces alike.
+ *     A(Nx, Ny, mode) = 16 per + 9 + ceil(blocks / 256) + 9
+ *   is the largest number of additions any single term passes through on its way to out: every term is non-negative, so
+ *   out[0] and out[1] carry a relative error of at most A 2^-53 from the summation (first order).
+ *   Two launches, no atomics, no fills: the same bits on every run.  Non-finite inputs are not checked and propagate.
+ *   MSN_ERR_SHAPE before any launch: D outside 1..1024, Nx < 1, Ny < 1 in modes 0 / 1, Nx != Ny in mode 1, Nx < 2 or Y != NULL
+ *   or Ny != 0 in mode 2, Nx or Ny >= 2^31, t not finite or <= 0, an unknown mode, a workspace that is too small.
+ * Alignment: d2_i = sum_c (x_ic - y_ic)^2 by fma in column order (the direct form of the kNN finish: non-negative, exactly 0 for
+ *   identical rows); out[0] = sum_i d2_i, out[1] = sum_i sqrt(d2_i); d2_rows_or_null, where given, receives the N values.
+ *   Thread u of workgroup b adds the rows (b + k blocks) 256 + u, k = 0, 1, ..., blocks = min(ceil(N / 256), 1024); then the same
+ *   two reductions.  1 <= D <= 1024, 1 <= N < 2^31, else MSN_ERR_SHAPE before any launch. */
+size_t msn_pair_potential_workspace_bytes(int64_t Nx, int64_t Ny, int D, int mode);
+int msn_pair_potential(const float* X, int64_t ldx, int64_t Nx, const float* Y, int64_t ldy, int64_t Ny, int D, double t, int mode,
+                       double* out, void* ws, size_t ws_bytes, msn_stream_t stream);
+size_t msn_pair_alignment_workspace_bytes(int64_t N, int D);
+int msn_pair_alignment(const float* X, int64_t ldx, const float* Y, int64_t ldy, int64_t N, int D, double* out,
+                       double* d2_rows_or_null, void* ws, size_t ws_bytes, msn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Threshold-free classification metrics (metrics.py; csrc/rank_metrics.hip): one-vs-rest AUROC, average precision, binned
  * ROC / precision-recall curves and top-k accuracy from integer counts.  Shared by the four entry points: S (N, C) fp32
  * scores with row stride ld >= C, 4-byte aligned (every load of S is a 4-byte load: the bits do not depend on stride or

@@ -147,6 +147,10 @@ SIGNATURES = {
     "msn_knn_search": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_int, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "msn_knn_predict_regression": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_int, c_ptr, c_i64, c_ptr]),
     "msn_knn_predict_classes": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr]),
+    "msn_pair_potential_workspace_bytes": (c_size, [c_i64, c_i64, c_int, c_int]),
+    "msn_pair_potential": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_int, c_f64, c_int, c_ptr, c_ptr, c_size, c_ptr]),
+    "msn_pair_alignment_workspace_bytes": (c_size, [c_i64, c_int]),
+    "msn_pair_alignment": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "msn_rank_counts_workspace_bytes": (c_size, [c_i64, c_int]),
     "msn_rank_counts": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "msn_threshold_counts": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),

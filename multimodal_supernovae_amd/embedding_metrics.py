@@ -1,0 +1,343 @@
+"""What the contrastive embedding itself looks like: alignment and uniformity (Wang & Isola 2020), the modality gap (Liang et
+al. 2022), effective rank / RankMe (Garrido et al. 2023), and recall@k, MRR and median rank in both directions.
+
+    pair_potential, pair_alignment
+                      the two pair sums in fp64 on the device (csrc/embedding_metrics.hip: msn_pair_potential sums
+                      exp(-t d^2) and d^2 over all pairs without writing the N x N matrix; msn_pair_alignment sums d^2 and d
+                      over partner rows).  Enqueue only.
+    uniformity, cross_uniformity, alignment
+                      the figures of one call: one host copy each
+    covariance_spectrum, effective_rank, participation_ratio, modality_gap
+                      host halves over probes.probe_gram's matrix, numpy fp64: importable and testable without a GPU
+    recall_at_k, mean_reciprocal_rank, median_rank, retrieval_metrics
+                      over the integer ranks of utils.retrieval_ranks
+    EmbeddingMetrics  reset / update(e1, e2) / compute() over a validation epoch
+    pair_potential_reference, pair_alignment_reference
+                      numpy longdouble restatements of the two kernels, importable without a GPU
+
+No scipy or scikit-learn at run time.  Nothing here issues a collective: with several ranks, gather the embeddings before the
+call, as for a kNN probe.  Not built: CKA, gradients of the alignment and uniformity losses, collectives, sample weights,
+D > 1024.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from ._device_args import ld, rows_on_gpu, workspace
+from ._lib import check, lib, ptr, stream_ptr
+
+MAX_D = 1024
+_MODES = {"all": 0, "offdiag": 1, "within": 2}
+
+
+# ------------------------------------------------------------------------------------------------- host: the spectrum
+def _gram_parts(G, D, who):
+    G = np.asarray(G, dtype=np.float64)
+    D = int(D)
+    if D < 1 or G.ndim != 2 or G.shape[0] != G.shape[1] or G.shape[0] < D + 1:
+        raise ValueError(f"{who}: G must be a probe_gram matrix of at least ({D + 1}, {D + 1}) for D = {D} (got {G.shape})")
+    n = G[D, D]
+    if n < 1:
+        raise ValueError(f"{who}: the Gram matrix holds no rows")
+    return G[:D, :D], G[:D, D], n
+
+
+def covariance_spectrum(G, D, center=True):
+    """Singular values, descending, of the centred (N, D) embedding matrix -- with center=False of the matrix itself -- from
+    probes.probe_gram's G: sqrt(max(lambda, 0)) over eigvalsh(X^T X - s s^T / n), s the column sums.  What a Gram matrix costs:
+    a singular value below sqrt(2^-52) of the largest is noise (the tests measure 1.3e-6 on rank-3 data)."""
+    A, s, n = _gram_parts(G, D, "covariance_spectrum")
+    if center:
+        A = A - np.outer(s, s) / n
+    lam = np.linalg.eigvalsh((A + A.T) / 2)
+    return np.sqrt(np.maximum(lam, 0.0))[::-1].copy()
+
+
+def effective_rank(s, eps=1e-7):
+    """exp(-sum p log p) with p = s / sum s + eps over singular values s: RankMe (Garrido et al. 2023) for the spectrum of the
+    uncentred matrix (covariance_spectrum(..., center=False))."""
+    s = np.asarray(s, dtype=np.float64)
+    p = s / s.sum() + eps
+    return float(np.exp(-np.sum(p * np.log(p))))
+
+
+def participation_ratio(s):
+    """(sum s^2)^2 / sum s^4 over singular values s: the participation ratio of the covariance eigenvalues s^2."""
+    s2 = np.asarray(s, dtype=np.float64) ** 2
+    return float(s2.sum() ** 2 / np.sum(s2 ** 2))
+
+
+def modality_gap(Gx, Gy, D):
+    """|mean(X) - mean(Y)|_2 (Liang et al. 2022) from the column sums of the two sets' probe_gram matrices."""
+    _, sx, nx = _gram_parts(Gx, D, "modality_gap")
+    _, sy, ny = _gram_parts(Gy, D, "modality_gap")
+    return float(np.linalg.norm(sx / nx - sy / ny))
+
+
+# ---------------------------------------------------------------------------------------------------- host: retrieval
+def _ranks(ranks, who):
+    r = np.asarray(ranks.detach().cpu() if isinstance(ranks, torch.Tensor) else ranks)
+    if r.ndim != 1 or len(r) == 0 or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError(f"{who}: ranks must be a non-empty vector of integers (got {r.dtype} {r.shape})")
+    return r.astype(np.int64)
+
+
+def recall_at_k(ranks, k):
+    """Share of the rows whose partner is among the k most similar: rank < k, rank = the number of rows strictly more similar
+    than the partner (utils.retrieval_ranks)."""
+    if int(k) < 1:
+        raise ValueError(f"recall_at_k: k must be at least 1 (got {k})")
+    r = _ranks(ranks, "recall_at_k")
+    return float(np.count_nonzero(r < int(k)) / len(r))
+
+
+def mean_reciprocal_rank(ranks):
+    """Mean of 1 / (rank + 1)."""
+    return float(np.mean(1.0 / (_ranks(ranks, "mean_reciprocal_rank") + 1.0)))
+
+
+def median_rank(ranks):
+    """Median of the 1-based ranks rank + 1 (the mean of the two middle values for an even count)."""
+    return float(np.median(_ranks(ranks, "median_rank") + 1))
+
+
+def _top_k(top_k):
+    ks = tuple(int(k) for k in top_k)
+    if not ks or min(ks) < 1:
+        raise ValueError(f"top_k must name at least one k >= 1 (got {top_k!r})")
+    return ks
+
+
+def _retrieval_from_ranks(r_a2b, r_b2a, ks):
+    out = {}
+    for sfx, r in (("_a2b", r_a2b), ("_b2a", r_b2a)):
+        for k in ks:
+            out[f"recall{k}{sfx}"] = recall_at_k(r, k)
+        out[f"mrr{sfx}"] = mean_reciprocal_rank(r)
+        out[f"medr{sfx}"] = median_rank(r)
+    for key in [f"recall{k}" for k in ks] + ["mrr", "medr"]:
+        out[key] = 0.5 * (out[key + "_a2b"] + out[key + "_b2a"])
+    return out
+
+
+def retrieval_metrics(e1, e2, top_k=(1, 5, 10)):
+    """recall{k}, mrr and medr of a CLIP-style retrieval over (N, D) partner sets, by cosine similarity: `_a2b` queries with
+    the rows of e1 and ranks the rows of e2 (utils.retrieval_ranks(e2, e1)), `_b2a` the other way round; the keys without a
+    suffix are the means of the two directions.  Two host copies of N ints."""
+    from .utils import retrieval_ranks
+    ks = _top_k(top_k)
+    return _retrieval_from_ranks(retrieval_ranks(e2, e1).cpu().numpy(), retrieval_ranks(e1, e2).cpu().numpy(), ks)
+
+
+# -------------------------------------------------------------------------------------------- host: the kernels restated
+def pair_potential_reference(X, Y=None, t=2.0, pairs="within"):
+    """numpy longdouble restatement of msn_pair_potential: (sum exp(-t d2), sum d2) over the pair set, d2 in the direct form
+    sum_c (x_c - y_c)^2."""
+    if pairs not in _MODES:
+        raise ValueError(f"pair_potential_reference: pairs must be 'within', 'all' or 'offdiag' (got {pairs!r})")
+    X = np.asarray(X, dtype=np.float32).astype(np.longdouble)
+    Y = X if Y is None else np.asarray(Y, dtype=np.float32).astype(np.longdouble)
+    if pairs == "within" and Y is not X:
+        raise ValueError("pair_potential_reference: 'within' pairs the rows of X with each other")
+    if X.ndim != 2 or Y.ndim != 2 or X.shape[1] != Y.shape[1] or (pairs == "offdiag" and len(X) != len(Y)):
+        raise ValueError(f"pair_potential_reference: X (Nx, D) and Y (Ny, D) needed (got {X.shape} and {Y.shape})")
+    t = np.longdouble(t)
+    se = sd = np.longdouble(0)
+    for i, x in enumerate(X):
+        d2 = ((Y - x) ** 2).sum(axis=1)
+        if pairs == "within":
+            d2 = d2[i + 1:]
+        elif pairs == "offdiag":
+            d2 = np.delete(d2, i)
+        se += np.exp(-t * d2).sum()
+        sd += d2.sum()
+    return se, sd
+
+
+def pair_alignment_reference(X, Y):
+    """numpy longdouble restatement of msn_pair_alignment: (sum d2, sum sqrt(d2), d2 per row)."""
+    X = np.asarray(X, dtype=np.float32).astype(np.longdouble)
+    Y = np.asarray(Y, dtype=np.float32).astype(np.longdouble)
+    if X.ndim != 2 or X.shape != Y.shape:
+        raise ValueError(f"pair_alignment_reference: two (N, D) sets of equal shape needed (got {X.shape} and {Y.shape})")
+    d2 = ((X - Y) ** 2).sum(axis=1)
+    return d2.sum(), np.sqrt(d2).sum(), d2
+
+
+# ------------------------------------------------------------------------------------------------------ device halves
+def _out2(out, device, who):
+    if out is None:
+        return torch.empty(2, dtype=torch.float64, device=device)
+    if out.shape != (2,) or out.dtype != torch.float64 or out.device != device or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous float64 (2,) tensor on {device}")
+    return out
+
+
+def pair_potential(X, Y=None, t=2.0, pairs="within", out=None):
+    """out (2 doubles on the device) = (sum exp(-t d2_ij), sum d2_ij) over the pairs of rows of X (Nx, D) and Y (Ny, D):
+    "within" the unordered pairs i < j of X (Y = None), "all" every (i, j), "offdiag" every (i, j) but i == j (Nx == Ny).
+    d2 = max(0, |x|^2 + |y|^2 - 2 x.y) in fp64 (msn_pair_potential).  Enqueue only."""
+    if pairs not in _MODES:
+        raise ValueError(f"pair_potential: pairs must be 'within', 'all' or 'offdiag' (got {pairs!r})")
+    X = rows_on_gpu(X, "pair_potential", "embeddings")
+    if pairs == "within":
+        if Y is not None:
+            raise ValueError("pair_potential: 'within' pairs the rows of X with each other; pass no Y")
+        Ny = 0
+    else:
+        if Y is None:
+            raise ValueError(f"pair_potential: pairs={pairs!r} needs Y")
+        Y = rows_on_gpu(Y, "pair_potential", "embeddings")
+        if Y.device != X.device:
+            raise _lib.MsnHipError("pair_potential: X and Y must live on the same GPU")
+        if Y.shape[1] != X.shape[1]:
+            raise ValueError(f"pair_potential: X has {X.shape[1]} columns, Y {Y.shape[1]}")
+        Ny = Y.shape[0]
+    Nx, D = X.shape
+    out = _out2(out, X.device, "pair_potential")
+    L = lib()
+    mode = _MODES[pairs]
+    ws = workspace(L.msn_pair_potential_workspace_bytes(Nx, Ny, D, mode), X.device)
+    check(L.msn_pair_potential(ptr(X), ld(X), Nx, ptr(Y), ld(Y) if Y is not None else 0, Ny, D, float(t), mode, ptr(out),
+                               ptr(ws), ws.numel(), stream_ptr()), "msn_pair_potential")
+    return out
+
+
+def pair_alignment(X, Y, out=None, rows=False):
+    """out (2 doubles on the device) = (sum_i d2_i, sum_i sqrt(d2_i)) with d2_i = sum_c (x_ic - y_ic)^2 over partner rows
+    (msn_pair_alignment); with rows=True returns (out, d2 (N) fp64).  Enqueue only."""
+    X = rows_on_gpu(X, "pair_alignment", "embeddings")
+    Y = rows_on_gpu(Y, "pair_alignment", "embeddings")
+    if Y.device != X.device:
+        raise _lib.MsnHipError("pair_alignment: X and Y must live on the same GPU")
+    if X.shape != Y.shape:
+        raise ValueError(f"pair_alignment: two (N, D) sets of equal shape needed (got {tuple(X.shape)} and {tuple(Y.shape)})")
+    N, D = X.shape
+    out = _out2(out, X.device, "pair_alignment")
+    d2 = torch.empty(N, dtype=torch.float64, device=X.device) if rows else None
+    L = lib()
+    ws = workspace(L.msn_pair_alignment_workspace_bytes(N, D), X.device)
+    check(L.msn_pair_alignment(ptr(X), ld(X), ptr(Y), ld(Y), N, D, ptr(out), ptr(d2), ptr(ws), ws.numel(), stream_ptr()),
+          "msn_pair_alignment")
+    return (out, d2) if rows else out
+
+
+def _unit_rows(X, who):
+    """L2-normalised rows (ops.l2norm_fwd, which takes D a multiple of 4: the rule of the kNN probes' cosine metric)."""
+    from . import ops
+    X = rows_on_gpu(X, who, "embeddings")
+    if X.shape[1] % 4 or X.shape[1] > MAX_D:
+        raise _lib.MsnHipError(f"{who}: normalize=True needs D a multiple of 4, at most {MAX_D} (got {X.shape[1]}); "
+                               "pass unit rows and normalize=False otherwise")
+    return ops.l2norm_fwd(X.contiguous())[0]
+
+
+def _log_mean(value, count):
+    return float(np.log(value / count)) if value > 0 else float("-inf")
+
+
+def uniformity(X, t=2.0, normalize=True):
+    """log of the mean of exp(-t |x_i - x_j|^2) over the N (N - 1) / 2 pairs i < j (Wang & Isola 2020): lower is more uniform."""
+    X = _unit_rows(X, "uniformity") if normalize else X
+    N = X.shape[0]
+    return _log_mean(float(pair_potential(X, None, t, "within").cpu()[0]), N * (N - 1) / 2)
+
+
+def cross_uniformity(X, Y, t=2.0, normalize=True, pairs="offdiag"):
+    """The same over pairs of a row of X and a row of Y: "offdiag" leaves the partners i == j out, "all" keeps them."""
+    if pairs not in ("offdiag", "all"):
+        raise ValueError(f"cross_uniformity: pairs must be 'offdiag' or 'all' (got {pairs!r})")
+    if normalize:
+        X, Y = _unit_rows(X, "cross_uniformity"), _unit_rows(Y, "cross_uniformity")
+    out = float(pair_potential(X, Y, t, pairs).cpu()[0])
+    Nx, Ny = X.shape[0], Y.shape[0]
+    return _log_mean(out, Nx * Ny - (Nx if pairs == "offdiag" else 0))
+
+
+def alignment(X, Y, alpha=2, normalize=True):
+    """Mean over partner rows of |x_i - y_i|^alpha, alpha = 2 or 1 (Wang & Isola 2020): lower is better aligned."""
+    if alpha not in (1, 2):
+        raise ValueError(f"alignment: alpha must be 2 or 1 (got {alpha!r})")
+    if normalize:
+        X, Y = _unit_rows(X, "alignment"), _unit_rows(Y, "alignment")
+    out = pair_alignment(X, Y).cpu()
+    return float(out[0 if alpha == 2 else 1]) / X.shape[0]
+
+
+class EmbeddingMetrics:
+    """The embedding figures of a validation epoch over two partner sets: update(e1, e2) adds a batch to two fp64 Gram
+    matrices on the device (probes.probe_gram, accumulate=True) and keeps a reference to it; compute() concatenates, runs the
+    pair kernels and the retrieval ranks, makes one host copy and returns
+
+        n, alignment, uniformity_a, uniformity_b, uniformity (their mean), uniformity_cross (partners left out),
+        modality_gap, erank_a, erank_b, erank (the smaller), and retrieval_metrics' keys.
+
+    normalize: L2-normalise the rows first (D a multiple of 4).  center: take the spectra of the centred sets; center=False
+    is RankMe.  No collective is issued: with several ranks the caller gathers the embeddings first, as for a kNN probe."""
+
+    def __init__(self, t=2.0, top_k=(1, 5, 10), normalize=True, center=True):
+        if not (t > 0 and np.isfinite(t)):
+            raise ValueError(f"EmbeddingMetrics: t must be finite and positive (got {t})")
+        self.t, self.top_k = float(t), _top_k(top_k)
+        self.normalize, self.center = bool(normalize), bool(center)
+        self.reset()
+
+    def reset(self):
+        self.gram_a = self.gram_b = None          # (D + 1)^2 fp64 on the device
+        self._a, self._b = [], []
+
+    def update(self, e1, e2):
+        who = "EmbeddingMetrics.update"
+        a = _unit_rows(e1, who) if self.normalize else rows_on_gpu(e1, who, "embeddings")
+        b = _unit_rows(e2, who) if self.normalize else rows_on_gpu(e2, who, "embeddings")
+        if a.shape != b.shape or a.device != b.device:
+            raise ValueError(f"{who}: two (N, D) sets of equal shape on one GPU needed (got {tuple(a.shape)} and {tuple(b.shape)})")
+        if self._a and a.shape[1] != self._a[0].shape[1]:
+            raise ValueError(f"{who}: D changed from {self._a[0].shape[1]} to {a.shape[1]}")
+        if a.shape[1] > MAX_D:
+            raise _lib.MsnHipError(f"{who}: D <= {MAX_D} (got {a.shape[1]})")
+        from .probes import probe_gram
+        self.gram_a = probe_gram(a, out=self.gram_a, accumulate=self.gram_a is not None)
+        self.gram_b = probe_gram(b, out=self.gram_b, accumulate=self.gram_b is not None)
+        self._a.append(a)
+        self._b.append(b)
+        return self
+
+    def compute(self):
+        if not self._a:
+            raise ValueError("EmbeddingMetrics.compute: nothing added yet")
+        from .utils import retrieval_ranks
+        A = self._a[0] if len(self._a) == 1 else torch.cat(self._a, dim=0)
+        B = self._b[0] if len(self._b) == 1 else torch.cat(self._b, dim=0)
+        N, D = A.shape
+        M = (D + 1) * (D + 1)
+        # one buffer, one copy: four pair results, the two Gram matrices, the two rank vectors (exact as doubles)
+        buf = torch.empty(8 + 2 * M + 2 * N, dtype=torch.float64, device=A.device)
+        pair_alignment(A, B, out=buf[0:2])
+        if N >= 2:
+            pair_potential(A, None, self.t, "within", out=buf[2:4])
+            pair_potential(B, None, self.t, "within", out=buf[4:6])
+            pair_potential(A, B, self.t, "offdiag", out=buf[6:8])
+        else:
+            buf[2:8].fill_(float("nan"))
+        buf[8:8 + M].copy_(self.gram_a.reshape(-1))
+        buf[8 + M:8 + 2 * M].copy_(self.gram_b.reshape(-1))
+        buf[8 + 2 * M:8 + 2 * M + N].copy_(retrieval_ranks(B, A))          # a -> b
+        buf[8 + 2 * M + N:].copy_(retrieval_ranks(A, B))                   # b -> a
+        h = buf.cpu().numpy()
+        Ga, Gb = h[8:8 + M].reshape(D + 1, D + 1), h[8 + M:8 + 2 * M].reshape(D + 1, D + 1)
+        r_a2b, r_b2a = h[8 + 2 * M:8 + 2 * M + N].astype(np.int64), h[8 + 2 * M + N:].astype(np.int64)
+        within, cross = N * (N - 1) / 2, N * (N - 1)
+        out = {"n": N, "alignment": float(h[0]) / N}
+        if N >= 2:
+            out["uniformity_a"], out["uniformity_b"] = _log_mean(h[2], within), _log_mean(h[4], within)
+            out["uniformity_cross"] = _log_mean(h[6], cross)
+        else:
+            out["uniformity_a"] = out["uniformity_b"] = out["uniformity_cross"] = float("nan")
+        out["uniformity"] = 0.5 * (out["uniformity_a"] + out["uniformity_b"])
+        out["modality_gap"] = modality_gap(Ga, Gb, D)
+        out["erank_a"] = effective_rank(covariance_spectrum(Ga, D, self.center))
+        out["erank_b"] = effective_rank(covariance_spectrum(Gb, D, self.center))
+        out["erank"] = min(out["erank_a"], out["erank_b"])
+        out.update(_retrieval_from_ranks(r_a2b, r_b2a, self.top_k))
+        return out

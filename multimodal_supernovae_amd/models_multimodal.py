@@ -112,7 +112,8 @@ class LightCurveImageCLIP(nn.Module):
                  conv_kwargs: Optional[Dict] = None, meta_kwargs: Optional[Dict] = None,
                  combinations: List[str] = ("host_galaxy", "spectral"), optimizer_kwargs: Optional[Dict] = None,
                  lr: float = 1e-4, loss: str = "sigmoid", regression: bool = False, classification: bool = False,
-                 n_classes: int = 5, global_negatives: bool = True, optimizer: str = "radam"):
+                 n_classes: int = 5, global_negatives: bool = True, optimizer: str = "radam",
+                 embedding_metrics: bool = False):
         super().__init__()
         if regression or classification:
             raise NotImplementedError("this class is the contrastive model; the supervised regression / classification "
@@ -147,6 +148,7 @@ class LightCurveImageCLIP(nn.Module):
             meta_kwargs.setdefault("dropout", 0.0)
             self.meta_encoder = MLP(output_dim=enc_dim, **meta_kwargs)
         self.loss = loss
+        self.embedding_metrics = bool(embedding_metrics)      # also log alignment, uniformity, gap, rank and recall@1 per pair
         self.embs_list = None
         self.logged = {}
 
@@ -264,11 +266,23 @@ class LightCurveImageCLIP(nn.Module):
         embs = [torch.cat(e, dim=0) for e in self.embs_list]
         if len(embs) == 2:
             self.log("AUC_val", get_AUC(embs[0], embs[1]), on_epoch=True, on_step=False, prog_bar=True, logger=True)
+            self._log_embedding_metrics(embs[0], embs[1], "")
         else:
             count = 1
             for i in range(len(embs) - 1):
                 for j in range(i + 1, len(embs)):
                     self.log(f"AUC_val{count}", get_AUC(embs[i], embs[j]), on_epoch=True, on_step=False, prog_bar=True,
                              logger=True)
+                    self._log_embedding_metrics(embs[i], embs[j], str(count))
                     count += 1
         self.embs_list = None
+
+    def _log_embedding_metrics(self, e1, e2, suffix):
+        """embedding_metrics=True: align_val, uniform_val, gap_val, erank_val and recall1_val next to AUC_val, same suffix."""
+        if not self.embedding_metrics:
+            return
+        from .embedding_metrics import EmbeddingMetrics
+        m = EmbeddingMetrics().update(e1, e2).compute()
+        for key, name in (("align_val", "alignment"), ("uniform_val", "uniformity"), ("gap_val", "modality_gap"),
+                          ("erank_val", "erank"), ("recall1_val", "recall1")):
+            self.log(f"{key}{suffix}", m[name], on_epoch=True, on_step=False, prog_bar=True, logger=True)
