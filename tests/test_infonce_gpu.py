@@ -1,6 +1,7 @@
 """GPU parity of the fused InfoNCE kernels (through the C-ABI) against the oracle, the golden
 vectors from the reference, and size-independent properties at the BASELINE sizes.
-Tolerance: 1e-3 relative (north star); in practice the fp32 kernels sit near 1e-5."""
+Tolerance: 1e-3 relative (north star); in practice the fp32 kernels sit near 1e-5 -- tests/test_infonce_pinned_gpu.py holds them to
+bounds derived from their rounding steps.  Ranks follow the margin rule of tests/infonce_refs.py (rank_rule)."""
 import math
 
 import pytest
@@ -265,10 +266,13 @@ def test_retrieval_auc_matches_reference_golden():
 @pytest.mark.parametrize("n,d", [(1000, 128), (4096, 128), (33, 8), (500, 100)])
 def test_retrieval_ranks_against_oracle(n, d):
     from multimodal_supernovae_amd.utils import retrieval_ranks
+    from infonce_refs import rank_rule
     from oracle.clip import roc_data
     g = torch.Generator().manual_seed(n)
     e1 = torch.randn(n, d, generator=g)
     e2 = e1 + 2.0 * torch.randn(n, d, generator=g)
-    got = retrieval_ranks(e1.cuda(), e2.cuda()).cpu().numpy()
+    got = retrieval_ranks(e1.cuda(), e2.cuda()).cpu()
     _, _, ref = roc_data(e1.double(), e2.double())
-    assert (abs(got - ref) <= 1).all() and (got != ref).mean() < 0.01      # fp32 vs fp64 near-ties only
+    # equal wherever the fp64 margin of the partner's score exceeds the derived score bound; the rows left out are counted
+    wrong, undecided, rows = rank_rule(got, e1, e2, normalised=True, ref=ref)
+    assert wrong == 0 and undecided <= 0.01 * rows, (wrong, undecided)
