@@ -668,8 +668,10 @@ int msn_sgd_step_dev(const void* table, int n_tensors, int64_t max_numel, void* 
  * Layer-wise adaptive optimizers, LAMB and LARS (csrc/optim_layerwise.hip): per tensor a trust ratio from the 2-norms of the
  * whole tensor, the parameter's taken BEFORE the update.  One call = three multi-tensor launches over the table (fp32, n_tensors
  * 1 .. 65535, max_numel >= every numel): moments + per-block fp64 partial sums, one block per tensor that adds them in a fixed
- * order and writes the ratio, the update.  Blocks per tensor: ceil(max_numel / 4096), at most min(1024, max(32, 8192 /
- * n_tensors)); a larger tensor is covered in several passes.
+ * order and writes the ratio, the update.
+ * The multi-tensor launch rule (csrc/multi_tensor.h), shared by these steps, gradient clipping, gradient accumulation and weight
+ * averaging below: grid y = tensor, grid x = blocks per tensor = ceil(max_numel / 4096), at most min(1024, max(32, 8192 /
+ * n_tensors)) and at least 1; a block covers 4096 elements per pass and a larger tensor is covered in several passes.
  *   ws:    DEVICE scratch, 8-byte aligned, of msn_layerwise_workspace_bytes(n_tensors, max_numel) bytes or more.  The size
  *          never shrinks with more tensors or larger ones, so scratch sized for a param group serves any subset of it.
  *   ratio: n_tensors DEVICE floats: the trust ratios in table order, written by the second launch, read by the third and left
@@ -720,10 +722,11 @@ int msn_lars_step_dev(const void* table, int n_tensors, int64_t max_numel, void*
  * Gradient clipping: torch.nn.utils.clip_grad_norm_ / clip_grad_value_ as pl.Trainer(gradient_clip_val=...,
  * gradient_clip_algorithm="norm" | "value") calls them after the gradient all-reduce and before optimizer.step().
  * table: DEVICE array of n_tensors (1 .. 65535) records of two 64-bit words {g*, numel} (fp32 gradients, in place);
- * max_numel >= every numel of the table.  One launch per pass for the whole model.
+ * max_numel >= every numel of the table.  One launch per pass for the whole model, by the multi-tensor launch rule above.
  *   msn_grad_norm: total_norm[0] = ||g||_p over all tensors (norm_type 1, 2 or INFINITY; NaN propagates) and
  *     coef[0] = min(max_norm / (total_norm + 1e-6), 1) (a NaN stays NaN), both DEVICE floats.  Per-block partials in fp64
- *     go to `ws` (msn_grad_norm_workspace_bytes) and one block sums them in a fixed order: bitwise reproducible.
+ *     go to `ws` (msn_grad_norm_workspace_bytes: one double per block of the rule) and one block sums them in a fixed
+ *     order: bitwise reproducible.
  *   msn_grad_scale: g *= coef[0] (the device-resident coefficient of msn_grad_norm).
  *   msn_grad_clamp: g = clamp(g, -clip_value, clip_value), NaN kept. */
 size_t msn_grad_norm_workspace_bytes(int n_tensors, int64_t max_numel);
@@ -736,7 +739,8 @@ int msn_grad_clamp(const void* table, int n_tensors, int64_t max_numel, float cl
  * Gradient accumulation over micro-batches, pl.Trainer(accumulate_grad_batches=k): one launch per micro-batch for the whole
  * model in place of autograd's one add per parameter.
  * table: DEVICE array of n_tensors (1 .. 65535) records of four 64-bit words {dst*, acc*, g*, numel} (fp32);
- * max_numel >= every numel of the table.  Per element dst = g (store: the first micro-batch of a window) or dst = acc + g
+ * max_numel >= every numel of the table (the multi-tensor launch rule).  Per element dst = g (store: the first micro-batch
+ * of a window) or dst = acc + g
  * (add: one fp32 add, bitwise defined; NaN / inf as the add has them).  dst may be acc, g, or a third buffer.  A record whose
  * acc is NULL is stored in either mode; a store with dst == g moves nothing.
  * add: 0 = store, 1 = add.  add_dev: NULL, or a DEVICE int that overrides `add` (non-zero = add) -- a step recorded once in
@@ -748,7 +752,7 @@ int msn_grad_accumulate(const void* table, int n_tensors, int64_t max_numel, int
  * Weight averaging over training (Lightning's WeightAveraging / StochasticWeightAveraging, torch's AveragedModel): one launch
  * per optimizer step for every averaged tensor.
  * table: DEVICE array of n_tensors (1 .. 65535) records of three 64-bit words {avg*, p*, numel} (fp32);
- * max_numel >= every numel of the table.  state: two DEVICE 64-bit words {n_averaged, active}.
+ * max_numel >= every numel of the table (the multi-tensor launch rule).  state: two DEVICE 64-bit words {n_averaged, active}.
  *   active == 0: the launch changes nothing, neither the averages nor n_averaged;
  *   n_averaged == 0: avg = p, a copy of the bits;
  *   otherwise d = p - avg, avg = fmaf(w, d, avg), one rounding each, with

@@ -1,7 +1,7 @@
 // Gradient clipping by norm or by value (torch.nn.utils.clip_grad_norm_ / clip_grad_value_, as pl.Trainer(gradient_clip_val=...,
 // gradient_clip_algorithm=...) calls them between the gradient all-reduce and optimizer.step()).
-// HBM-bound multi-tensor launches through a device table of per-tensor descriptors {g*, numel} (blockIdx.y = tensor), the
-// idiom of the RAdam step (optim_steps.hip): a float4 path when a gradient is 16-byte aligned, a scalar tail otherwise.
+// HBM-bound multi-tensor launches through a device table of per-tensor descriptors {g*, numel} (blockIdx.y = tensor) with the
+// geometry and the pass loop of multi_tensor.h: a float4 path when a gradient is 16-byte aligned, a scalar tail otherwise.
 //   norm:  per-block partials in fp64 into caller-owned scratch, then ONE block combines them in a fixed order and writes the
 //          total norm and the clip coefficient to device memory (no float atomics: the same bits on every run)
 //   scale: g *= coef[0] in place (the coefficient never leaves the device)
@@ -11,7 +11,7 @@
 #include <algorithm>
 #include <math.h>
 
-#include "msn_common.h"
+#include "multi_tensor.h"
 
 namespace msn {
 
@@ -20,23 +20,7 @@ struct GradTensor {  // 2 x 8 bytes, uploaded by the host as int64 words
     int64_t n;
 };
 
-constexpr int kClipThreads = 256;
 constexpr int kFinishThreads = 1024;
-constexpr int kUnroll = 4;                                                  // float4 loads in flight per lane and pass
-constexpr int64_t kBlockElems = 4LL * kClipThreads * kUnroll;               // elements one block covers per pass
-
-// Blocks per tensor (grid x): enough for the largest tensor, but about 8192 blocks in all -- a grid of mostly empty blocks
-// (a model's many small tensors beside a few large ones) costs more to dispatch than the pass itself moves; a tensor
-// larger than gx blocks cover loops over its passes.
-static inline int clip_grid_x(int n_tensors, int64_t max_numel) {
-    const int64_t cap = std::min<int64_t>(1024, std::max<int64_t>(32, 8192 / std::max(n_tensors, 1)));
-    return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(max_numel, kBlockElems), cap));
-}
-
-// blocks that work on a tensor of n elements (every kernel and the finishing pass agree on it)
-__device__ __forceinline__ int tensor_blocks(int64_t n, int gx) {
-    return (int)std::min<int64_t>((n + kBlockElems - 1) / kBlockElems, (int64_t)gx);
-}
 
 // nan_max, norm_combine<P>: msn_common.h (shared with optim_layerwise.hip)
 template <int P>
@@ -49,11 +33,11 @@ __device__ __forceinline__ double norm_term(float x) {
 // block_combine<P, THREADS>: msn_common.h
 
 template <int P>
-__global__ __launch_bounds__(kClipThreads) void grad_norm_partial_kernel(const GradTensor* __restrict__ table, int gx,
-                                                                         double* __restrict__ part) {
-    __shared__ double red[kClipThreads / kWave];
+__global__ __launch_bounds__(kMtThreads) void grad_norm_partial_kernel(const GradTensor* __restrict__ table, int gx,
+                                                                       double* __restrict__ part) {
+    __shared__ double red[kMtThreads / kWave];
     const GradTensor t = table[blockIdx.y];
-    const int nb = tensor_blocks(t.n, gx);
+    const int nb = mt_blocks(t.n, gx);
     if ((int)blockIdx.x >= nb) {                       // an idle block leaves the neutral partial: the finishing pass reads every slot
         if (threadIdx.x == 0) part[(int64_t)blockIdx.y * gx + blockIdx.x] = 0.0;
         return;
@@ -62,25 +46,24 @@ __global__ __launch_bounds__(kClipThreads) void grad_norm_partial_kernel(const G
     const bool vec = (reinterpret_cast<uintptr_t>(t.g) & 15) == 0;
     const int64_t n4 = vec ? t.n / 4 : 0;
     const float4* g4 = reinterpret_cast<const float4*>(t.g);
-    for (int64_t base = (int64_t)blockIdx.x * (kClipThreads * kUnroll); base < n4;
-         base += (int64_t)nb * (kClipThreads * kUnroll)) {
-        float4 v[kUnroll];
+    mt_passes(n4, nb, [&](int64_t q0) {
+        float4 v[kMtUnroll];
 #pragma unroll
-        for (int k = 0; k < kUnroll; ++k) {
-            const int64_t i = base + k * kClipThreads + threadIdx.x;
+        for (int k = 0; k < kMtUnroll; ++k) {
+            const int64_t i = q0 + k * kMtThreads;
             v[k] = i < n4 ? g4[i] : make_float4(0.f, 0.f, 0.f, 0.f);      // zero is neutral for the sums and for max |g|
         }
 #pragma unroll
-        for (int k = 0; k < kUnroll; ++k) {
+        for (int k = 0; k < kMtUnroll; ++k) {
             acc = norm_combine<P>(acc, norm_term<P>(v[k].x));
             acc = norm_combine<P>(acc, norm_term<P>(v[k].y));
             acc = norm_combine<P>(acc, norm_term<P>(v[k].z));
             acc = norm_combine<P>(acc, norm_term<P>(v[k].w));
         }
-    }
-    for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * kClipThreads + threadIdx.x; i < t.n; i += (int64_t)nb * kClipThreads)
+    });
+    for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * kMtThreads + threadIdx.x; i < t.n; i += (int64_t)nb * kMtThreads)
         acc = norm_combine<P>(acc, norm_term<P>(t.g[i]));
-    const double r = block_combine<P, kClipThreads>(acc, red);
+    const double r = block_combine<P, kMtThreads>(acc, red);
     if (threadIdx.x == 0) part[(int64_t)blockIdx.y * gx + blockIdx.x] = r;
 }
 
@@ -110,42 +93,50 @@ __global__ __launch_bounds__(kFinishThreads) void grad_norm_finish_kernel(int64_
     }
 }
 
-// In-place elementwise map over every tensor of the table: the passes of the partial kernel (kUnroll float4 per lane and
+// In-place elementwise map over every tensor of the table: the passes of the partial kernel (kMtUnroll float4 per lane and
 // pass when aligned), a scalar tail otherwise.
 template <typename F>
 __device__ __forceinline__ void grad_map(const GradTensor& t, int gx, F f) {
-    const int nb = tensor_blocks(t.n, gx);
+    const int nb = mt_blocks(t.n, gx);
     if ((int)blockIdx.x >= nb) return;
     const bool vec = (reinterpret_cast<uintptr_t>(t.g) & 15) == 0;
     const int64_t n4 = vec ? t.n / 4 : 0;
     float4* g4 = reinterpret_cast<float4*>(t.g);
-    for (int64_t base = (int64_t)blockIdx.x * (kClipThreads * kUnroll); base < n4;
-         base += (int64_t)nb * (kClipThreads * kUnroll)) {
-        float4 v[kUnroll];
+    mt_passes(n4, nb, [&](int64_t q0) {
+        float4 v[kMtUnroll];
 #pragma unroll
-        for (int k = 0; k < kUnroll; ++k) {
-            const int64_t i = base + k * kClipThreads + threadIdx.x;
+        for (int k = 0; k < kMtUnroll; ++k) {
+            const int64_t i = q0 + k * kMtThreads;
             if (i < n4) v[k] = g4[i];
         }
 #pragma unroll
-        for (int k = 0; k < kUnroll; ++k) {
-            const int64_t i = base + k * kClipThreads + threadIdx.x;
+        for (int k = 0; k < kMtUnroll; ++k) {
+            const int64_t i = q0 + k * kMtThreads;
             if (i < n4) g4[i] = make_float4(f(v[k].x), f(v[k].y), f(v[k].z), f(v[k].w));
         }
-    }
-    for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * kClipThreads + threadIdx.x; i < t.n; i += (int64_t)nb * kClipThreads)
+    });
+    for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * kMtThreads + threadIdx.x; i < t.n; i += (int64_t)nb * kMtThreads)
         t.g[i] = f(t.g[i]);
 }
 
-__global__ __launch_bounds__(kClipThreads) void grad_scale_kernel(const GradTensor* __restrict__ table, int gx,
-                                                                  const float* __restrict__ coef) {
+__global__ __launch_bounds__(kMtThreads) void grad_scale_kernel(const GradTensor* __restrict__ table, int gx,
+                                                                const float* __restrict__ coef) {
     const float c = coef[0];
     grad_map(table[blockIdx.y], gx, [c](float x) { return x * c; });
 }
 
-__global__ __launch_bounds__(kClipThreads) void grad_clamp_kernel(const GradTensor* __restrict__ table, int gx, float v) {
+__global__ __launch_bounds__(kMtThreads) void grad_clamp_kernel(const GradTensor* __restrict__ table, int gx, float v) {
     // comparisons a NaN fails: NaN stays NaN (torch.clamp)
     grad_map(table[blockIdx.y], gx, [v](float x) { return x < -v ? -v : (x > v ? v : x); });
+}
+
+// the two launches of msn_grad_norm for one norm type
+template <int P>
+static void launch_grad_norm(const GradTensor* tab, int n_tensors, int gx, double* part, float max_norm, float* total_norm,
+                             float* coef, hipStream_t st) {
+    hipLaunchKernelGGL(grad_norm_partial_kernel<P>, dim3(gx, n_tensors), dim3(kMtThreads), 0, st, tab, gx, part);
+    hipLaunchKernelGGL(grad_norm_finish_kernel<P>, dim3(1), dim3(kFinishThreads), 0, st, (int64_t)n_tensors * gx, part, max_norm,
+                       total_norm, coef);
 }
 
 }  // namespace msn
@@ -153,49 +144,31 @@ __global__ __launch_bounds__(kClipThreads) void grad_clamp_kernel(const GradTens
 using namespace msn;
 
 extern "C" size_t msn_grad_norm_workspace_bytes(int n_tensors, int64_t max_numel) {
-    if (n_tensors <= 0 || n_tensors > 65535 || max_numel < 0) return 0;
-    return (size_t)n_tensors * (size_t)clip_grid_x(n_tensors, max_numel) * sizeof(double);
+    if (n_tensors <= 0 || n_tensors > kMtMaxTensors || max_numel < 0) return 0;
+    return (size_t)n_tensors * (size_t)mt_grid_x(n_tensors, max_numel) * sizeof(double);
 }
 
 extern "C" int msn_grad_norm(const void* table, int n_tensors, int64_t max_numel, float norm_type, float max_norm,
                              float* total_norm, float* coef, void* ws, size_t ws_bytes, msn_stream_t stream) {
     MSN_REQUIRE(table && total_norm && coef, "msn_grad_norm: null table or output pointer");
-    MSN_REQUIRE(n_tensors > 0 && n_tensors <= 65535, "msn_grad_norm: n_tensors must be in 1..65535 (got %d)", n_tensors);
-    MSN_REQUIRE(max_numel >= 0, "msn_grad_norm: negative max_numel");
+    MSN_REQUIRE_TABLE("msn_grad_norm", n_tensors, max_numel);
     MSN_REQUIRE(norm_type == 1.f || norm_type == 2.f || norm_type == INFINITY,
                 "msn_grad_norm: norm_type must be 1, 2 or inf (got %g)", (double)norm_type);
     MSN_REQUIRE(max_norm >= 0.f, "msn_grad_norm: max_norm must be a non-negative number");
     const size_t need = msn_grad_norm_workspace_bytes(n_tensors, max_numel);
     MSN_REQUIRE(ws && ws_bytes >= need, "msn_grad_norm: workspace of %zu bytes needed, %zu given", need, ws_bytes);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const GradTensor* tab = static_cast<const GradTensor*>(table);
-    const int gx = clip_grid_x(n_tensors, max_numel);
-    const int64_t n_part = (int64_t)n_tensors * gx;
-    double* part = static_cast<double*>(ws);
-    const dim3 grid(gx, n_tensors);
-    if (norm_type == 2.f) {
-        hipLaunchKernelGGL(grad_norm_partial_kernel<2>, grid, dim3(kClipThreads), 0, st, tab, gx, part);
-        hipLaunchKernelGGL(grad_norm_finish_kernel<2>, dim3(1), dim3(kFinishThreads), 0, st, n_part, part, max_norm,
-                           total_norm, coef);
-    } else if (norm_type == 1.f) {
-        hipLaunchKernelGGL(grad_norm_partial_kernel<1>, grid, dim3(kClipThreads), 0, st, tab, gx, part);
-        hipLaunchKernelGGL(grad_norm_finish_kernel<1>, dim3(1), dim3(kFinishThreads), 0, st, n_part, part, max_norm,
-                           total_norm, coef);
-    } else {
-        hipLaunchKernelGGL(grad_norm_partial_kernel<0>, grid, dim3(kClipThreads), 0, st, tab, gx, part);
-        hipLaunchKernelGGL(grad_norm_finish_kernel<0>, dim3(1), dim3(kFinishThreads), 0, st, n_part, part, max_norm,
-                           total_norm, coef);
-    }
+    const auto launch = norm_type == 2.f ? launch_grad_norm<2> : norm_type == 1.f ? launch_grad_norm<1> : launch_grad_norm<0>;
+    launch(static_cast<const GradTensor*>(table), n_tensors, mt_grid_x(n_tensors, max_numel), static_cast<double*>(ws), max_norm,
+           total_norm, coef, static_cast<hipStream_t>(stream));
     MSN_LAUNCH_CHECK();
     return MSN_OK;
 }
 
 extern "C" int msn_grad_scale(const void* table, int n_tensors, int64_t max_numel, const float* coef, msn_stream_t stream) {
     MSN_REQUIRE(table && coef, "msn_grad_scale: null table or coefficient");
-    MSN_REQUIRE(n_tensors > 0 && n_tensors <= 65535, "msn_grad_scale: n_tensors must be in 1..65535 (got %d)", n_tensors);
-    MSN_REQUIRE(max_numel >= 0, "msn_grad_scale: negative max_numel");
-    const int gx = clip_grid_x(n_tensors, max_numel);
-    hipLaunchKernelGGL(grad_scale_kernel, dim3(gx, n_tensors), dim3(kClipThreads), 0, static_cast<hipStream_t>(stream),
+    MSN_REQUIRE_TABLE("msn_grad_scale", n_tensors, max_numel);
+    const int gx = mt_grid_x(n_tensors, max_numel);
+    hipLaunchKernelGGL(grad_scale_kernel, dim3(gx, n_tensors), dim3(kMtThreads), 0, static_cast<hipStream_t>(stream),
                        static_cast<const GradTensor*>(table), gx, coef);
     MSN_LAUNCH_CHECK();
     return MSN_OK;
@@ -203,11 +176,10 @@ extern "C" int msn_grad_scale(const void* table, int n_tensors, int64_t max_nume
 
 extern "C" int msn_grad_clamp(const void* table, int n_tensors, int64_t max_numel, float clip_value, msn_stream_t stream) {
     MSN_REQUIRE(table, "msn_grad_clamp: null table");
-    MSN_REQUIRE(n_tensors > 0 && n_tensors <= 65535, "msn_grad_clamp: n_tensors must be in 1..65535 (got %d)", n_tensors);
-    MSN_REQUIRE(max_numel >= 0, "msn_grad_clamp: negative max_numel");
+    MSN_REQUIRE_TABLE("msn_grad_clamp", n_tensors, max_numel);
     MSN_REQUIRE(clip_value >= 0.f, "msn_grad_clamp: clip_value must be a non-negative number");
-    const int gx = clip_grid_x(n_tensors, max_numel);
-    hipLaunchKernelGGL(grad_clamp_kernel, dim3(gx, n_tensors), dim3(kClipThreads), 0, static_cast<hipStream_t>(stream),
+    const int gx = mt_grid_x(n_tensors, max_numel);
+    hipLaunchKernelGGL(grad_clamp_kernel, dim3(gx, n_tensors), dim3(kMtThreads), 0, static_cast<hipStream_t>(stream),
                        static_cast<const GradTensor*>(table), gx, clip_value);
     MSN_LAUNCH_CHECK();
     return MSN_OK;

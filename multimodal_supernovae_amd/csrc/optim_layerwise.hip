@@ -17,31 +17,14 @@
 // elements whether it loads them as one float4 (every pointer of the tensor 16-byte aligned) or as four scalars (otherwise);
 // the n % 4 elements of the tail go to the first lanes of the tensor's block 0 in both.  Every multiply-add is spelled out and
 // contraction is off, as in optim_steps.hip.
-#include <algorithm>
 #include <cstddef>
 #include <math.h>
 
-#include "msn_common.h"
+#include "multi_tensor.h"
 
 #pragma clang fp contract(off)
 
 namespace msn {
-
-constexpr int kLwThreads = 256;
-constexpr int kLwUnroll = 4;                                               // quads (4 elements) in flight per lane and pass
-constexpr int64_t kLwBlockElems = 4LL * kLwThreads * kLwUnroll;            // elements one block covers per pass
-
-// Blocks per tensor (grid x), the rule of grad_clip.hip: enough for the largest tensor, but about 8192 blocks in all; a tensor
-// larger than gx blocks cover loops over its passes.
-static inline int lw_grid_x(int n_tensors, int64_t max_numel) {
-    const int64_t cap = std::min<int64_t>(1024, std::max<int64_t>(32, 8192 / std::max(n_tensors, 1)));
-    return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(max_numel, kLwBlockElems), cap));
-}
-
-// blocks that work on a tensor of n elements (every launch of the pass agrees on it)
-__device__ __forceinline__ int lw_blocks(int64_t n, int gx) {
-    return (int)std::min<int64_t>((n + kLwBlockElems - 1) / kLwBlockElems, (int64_t)gx);
-}
 
 // every pointer given sits on a 16-byte boundary (a null pointer does)
 __device__ __forceinline__ bool lw_aligned(const void* a, const void* b, const void* c = nullptr, const void* d = nullptr) {
@@ -60,13 +43,12 @@ __device__ __forceinline__ void store_quad(float* p, int64_t q, float4 v) {
     else { p[4 * q] = v.x; p[4 * q + 1] = v.y; p[4 * q + 2] = v.z; p[4 * q + 3] = v.w; }
 }
 
-// The element-to-lane map of every launch here: quad q = base + k * kLwThreads + threadIdx.x of the n / 4 whole quads, kLwUnroll
-// per lane and pass, then the n % 4 tail elements on the first lanes of block 0.  quads(q, k) loads, element(...) works.
+// The element-to-lane map of every launch here: the passes of multi_tensor.h over the n / 4 whole quads, aligned or not, then the
+// n % 4 tail elements on the first lanes of block 0.  quads(q0, n4) works on a lane's quads of one pass, tail(i) on element i.
 template <class Quads, class Tail>
 __device__ __forceinline__ void lw_for_each(int64_t n, int nb, Quads quads, Tail tail) {
     const int64_t n4 = n / 4;
-    for (int64_t base = (int64_t)blockIdx.x * (kLwThreads * kLwUnroll); base < n4; base += (int64_t)nb * (kLwThreads * kLwUnroll))
-        quads(base + threadIdx.x, n4);
+    mt_passes(n4, nb, [&](int64_t q0) { quads(q0, n4); });
     if (blockIdx.x == 0 && (int64_t)threadIdx.x < n - 4 * n4) tail(4 * n4 + threadIdx.x);
 }
 
@@ -77,9 +59,9 @@ __device__ __forceinline__ void lw_sq(double& acc, float x) {
 
 // Writes the block's two partial sums: part[(tensor * 2 + which) * gx + block].
 __device__ __forceinline__ void lw_write_partials(double a, double b, double* __restrict__ part, int gx) {
-    __shared__ double red_a[kLwThreads / kWave], red_b[kLwThreads / kWave];
-    const double ra = block_combine<2, kLwThreads>(a, red_a);
-    const double rb = block_combine<2, kLwThreads>(b, red_b);
+    __shared__ double red_a[kMtThreads / kWave], red_b[kMtThreads / kWave];
+    const double ra = block_combine<2, kMtThreads>(a, red_a);
+    const double rb = block_combine<2, kMtThreads>(b, red_b);
     if (threadIdx.x == 0) {
         part[((int64_t)blockIdx.y * 2 + 0) * gx + blockIdx.x] = ra;
         part[((int64_t)blockIdx.y * 2 + 1) * gx + blockIdx.x] = rb;
@@ -90,19 +72,11 @@ __device__ __forceinline__ void lw_write_partials(double a, double b, double* __
 __device__ __forceinline__ double lw_sum_partials(const double* __restrict__ part, int which, int gx, double* red) {
     const double* src = part + ((int64_t)blockIdx.x * 2 + which) * gx;
     double acc = 0.0;
-    for (int j = threadIdx.x; j < gx; j += kLwThreads) acc += src[j];
-    return block_combine<2, kLwThreads>(acc, red);
+    for (int j = threadIdx.x; j < gx; j += kMtThreads) acc += src[j];
+    return block_combine<2, kMtThreads>(acc, red);
 }
 
-// ---- LAMB ---------------------------------------------------------------------------------------------------------------------
-struct LambTensor {  // 5 x 8 bytes, uploaded by the host as int64 words (AdamTensor's layout)
-    float* p;
-    const float* g;
-    float* m;
-    float* v;
-    int64_t n;
-};
-
+// ---- LAMB (records: MomentTensor of multi_tensor.h) ---------------------------------------------------------------------------
 // inv_c1 = 1 / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t) (both 1 without bias correction).  There is no float beta1: the
 // first moment is the fused lerp of adam_kernel, for the reason written there.
 struct LambHyper {
@@ -144,21 +118,21 @@ __device__ __forceinline__ float lamb_update(float p, float m, float v, const La
 }
 
 template <bool VEC>
-__device__ __forceinline__ void lamb_moments_body(const LambTensor& t, int nb, const LambHyper& h, double& sp, double& su) {
+__device__ __forceinline__ void lamb_moments_body(const MomentTensor& t, int nb, const LambHyper& h, double& sp, double& su) {
     lw_for_each(t.n, nb,
         [&](int64_t q0, int64_t n4) {
-            float4 p[kLwUnroll], g[kLwUnroll], m[kLwUnroll], v[kLwUnroll];
+            float4 p[kMtUnroll], g[kMtUnroll], m[kMtUnroll], v[kMtUnroll];
 #pragma unroll
-            for (int k = 0; k < kLwUnroll; ++k) {
-                const int64_t q = q0 + k * kLwThreads;
+            for (int k = 0; k < kMtUnroll; ++k) {
+                const int64_t q = q0 + k * kMtThreads;
                 if (q < n4) {
                     p[k] = load_quad<VEC>(t.p, q); g[k] = load_quad<VEC>(t.g, q);
                     m[k] = load_quad<VEC>(t.m, q); v[k] = load_quad<VEC>(t.v, q);
                 }
             }
 #pragma unroll
-            for (int k = 0; k < kLwUnroll; ++k) {
-                const int64_t q = q0 + k * kLwThreads;
+            for (int k = 0; k < kMtUnroll; ++k) {
+                const int64_t q = q0 + k * kMtThreads;
                 if (q < n4) {
                     lamb_moments(g[k].x, m[k].x, v[k].x, h); lamb_moments(g[k].y, m[k].y, v[k].y, h);
                     lamb_moments(g[k].z, m[k].z, v[k].z, h); lamb_moments(g[k].w, m[k].w, v[k].w, h);
@@ -182,11 +156,11 @@ __device__ __forceinline__ void lamb_moments_body(const LambTensor& t, int nb, c
 }
 
 // dev != NULL: the scalars come from device memory (a launch recorded in a HIP graph is replayed with the values of the replay)
-__global__ __launch_bounds__(kLwThreads) void lamb_moments_kernel(const LambTensor* __restrict__ table, int gx, LambHyper h,
+__global__ __launch_bounds__(kMtThreads) void lamb_moments_kernel(const MomentTensor* __restrict__ table, int gx, LambHyper h,
                                                                   const LambHyper* __restrict__ dev, double* __restrict__ part) {
     if (dev) h = *dev;
-    const LambTensor t = table[blockIdx.y];
-    const int nb = lw_blocks(t.n, gx);
+    const MomentTensor t = table[blockIdx.y];
+    const int nb = mt_blocks(t.n, gx);
     double sp = 0.0, su = 0.0;
     if ((int)blockIdx.x < nb) {                        // an idle block leaves the neutral partials: the finishing pass reads every slot
         if (lw_aligned(t.p, t.g, t.m, t.v)) lamb_moments_body<true>(t, nb, h, sp, su);
@@ -197,10 +171,10 @@ __global__ __launch_bounds__(kLwThreads) void lamb_moments_kernel(const LambTens
 
 // ratio = ||p|| / ||u|| if (wd != 0 or always_adapt) and ||p|| > 0 and ||u|| > 0, else 1; with trust_clip min(ratio, 1).  The
 // decision about wd is taken on the exact double (dev != NULL: the one of the device block).
-__global__ __launch_bounds__(kLwThreads) void lamb_finish_kernel(const double* __restrict__ part, int gx, double wd,
+__global__ __launch_bounds__(kMtThreads) void lamb_finish_kernel(const double* __restrict__ part, int gx, double wd,
                                                                  const LambHyperDev* __restrict__ dev, int always_adapt,
                                                                  int trust_clip, float* __restrict__ ratio) {
-    __shared__ double red_p[kLwThreads / kWave], red_u[kLwThreads / kWave];
+    __shared__ double red_p[kMtThreads / kWave], red_u[kMtThreads / kWave];
     const double sp = lw_sum_partials(part, 0, gx, red_p), su = lw_sum_partials(part, 1, gx, red_u);
     if (threadIdx.x == 0) {
         if (dev) wd = dev->weight_decay;
@@ -213,22 +187,22 @@ __global__ __launch_bounds__(kLwThreads) void lamb_finish_kernel(const double* _
 }
 
 template <bool VEC>
-__device__ __forceinline__ void lamb_apply_body(const LambTensor& t, int nb, const LambHyper& h, float step) {
+__device__ __forceinline__ void lamb_apply_body(const MomentTensor& t, int nb, const LambHyper& h, float step) {
     auto upd = [&](float& p, float m, float v) {
 #pragma clang fp contract(off)
         p = fmaf(-step, lamb_update(p, m, v, h), p);
     };
     lw_for_each(t.n, nb,
         [&](int64_t q0, int64_t n4) {
-            float4 p[kLwUnroll], m[kLwUnroll], v[kLwUnroll];
+            float4 p[kMtUnroll], m[kMtUnroll], v[kMtUnroll];
 #pragma unroll
-            for (int k = 0; k < kLwUnroll; ++k) {
-                const int64_t q = q0 + k * kLwThreads;
+            for (int k = 0; k < kMtUnroll; ++k) {
+                const int64_t q = q0 + k * kMtThreads;
                 if (q < n4) { p[k] = load_quad<VEC>(t.p, q); m[k] = load_quad<VEC>(t.m, q); v[k] = load_quad<VEC>(t.v, q); }
             }
 #pragma unroll
-            for (int k = 0; k < kLwUnroll; ++k) {
-                const int64_t q = q0 + k * kLwThreads;
+            for (int k = 0; k < kMtUnroll; ++k) {
+                const int64_t q = q0 + k * kMtThreads;
                 if (q < n4) {
                     upd(p[k].x, m[k].x, v[k].x); upd(p[k].y, m[k].y, v[k].y); upd(p[k].z, m[k].z, v[k].z); upd(p[k].w, m[k].w, v[k].w);
                     store_quad<VEC>(t.p, q, p[k]);
@@ -243,11 +217,11 @@ __device__ __forceinline__ void lamb_apply_body(const LambTensor& t, int nb, con
 }
 
 // p -= (lr * ratio) u
-__global__ __launch_bounds__(kLwThreads) void lamb_apply_kernel(const LambTensor* __restrict__ table, int gx, LambHyper h,
+__global__ __launch_bounds__(kMtThreads) void lamb_apply_kernel(const MomentTensor* __restrict__ table, int gx, LambHyper h,
                                                                 const LambHyper* __restrict__ dev, const float* __restrict__ ratio) {
     if (dev) h = *dev;
-    const LambTensor t = table[blockIdx.y];
-    const int nb = lw_blocks(t.n, gx);
+    const MomentTensor t = table[blockIdx.y];
+    const int nb = mt_blocks(t.n, gx);
     if ((int)blockIdx.x >= nb) return;
     const float step = h.lr * ratio[blockIdx.y];
     if (lw_aligned(t.p, t.m, t.v)) lamb_apply_body<true>(t, nb, h, step);
@@ -260,14 +234,7 @@ __global__ void lamb_prepare_kernel(LambHyperDev* __restrict__ hyper, int bias_c
     lamb_step_terms(hyper->beta1, hyper->beta2, bias_correction, step, &hyper->h.inv_c1, &hyper->h.bc2_sqrt);
 }
 
-// ---- LARS ---------------------------------------------------------------------------------------------------------------------
-struct LarsTensor {  // 4 x 8 bytes (SgdTensor's layout); buf == NULL: no momentum buffer (momentum == 0)
-    float* p;
-    const float* g;
-    float* buf;
-    int64_t n;
-};
-
+// ---- LARS (records: SgdTensor of multi_tensor.h) ------------------------------------------------------------------------------
 struct LarsHyper {
     float lr, momentum, omd /* 1 - dampening */, weight_decay;
 };
@@ -283,19 +250,19 @@ static_assert(sizeof(LarsHyperDev) == 64 && offsetof(LarsHyperDev, h) == 32 && o
               "layout shared with optim.py");
 
 template <bool VEC>
-__device__ __forceinline__ void lars_norms_body(const LarsTensor& t, int nb, double& sp, double& sg) {
+__device__ __forceinline__ void lars_norms_body(const SgdTensor& t, int nb, double& sp, double& sg) {
     lw_for_each(t.n, nb,
         [&](int64_t q0, int64_t n4) {
-            float4 p[kLwUnroll], g[kLwUnroll];
+            float4 p[kMtUnroll], g[kMtUnroll];
 #pragma unroll
-            for (int k = 0; k < kLwUnroll; ++k) {
-                const int64_t q = q0 + k * kLwThreads;
+            for (int k = 0; k < kMtUnroll; ++k) {
+                const int64_t q = q0 + k * kMtThreads;
                 const bool in = q < n4;                            // zero is neutral for the sums
                 p[k] = in ? load_quad<VEC>(t.p, q) : make_float4(0.f, 0.f, 0.f, 0.f);
                 g[k] = in ? load_quad<VEC>(t.g, q) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
 #pragma unroll
-            for (int k = 0; k < kLwUnroll; ++k) {
+            for (int k = 0; k < kMtUnroll; ++k) {
                 lw_sq(sp, p[k].x); lw_sq(sp, p[k].y); lw_sq(sp, p[k].z); lw_sq(sp, p[k].w);
                 lw_sq(sg, g[k].x); lw_sq(sg, g[k].y); lw_sq(sg, g[k].z); lw_sq(sg, g[k].w);
             }
@@ -306,10 +273,10 @@ __device__ __forceinline__ void lars_norms_body(const LarsTensor& t, int nb, dou
         });
 }
 
-__global__ __launch_bounds__(kLwThreads) void lars_norms_kernel(const LarsTensor* __restrict__ table, int gx,
+__global__ __launch_bounds__(kMtThreads) void lars_norms_kernel(const SgdTensor* __restrict__ table, int gx,
                                                                 double* __restrict__ part) {
-    const LarsTensor t = table[blockIdx.y];
-    const int nb = lw_blocks(t.n, gx);
+    const SgdTensor t = table[blockIdx.y];
+    const int nb = mt_blocks(t.n, gx);
     double sp = 0.0, sg = 0.0;
     if ((int)blockIdx.x < nb) {
         if (lw_aligned(t.p, t.g)) lars_norms_body<true>(t, nb, sp, sg);
@@ -320,10 +287,10 @@ __global__ __launch_bounds__(kLwThreads) void lars_norms_kernel(const LarsTensor
 
 // ratio = trust_coefficient ||p|| / (||g|| + wd ||p|| + eps) if wd != 0 and ||p|| > 0 and ||g|| > 0, else 1 -- in double from the
 // exact scalars (dev != NULL: those of the device block), rounded to float once.
-__global__ __launch_bounds__(kLwThreads) void lars_finish_kernel(const double* __restrict__ part, int gx, double wd, double tc,
+__global__ __launch_bounds__(kMtThreads) void lars_finish_kernel(const double* __restrict__ part, int gx, double wd, double tc,
                                                                  double eps, const LarsHyperDev* __restrict__ dev,
                                                                  float* __restrict__ ratio) {
-    __shared__ double red_p[kLwThreads / kWave], red_g[kLwThreads / kWave];
+    __shared__ double red_p[kMtThreads / kWave], red_g[kMtThreads / kWave];
     const double sp = lw_sum_partials(part, 0, gx, red_p), sg = lw_sum_partials(part, 1, gx, red_g);
     if (threadIdx.x == 0) {
 #pragma clang fp contract(off)
@@ -339,7 +306,7 @@ __global__ __launch_bounds__(kLwThreads) void lars_finish_kernel(const double* _
 }
 
 template <bool VEC>
-__device__ __forceinline__ void lars_apply_body(const LarsTensor& t, int nb, const LarsHyper& h, float q, bool with_buf,
+__device__ __forceinline__ void lars_apply_body(const SgdTensor& t, int nb, const LarsHyper& h, float q, bool with_buf,
                                                 int nesterov, int first) {
     // d = q (g + wd p), then sgd_kernel's update.  q == 1 multiplies exactly: with wd == 0 this IS the SGD step, bit for bit.
     auto upd = [&](float& p, float g, float& buf) {
@@ -354,10 +321,10 @@ __device__ __forceinline__ void lars_apply_body(const LarsTensor& t, int nb, con
     };
     lw_for_each(t.n, nb,
         [&](int64_t q0, int64_t n4) {
-            float4 p[kLwUnroll], g[kLwUnroll], b[kLwUnroll];
+            float4 p[kMtUnroll], g[kMtUnroll], b[kMtUnroll];
 #pragma unroll
-            for (int k = 0; k < kLwUnroll; ++k) {
-                const int64_t i = q0 + k * kLwThreads;
+            for (int k = 0; k < kMtUnroll; ++k) {
+                const int64_t i = q0 + k * kMtThreads;
                 b[k] = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (i < n4) {
                     p[k] = load_quad<VEC>(t.p, i); g[k] = load_quad<VEC>(t.g, i);
@@ -365,8 +332,8 @@ __device__ __forceinline__ void lars_apply_body(const LarsTensor& t, int nb, con
                 }
             }
 #pragma unroll
-            for (int k = 0; k < kLwUnroll; ++k) {
-                const int64_t i = q0 + k * kLwThreads;
+            for (int k = 0; k < kMtUnroll; ++k) {
+                const int64_t i = q0 + k * kMtThreads;
                 if (i < n4) {
                     upd(p[k].x, g[k].x, b[k].x); upd(p[k].y, g[k].y, b[k].y); upd(p[k].z, g[k].z, b[k].z); upd(p[k].w, g[k].w, b[k].w);
                     store_quad<VEC>(t.p, i, p[k]);
@@ -382,12 +349,12 @@ __device__ __forceinline__ void lars_apply_body(const LarsTensor& t, int nb, con
         });
 }
 
-__global__ __launch_bounds__(kLwThreads) void lars_apply_kernel(const LarsTensor* __restrict__ table, int gx, LarsHyper h,
+__global__ __launch_bounds__(kMtThreads) void lars_apply_kernel(const SgdTensor* __restrict__ table, int gx, LarsHyper h,
                                                                 const LarsHyper* __restrict__ dev, int nesterov, int first,
                                                                 const float* __restrict__ ratio) {
     if (dev) h = *dev;
-    const LarsTensor t = table[blockIdx.y];
-    const int nb = lw_blocks(t.n, gx);
+    const SgdTensor t = table[blockIdx.y];
+    const int nb = mt_blocks(t.n, gx);
     if ((int)blockIdx.x >= nb) return;
     const bool with_buf = t.buf != nullptr && h.momentum != 0.f;
     const float q = ratio[blockIdx.y];
@@ -396,7 +363,33 @@ __global__ __launch_bounds__(kLwThreads) void lars_apply_kernel(const LarsTensor
 }
 
 static inline size_t lw_partial_bytes(int n_tensors, int64_t max_numel) {
-    return (size_t)n_tensors * (size_t)lw_grid_x(n_tensors, max_numel) * 2 * sizeof(double);
+    return (size_t)n_tensors * (size_t)mt_grid_x(n_tensors, max_numel) * 2 * sizeof(double);
+}
+
+// The three launches of a step, eager (dev == NULL: the scalars h, wd, ... by value) or recorded (dev: the device block, from
+// which every launch reads its scalars; the by-value ones are then ignored).
+static void lamb_launch(const void* table, int n_tensors, int64_t max_numel, const LambHyper& h, double wd,
+                        const LambHyperDev* dev, int always_adapt, int trust_clip, void* ws, float* ratio, hipStream_t st) {
+    const MomentTensor* tab = static_cast<const MomentTensor*>(table);
+    const int gx = mt_grid_x(n_tensors, max_numel);
+    double* part = static_cast<double*>(ws);
+    const LambHyper* hp = dev ? &dev->h : nullptr;
+    hipLaunchKernelGGL(lamb_moments_kernel, dim3(gx, n_tensors), dim3(kMtThreads), 0, st, tab, gx, h, hp, part);
+    hipLaunchKernelGGL(lamb_finish_kernel, dim3(n_tensors), dim3(kMtThreads), 0, st, part, gx, wd, dev, always_adapt ? 1 : 0,
+                       trust_clip ? 1 : 0, ratio);
+    hipLaunchKernelGGL(lamb_apply_kernel, dim3(gx, n_tensors), dim3(kMtThreads), 0, st, tab, gx, h, hp, ratio);
+}
+
+static void lars_launch(const void* table, int n_tensors, int64_t max_numel, const LarsHyper& h, double wd, double tc, double eps,
+                        const LarsHyperDev* dev, int nesterov, int first, void* ws, float* ratio, hipStream_t st) {
+    const SgdTensor* tab = static_cast<const SgdTensor*>(table);
+    const int gx = mt_grid_x(n_tensors, max_numel);
+    double* part = static_cast<double*>(ws);
+    const LarsHyper* hp = dev ? &dev->h : nullptr;
+    hipLaunchKernelGGL(lars_norms_kernel, dim3(gx, n_tensors), dim3(kMtThreads), 0, st, tab, gx, part);
+    hipLaunchKernelGGL(lars_finish_kernel, dim3(n_tensors), dim3(kMtThreads), 0, st, part, gx, wd, tc, eps, dev, ratio);
+    hipLaunchKernelGGL(lars_apply_kernel, dim3(gx, n_tensors), dim3(kMtThreads), 0, st, tab, gx, h, hp, nesterov ? 1 : 0,
+                       first ? 1 : 0, ratio);
 }
 
 }  // namespace msn
@@ -404,18 +397,21 @@ static inline size_t lw_partial_bytes(int n_tensors, int64_t max_numel) {
 using namespace msn;
 
 // Never less than a launch of n_tensors tensors of at most max_numel elements needs (2 doubles per block of the first launch),
-// and never less for more tensors or larger ones: scratch sized for a whole param group serves any subset of it.
+// and never less for more tensors or larger ones: scratch sized for a whole param group serves any subset of it.  (n * mt_grid_x
+// itself is not monotone in n: 8192 / n is rounded down.)
 extern "C" size_t msn_layerwise_workspace_bytes(int n_tensors, int64_t max_numel) {
-    if (n_tensors <= 0 || n_tensors > 65535 || max_numel < 0) return 0;
+    if (n_tensors <= 0 || n_tensors > kMtMaxTensors || max_numel < 0) return 0;
     const int64_t n = n_tensors;
-    const int64_t blocks = std::max<int64_t>(n, std::min(std::min(n * cdiv(max_numel, kLwBlockElems), n * 1024),
-                                                         std::max<int64_t>(32 * n, 8192)));
+    const int64_t blocks = std::max(n, std::min(std::min(n * cdiv(max_numel, kMtBlockElems), n * kMtCapMax),
+                                                std::max(kMtCapMin * n, kMtGridBlocks)));
     return (size_t)blocks * 2 * sizeof(double);
 }
 
+// The layer-wise entry points need a largest tensor (max_numel > 0, where the other multi-tensor launches accept 0), scratch and
+// a place for the ratios.
 #define LW_REQUIRE_COMMON(name)                                                                                              \
     MSN_REQUIRE(table && ws && ratio, name ": null table, workspace or ratio pointer");                                      \
-    MSN_REQUIRE(n_tensors > 0 && n_tensors <= 65535, name ": n_tensors must be in 1..65535 (got %d)", n_tensors);            \
+    MSN_REQUIRE_TABLE(name, n_tensors, max_numel);                                                                           \
     MSN_REQUIRE(max_numel > 0, name ": max_numel must be positive");                                                         \
     MSN_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7) == 0 && ws_bytes >= lw_partial_bytes(n_tensors, max_numel),            \
                 name ": 8-byte aligned workspace of %zu bytes needed, %zu given", lw_partial_bytes(n_tensors, max_numel), ws_bytes)
@@ -430,15 +426,8 @@ extern "C" int msn_lamb_step(const void* table, int n_tensors, int64_t max_numel
     MSN_REQUIRE(step >= 1 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "msn_lamb_step: bad step or betas");
     LambHyper h = {(float)beta2, (float)eps, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)lr, (float)weight_decay, 0.f, 0.f};
     lamb_step_terms(beta1, beta2, bias_correction, step, &h.inv_c1, &h.bc2_sqrt);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const LambTensor* tab = static_cast<const LambTensor*>(table);
-    const int gx = lw_grid_x(n_tensors, max_numel);
-    double* part = static_cast<double*>(ws);
-    const LambHyper* none = nullptr;
-    hipLaunchKernelGGL(lamb_moments_kernel, dim3(gx, n_tensors), dim3(kLwThreads), 0, st, tab, gx, h, none, part);
-    hipLaunchKernelGGL(lamb_finish_kernel, dim3(n_tensors), dim3(kLwThreads), 0, st, part, gx, weight_decay,
-                       static_cast<const LambHyperDev*>(nullptr), always_adapt ? 1 : 0, trust_clip ? 1 : 0, ratio);
-    hipLaunchKernelGGL(lamb_apply_kernel, dim3(gx, n_tensors), dim3(kLwThreads), 0, st, tab, gx, h, none, ratio);
+    lamb_launch(table, n_tensors, max_numel, h, weight_decay, nullptr, always_adapt, trust_clip, ws, ratio,
+                static_cast<hipStream_t>(stream));
     MSN_LAUNCH_CHECK();
     return MSN_OK;
 }
@@ -453,16 +442,9 @@ extern "C" int msn_lamb_step_dev(const void* table, int n_tensors, int64_t max_n
     MSN_REQUIRE(hyper && (reinterpret_cast<uintptr_t>(hyper) & 7) == 0 && step_counter,
                 "msn_lamb_step_dev: null or misaligned hyper block, or null step counter");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const LambTensor* tab = static_cast<const LambTensor*>(table);
     LambHyperDev* hd = static_cast<LambHyperDev*>(hyper);
-    const int gx = lw_grid_x(n_tensors, max_numel);
-    double* part = static_cast<double*>(ws);
-    const LambHyper* hp = &hd->h;
     hipLaunchKernelGGL(lamb_prepare_kernel, dim3(1), dim3(1), 0, st, hd, bias_correction ? 1 : 0, step_counter);
-    hipLaunchKernelGGL(lamb_moments_kernel, dim3(gx, n_tensors), dim3(kLwThreads), 0, st, tab, gx, LambHyper{}, hp, part);
-    hipLaunchKernelGGL(lamb_finish_kernel, dim3(n_tensors), dim3(kLwThreads), 0, st, part, gx, 0.0,
-                       static_cast<const LambHyperDev*>(hd), always_adapt ? 1 : 0, trust_clip ? 1 : 0, ratio);
-    hipLaunchKernelGGL(lamb_apply_kernel, dim3(gx, n_tensors), dim3(kLwThreads), 0, st, tab, gx, LambHyper{}, hp, ratio);
+    lamb_launch(table, n_tensors, max_numel, LambHyper{}, 0.0, hd, always_adapt, trust_clip, ws, ratio, st);
     MSN_LAUNCH_CHECK();
     return MSN_OK;
 }
@@ -476,15 +458,8 @@ extern "C" int msn_lars_step(const void* table, int n_tensors, int64_t max_numel
     MSN_REQUIRE(momentum >= 0.0 && (!nesterov || (momentum > 0.0 && dampening == 0.0)) && trust_coefficient > 0.0,
                 "msn_lars_step: bad momentum, nesterov or trust_coefficient");
     const LarsHyper h = {(float)lr, (float)momentum, (float)(1.0 - dampening), (float)weight_decay};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const LarsTensor* tab = static_cast<const LarsTensor*>(table);
-    const int gx = lw_grid_x(n_tensors, max_numel);
-    double* part = static_cast<double*>(ws);
-    hipLaunchKernelGGL(lars_norms_kernel, dim3(gx, n_tensors), dim3(kLwThreads), 0, st, tab, gx, part);
-    hipLaunchKernelGGL(lars_finish_kernel, dim3(n_tensors), dim3(kLwThreads), 0, st, part, gx, weight_decay, trust_coefficient,
-                       eps, static_cast<const LarsHyperDev*>(nullptr), ratio);
-    hipLaunchKernelGGL(lars_apply_kernel, dim3(gx, n_tensors), dim3(kLwThreads), 0, st, tab, gx, h,
-                       static_cast<const LarsHyper*>(nullptr), nesterov ? 1 : 0, first ? 1 : 0, ratio);
+    lars_launch(table, n_tensors, max_numel, h, weight_decay, trust_coefficient, eps, nullptr, nesterov, first, ws, ratio,
+                static_cast<hipStream_t>(stream));
     MSN_LAUNCH_CHECK();
     return MSN_OK;
 }
@@ -496,15 +471,8 @@ extern "C" int msn_lars_step_dev(const void* table, int n_tensors, int64_t max_n
                                  size_t ws_bytes, float* ratio, msn_stream_t stream) {
     LW_REQUIRE_COMMON("msn_lars_step_dev");
     MSN_REQUIRE(hyper && (reinterpret_cast<uintptr_t>(hyper) & 7) == 0, "msn_lars_step_dev: null or misaligned hyper block");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const LarsTensor* tab = static_cast<const LarsTensor*>(table);
-    const LarsHyperDev* hd = static_cast<const LarsHyperDev*>(hyper);
-    const int gx = lw_grid_x(n_tensors, max_numel);
-    double* part = static_cast<double*>(ws);
-    hipLaunchKernelGGL(lars_norms_kernel, dim3(gx, n_tensors), dim3(kLwThreads), 0, st, tab, gx, part);
-    hipLaunchKernelGGL(lars_finish_kernel, dim3(n_tensors), dim3(kLwThreads), 0, st, part, gx, 0.0, 0.0, 0.0, hd, ratio);
-    hipLaunchKernelGGL(lars_apply_kernel, dim3(gx, n_tensors), dim3(kLwThreads), 0, st, tab, gx, LarsHyper{}, &hd->h,
-                       nesterov ? 1 : 0, 0, ratio);
+    lars_launch(table, n_tensors, max_numel, LarsHyper{}, 0.0, 0.0, 0.0, static_cast<const LarsHyperDev*>(hyper), nesterov, 0, ws,
+                ratio, static_cast<hipStream_t>(stream));
     MSN_LAUNCH_CHECK();
     return MSN_OK;
 }

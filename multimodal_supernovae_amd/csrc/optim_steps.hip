@@ -9,18 +9,11 @@
 #include <algorithm>
 #include <cstddef>
 
-#include "msn_common.h"
+#include "multi_tensor.h"
 
 namespace msn {
 
-struct MomentTensor {  // 5 x 8 bytes, uploaded by the host as int64 words: the record of RAdam, Adam and AdamW
-    float* p;
-    const float* g;
-    float* m;
-    float* v;
-    int64_t n;
-};
-
+// The records MomentTensor and SgdTensor are multi_tensor.h's (shared with optim_layerwise.hip); its geometry is not used here:
 static inline unsigned grid_x(int64_t max_numel) {   // one float4 per thread, capped: a larger tensor is strided over
     const unsigned gx = (unsigned)std::min<int64_t>(cdiv(max_numel, 4 * 256), 1024);
     return gx ? gx : 1;
@@ -187,13 +180,6 @@ __global__ void adam_kernel(const MomentTensor* __restrict__ table, AdamHyper h,
 }
 
 // ---- SGD -------------------------------------------------------------------------------------------------------------------------
-struct SgdTensor {  // 4 x 8 bytes; buf == NULL: no momentum buffer (momentum == 0)
-    float* p;
-    const float* g;
-    float* buf;
-    int64_t n;
-};
-
 struct SgdHyper {
     float lr, momentum, omd /* 1 - dampening */, weight_decay;
 };

@@ -1,6 +1,6 @@
 // Weight averaging over training (pl.callbacks.WeightAveraging / torch.optim.swa_utils.AveragedModel): ONE multi-tensor launch per
 // optimizer step over every trainable parameter instead of torch._foreach_lerp_ on stock ATen.  A device table of per-tensor
-// descriptors {avg*, p*, numel} (blockIdx.y = tensor), the idiom of grad_accum.hip, grad_clip.hip and the RAdam step (optim_steps.hip):
+// descriptors {avg*, p*, numel} (blockIdx.y = tensor) with the geometry and the pass loop of multi_tensor.h:
 // a float4 path when both pointers of a tensor are 16-byte aligned, a scalar path otherwise.  Reads avg and p, writes avg: 12 B
 // per element (swap: 16 B).  Per element, each line ONE rounding, so the result is defined bit for bit:
 //   n_averaged == 0:   avg = p                                  a copy of the bits (NaN payloads, infinities, -0.0, denormals)
@@ -12,9 +12,7 @@
 // not by the `active` word the host writes on the replaying stream in front of a replay, and the count advances on the device
 // (a one-thread finishing kernel BEHIND the main one on the same stream -- no block writes state while others read it), as
 // RAdam's step count does (radam_prepare_kernel).
-#include <algorithm>
-
-#include "msn_common.h"
+#include "multi_tensor.h"
 
 namespace msn {
 
@@ -24,16 +22,7 @@ struct AvgTensor {  // 3 x 8 bytes, uploaded by the host as int64 words
     int64_t n;
 };
 
-constexpr int kAvgThreads = 256;
-constexpr int kAvgUnroll = 4;                                           // float4 loads per operand, lane and pass
-constexpr int64_t kAvgBlockElems = 4LL * kAvgThreads * kAvgUnroll;      // elements one block covers per pass
-static_assert(kAvgUnroll == 4, "avg_tensor names its four registers per operand");
-
-// Blocks per tensor (grid x): the rule of accum_grid_x (grad_accum.hip) and clip_grid_x (grad_clip.hip).
-static inline int avg_grid_x(int n_tensors, int64_t max_numel) {
-    const int64_t cap = std::min<int64_t>(1024, std::max<int64_t>(32, 8192 / std::max(n_tensors, 1)));
-    return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(max_numel, kAvgBlockElems), cap));
-}
+static_assert(kMtUnroll == 4, "avg_tensor names its four registers per operand");
 
 enum { kAvgCopy = 0, kAvgLerp = 1, kAvgSwap = 2 };
 
@@ -63,16 +52,15 @@ __device__ __forceinline__ void avg_store(float4* a4, float4* p4, int64_t i, int
 
 template <int OP>
 __device__ __forceinline__ void avg_tensor(const AvgTensor& t, int gx, float w) {
-    const int nb = (int)std::min<int64_t>((t.n + kAvgBlockElems - 1) / kAvgBlockElems, (int64_t)gx);
+    const int nb = mt_blocks(t.n, gx);
     if ((int)blockIdx.x >= nb) return;
     const uintptr_t bits = reinterpret_cast<uintptr_t>(t.avg) | reinterpret_cast<uintptr_t>(t.p);
     const int64_t n4 = (bits & 15) == 0 ? t.n / 4 : 0;
     float4* a4 = reinterpret_cast<float4*>(t.avg);
     float4* p4 = reinterpret_cast<float4*>(t.p);
     // (four named registers per operand, not arrays: hipcc kept float4 arrays of this loop in scratch memory)
-    for (int64_t base = (int64_t)blockIdx.x * (kAvgThreads * kAvgUnroll); base < n4;
-         base += (int64_t)nb * (kAvgThreads * kAvgUnroll)) {
-        const int64_t i0 = base + threadIdx.x, i1 = i0 + kAvgThreads, i2 = i1 + kAvgThreads, i3 = i2 + kAvgThreads;
+    mt_passes(n4, nb, [&](int64_t i0) {
+        const int64_t i1 = i0 + kMtThreads, i2 = i1 + kMtThreads, i3 = i2 + kMtThreads;
         float4 v0, v1, v2, v3, a0, a1, a2, a3;
         avg_load<OP>(a4, p4, i0, n4, a0, v0);
         avg_load<OP>(a4, p4, i1, n4, a1, v1);
@@ -82,8 +70,8 @@ __device__ __forceinline__ void avg_tensor(const AvgTensor& t, int gx, float w) 
         avg_store<OP>(a4, p4, i1, n4, a1, v1, w);
         avg_store<OP>(a4, p4, i2, n4, a2, v2, w);
         avg_store<OP>(a4, p4, i3, n4, a3, v3, w);
-    }
-    for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * kAvgThreads + threadIdx.x; i < t.n; i += (int64_t)nb * kAvgThreads) {
+    });
+    for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * kMtThreads + threadIdx.x; i < t.n; i += (int64_t)nb * kMtThreads) {
         const float v = t.p[i];
         if constexpr (OP == kAvgLerp) {
             t.avg[i] = lerp1(t.avg[i], v, w);
@@ -97,8 +85,8 @@ __device__ __forceinline__ void avg_tensor(const AvgTensor& t, int gx, float w) 
     }
 }
 
-__global__ __launch_bounds__(kAvgThreads) void weight_avg_kernel(const AvgTensor* __restrict__ table, int gx, int mode, float weight,
-                                                                 const long long* __restrict__ state) {
+__global__ __launch_bounds__(kMtThreads) void weight_avg_kernel(const AvgTensor* __restrict__ table, int gx, int mode, float weight,
+                                                                const long long* __restrict__ state) {
     const AvgTensor t = table[blockIdx.y];
     if (mode == MSN_AVG_SWAP) {
         avg_tensor<kAvgSwap>(t, gx, 0.f);
@@ -124,16 +112,15 @@ using namespace msn;
 extern "C" int msn_weight_average(const void* table, int n_tensors, int64_t max_numel, int mode, float weight, long long* state,
                                   msn_stream_t stream) {
     MSN_REQUIRE(table, "msn_weight_average: null table");
-    MSN_REQUIRE(n_tensors > 0 && n_tensors <= 65535, "msn_weight_average: n_tensors must be in 1..65535 (got %d)", n_tensors);
-    MSN_REQUIRE(max_numel >= 0, "msn_weight_average: negative max_numel");
+    MSN_REQUIRE_TABLE("msn_weight_average", n_tensors, max_numel);
     MSN_REQUIRE(mode == MSN_AVG_EMA || mode == MSN_AVG_SWA || mode == MSN_AVG_SWAP,
                 "msn_weight_average: mode must be MSN_AVG_EMA, MSN_AVG_SWA or MSN_AVG_SWAP (got %d)", mode);
     MSN_REQUIRE(mode != MSN_AVG_EMA || (weight >= 0.f && weight <= 1.f),
                 "msn_weight_average: the EMA weight 1 - decay must lie in [0, 1] (got %g)", (double)weight);
     MSN_REQUIRE(mode == MSN_AVG_SWAP || state, "msn_weight_average: null state in an averaging mode");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int gx = avg_grid_x(n_tensors, max_numel);
-    hipLaunchKernelGGL(weight_avg_kernel, dim3(gx, n_tensors), dim3(kAvgThreads), 0, st, static_cast<const AvgTensor*>(table), gx,
+    const int gx = mt_grid_x(n_tensors, max_numel);
+    hipLaunchKernelGGL(weight_avg_kernel, dim3(gx, n_tensors), dim3(kMtThreads), 0, st, static_cast<const AvgTensor*>(table), gx,
                        mode, weight, static_cast<const long long*>(state));
     MSN_LAUNCH_CHECK();
     if (mode != MSN_AVG_SWAP) {

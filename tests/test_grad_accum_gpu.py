@@ -17,12 +17,12 @@ pytestmark = pytest.mark.gpu
 TK = dict(n_out=8, emb=16, heads=4, depth=2, dropout=0.0, time_norm=20583.37, agg="mean")
 SK = dict(n_out=8, emb=8, heads=2, depth=2, dropout=0.0, time_norm=17945.14, agg="mean")
 COMBOS = ["lightcurve", "spectral"]
-PASS = 4 * 256 * 4                    # elements one block covers per pass (kAccumBlockElems of csrc/grad_accum.hip)
+PASS = 4 * 256 * 4                    # elements one block covers per pass (kMtBlockElems of csrc/multi_tensor.h)
 GUARD, SENTINEL = 8, -12345.0         # floats in front of and behind every tensor that no launch may touch
 
 
 def _cap(n_tensors):
-    """Blocks per tensor of a table of n_tensors (accum_grid_x's cap, the rule of clip_grid_x)."""
+    """Blocks per tensor of a table of n_tensors (the cap of mt_grid_x, csrc/multi_tensor.h)."""
     return min(1024, max(32, 8192 // n_tensors))
 
 

@@ -46,6 +46,24 @@ def test_grad_norm_refuses_bad_arguments():
         assert rc == 1 and msg in lib.msn_last_error(), (args, lib.msn_last_error())
 
 
+def test_multi_tensor_geometry_through_the_workspace_sizes():
+    """mt_grid_x of csrc/multi_tensor.h, as the two entry points that size caller-owned scratch from it expose it: one fp64 partial
+    per block for the gradient norm, two for the layer-wise steps, whose size is an envelope that never shrinks with n or m."""
+    lib = _lib()
+
+    def gx(n, m):
+        return max(1, min(-(-m // 4096), min(1024, max(32, 8192 // n))))
+
+    points = {(3, 5000): 48, (8, 0): 64, (40, 200_000): 15_680, (301, 300_001): 77_056, (1, 10**9): 8_192,
+              (65_535, 10**7): 16_776_960}
+    for (n, m), want in points.items():
+        assert n * gx(n, m) * 8 == want
+        assert lib.msn_grad_norm_workspace_bytes(n, m) == want, (n, m)
+        assert lib.msn_layerwise_workspace_bytes(n, m) == 2 * want, (n, m)
+    assert 100 * gx(100, 10**6) * 16 == 129_600 and lib.msn_layerwise_workspace_bytes(100, 10**6) == 131_072    # the envelope
+    assert lib.msn_grad_norm_workspace_bytes(100, 10**6) == 64_800
+
+
 def test_grad_scale_and_clamp_refuse_bad_arguments():
     lib = _lib()
     for args, msg in [((None, 2, 10, FAKE, None), b"null"), ((FAKE, 2, 10, None, None), b"null"),

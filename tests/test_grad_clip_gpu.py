@@ -52,16 +52,32 @@ def _headline_params():
 
 
 SIZES = [1, 3, 5, 1023, 4097]
+# The "small" table of tests/test_grad_accum_gpu.py: 301 tensors put mt_grid_x's cap (csrc/multi_tensor.h) at its minimum of 32
+# blocks per tensor, and 32 x kMtBlockElems (4096) < 300 001, so every block of the large tensor takes three passes.
+CAPPED = [1 + (7 * i) % 61 for i in range(300)] + [300_001]
+SECOND_PASS = 32 * 4096                 # the first element of the large tensor that a block reaches in its second pass
+
+
+def _capped_params(where, seed):
+    """CAPPED with every gradient 16-byte aligned ("capped"), or tensor 5 one float and the large one three floats off."""
+    offsets = [0] * len(CAPPED)
+    if where == "capped_misaligned":
+        offsets[5], offsets[300] = 1, 3
+    params = _params(CAPPED, seed=seed, offsets=offsets)
+    assert [p.grad.data_ptr() % 16 for p in (params[5], params[300])] == ([4, 12] if where == "capped_misaligned" else [0, 0])
+    return params
 
 
 @pytest.mark.parametrize("norm_type", [1.0, 2.0, math.inf])
-@pytest.mark.parametrize("where", ["sizes", "misaligned", "headline"])
+@pytest.mark.parametrize("where", ["sizes", "misaligned", "headline", "capped", "capped_misaligned"])
 @pytest.mark.parametrize("below", [True, False])
 def test_clip_grad_norm_matches_torch_fp64(norm_type, where, below):
     from multimodal_supernovae_amd import optim
     if where == "headline":
         params = _headline_params()
         assert sum(p.numel() for p in params) > 20_000_000
+    elif where.startswith("capped"):
+        params = _capped_params(where, seed=8)
     elif where == "misaligned":
         params = _params(SIZES + [70000], seed=1, offsets=[1, 2, 3, 1, 2, 3])
         assert any(p.grad.data_ptr() % 16 for p in params)
@@ -128,13 +144,20 @@ def test_clip_grad_value_is_torch_clamp_bit_for_bit(clip_value):
     params[5].grad[11] = math.nan
     params[5].grad[12] = math.inf
     params[3].grad[0] = -math.inf
-    want = [torch.clamp(p.grad.cpu(), -clip_value, clip_value) for p in params]
-    assert optim.clip_grad_value_(params, clip_value) is None
-    for p, w in zip(params, want):
-        got = p.grad.cpu()
-        assert torch.equal(torch.isnan(got), torch.isnan(w))
-        keep = ~torch.isnan(w)
-        assert torch.equal(got[keep].view(torch.int32), w[keep].view(torch.int32))
+    tables = [params]
+    for where in ("capped", "capped_misaligned"):                       # the planted values sit in the large tensor's second pass
+        params = _capped_params(where, seed=9)
+        large = params[300].grad
+        large[SECOND_PASS + 5], large[SECOND_PASS + 4102], large[SECOND_PASS + 70_001] = math.nan, math.inf, -math.inf
+        tables.append(params)
+    for params in tables:
+        want = [torch.clamp(p.grad.cpu(), -clip_value, clip_value) for p in params]
+        assert optim.clip_grad_value_(params, clip_value) is None
+        for p, w in zip(params, want):
+            got = p.grad.cpu()
+            assert torch.equal(torch.isnan(got), torch.isnan(w))
+            keep = ~torch.isnan(w)
+            assert torch.equal(got[keep].view(torch.int32), w[keep].view(torch.int32))
 
 
 def test_clipping_is_deterministic_and_skips_parameters_without_gradient():

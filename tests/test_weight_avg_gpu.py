@@ -23,13 +23,13 @@ from conftest import ROOT
 pytestmark = pytest.mark.gpu
 
 EMA, SWA, SWAP = 0, 1, 2              # MSN_AVG_* of include/msn_hip.h
-PASS = 4 * 256 * 4                    # elements one block covers per pass (kAvgBlockElems of csrc/weight_avg.hip)
+PASS = 4 * 256 * 4                    # elements one block covers per pass (kMtBlockElems of csrc/multi_tensor.h)
 GUARD, SENTINEL = 8, -12345.0         # floats in front of and behind every tensor that no launch may touch
 ALIGN = ["aligned", "avg", "p", "both"]          # which operand is a view one element into an aligned buffer
 
 
 def _cap(n_tensors):
-    """Blocks per tensor of a table of n_tensors (avg_grid_x's cap, the rule of accum_grid_x)."""
+    """Blocks per tensor of a table of n_tensors (the cap of mt_grid_x, csrc/multi_tensor.h)."""
     return min(1024, max(32, 8192 // n_tensors))
 
 
