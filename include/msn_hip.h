@@ -998,6 +998,52 @@ int msn_pair_alignment(const float* X, int64_t ldx, const float* Y, int64_t ldy,
                        double* d2_rows_or_null, void* ws, size_t ws_bytes, msn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Alignment + uniformity as a training loss (loss.py, embedding_metrics.py; csrc/uniformity_loss.hip).
+ *
+ * Row field: X (Nx, D) and Y (Ny, D) fp32, row strides ldx, ldy >= D, 4-byte aligned (every load is a 4-byte load), Y may alias
+ *   X.  With w_ij = exp(-t d2_ij), d2_ij and exp exactly as msn_pair_potential forms them (the same bits), over the rows j of Y
+ *   but j == i + self_offset (self_offset >= 0; -1 leaves nothing out):
+ *     r (Nx) fp64        r_i  = sum_j w_ij
+ *     F (Nx, D) fp64     F_ic = fma(r_i, x_ic, -M_ic),  M_ic = sum_j w_ij y_jc      (= sum_j w_ij (x_ic - y_jc), dense rows)
+ *   M is a second product on the fp64 matrix instruction chained behind the scores: the 64 x 64 tile of w goes through LDS and
+ *   becomes the A operand, the Y tile is staged again chunk by chunk, the 64 x D accumulator stays in registers.  The Nx x Ny
+ *   matrix is never written; a row past Nx is never written, a row past Ny contributes nothing.
+ *   Plan: workgroup (ti, s) owns row tile ti and the column tiles s per .. (s + 1) per - 1 with TI = ceil(Nx / 64),
+ *   TJ = ceil(Ny / 64), per = ceil(TJ / min(TJ, ceil(512 / TI))), slabs = ceil(TJ / per): a function of (Nx, Ny), no device
+ *   query.  Per-slab partials sit in `ws` (msn_pair_field_workspace_bytes = 8 slabs Nx (D + 1) bytes); the finishing launch adds
+ *   them in slab order.
+ *     A_f(Nx, Ny) = 64 per + slabs
+ *   is the largest number of additions any single term passes through on its way to r_i or M_ic (4 per matrix instruction, 16
+ *   instructions per column tile; r's own chain is shorter).  The terms of r_i are non-negative: r_i carries a relative error of
+ *   A_f 2^-53 from the summation; M_ic one of A_f 2^-53 sum_j w_ij |y_jc|; F_ic one more rounding (the fma).
+ *   Two launches, no atomics, no fills: the same bits on every run and for every stride or alignment.  Non-finite inputs are
+ *   not checked and propagate.
+ *   MSN_ERR_SHAPE before any launch: D outside 1..256, Nx or Ny < 1 or >= 2^31, t not finite or <= 0, self_offset < -1, a null
+ *   pointer, a row stride below D, a workspace that is too small.
+ * Loss, N >= 2 partner rows: L = (1 / N) sum_i |x_i - y_i|^alpha + lam / 2 (U_x + U_y), U = log(2 S / (N (N - 1))),
+ *   S = sum_i r_i / 2 with r_x, r_y the fields of X and of Y against themselves with self_offset 0.
+ *   Forward (two launches): d2_i by fma in column order and the three sums over the rows in the order of msn_pair_alignment
+ *   (thread u of workgroup b adds the rows (b + k blocks) 256 + u; the xor tree, the four waves in order; one finishing workgroup
+ *   likewise).  loss (1 float) is rounded once from fp64; comp (5 doubles) = (align, U_x, U_y, S_x, S_y); d2_rows (N doubles) is
+ *   kept for the backward.  ws: msn_align_uniform_workspace_bytes(N) = 24 min(ceil(N / 256), 1024) bytes.
+ *   Backward (one launch), from the saved F_x, F_y (N, D dense), d2_rows, comp and the device scalar g (1 float):
+ *     dX_ic = fl32(g (k_i (x_ic - y_ic) - lam t Fx_ic / S_x)),  dY_ic = fl32(g (-k_i (x_ic - y_ic) - lam t Fy_ic / S_y)),
+ *   k_i = 2 / N (alpha 2) or 1 / (N sqrt(d2_i)) (alpha 1; 0 where d2_i == 0), evaluated in fp64.  S == 0 (every w underflowed)
+ *   is not checked: U is -inf and the gradient is not finite.  No host read: the step records into a graph.
+ *   MSN_ERR_SHAPE before any launch: D outside 1..256, N < 2 or >= 2^31, alpha not 1 or 2, lam negative or not finite, t not
+ *   finite or <= 0 (backward), a null pointer, a row stride below D, a workspace that is too small. */
+size_t msn_pair_field_workspace_bytes(int64_t Nx, int64_t Ny, int D);
+int msn_pair_field(const float* X, int64_t ldx, int64_t Nx, const float* Y, int64_t ldy, int64_t Ny, int D, double t,
+                   int64_t self_offset, double* r, double* F, void* ws, size_t ws_bytes, msn_stream_t stream);
+size_t msn_align_uniform_workspace_bytes(int64_t N);
+int msn_align_uniform_fwd(const float* X, int64_t ldx, const float* Y, int64_t ldy, int64_t N, int D, const double* r_x,
+                          const double* r_y, int alpha, double lam, float* loss, double* comp, double* d2_rows, void* ws,
+                          size_t ws_bytes, msn_stream_t stream);
+int msn_align_uniform_bwd(const float* X, int64_t ldx, const float* Y, int64_t ldy, int64_t N, int D, const double* F_x,
+                          const double* F_y, const double* d2_rows, const double* comp, const float* g, int alpha, double t,
+                          double lam, float* dX, int64_t lddx, float* dY, int64_t lddy, msn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Threshold-free classification metrics (metrics.py; csrc/rank_metrics.hip): one-vs-rest AUROC, average precision, binned
  * ROC / precision-recall curves and top-k accuracy from integer counts.  Shared by the four entry points: S (N, C) fp32
  * scores with row stride ld >= C, 4-byte aligned (every load of S is a 4-byte load: the bits do not depend on stride or

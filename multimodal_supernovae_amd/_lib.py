@@ -151,6 +151,13 @@ SIGNATURES = {
     "msn_pair_potential": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_int, c_f64, c_int, c_ptr, c_ptr, c_size, c_ptr]),
     "msn_pair_alignment_workspace_bytes": (c_size, [c_i64, c_int]),
     "msn_pair_alignment": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "msn_pair_field_workspace_bytes": (c_size, [c_i64, c_i64, c_int]),
+    "msn_pair_field": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_int, c_f64, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "msn_align_uniform_workspace_bytes": (c_size, [c_i64]),
+    "msn_align_uniform_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_int, c_f64, c_ptr, c_ptr, c_ptr,
+                                      c_ptr, c_size, c_ptr]),
+    "msn_align_uniform_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_f64,
+                                      c_f64, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
     "msn_rank_counts_workspace_bytes": (c_size, [c_i64, c_int]),
     "msn_rank_counts": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "msn_threshold_counts": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),

@@ -5,6 +5,9 @@ al. 2022), effective rank / RankMe (Garrido et al. 2023), and recall@k, MRR and 
                       the two pair sums in fp64 on the device (csrc/embedding_metrics.hip: msn_pair_potential sums
                       exp(-t d^2) and d^2 over all pairs without writing the N x N matrix; msn_pair_alignment sums d^2 and d
                       over partner rows).  Enqueue only.
+    pair_field        per row r_i = sum_j exp(-t d^2_ij) and F_i = sum_j exp(-t d^2_ij) (x_i - y_j) in fp64 on the device
+                      (csrc/uniformity_loss.hip: msn_pair_field, a second fp64 matrix product behind the scores): what the
+                      gradient of the uniformity needs (loss.align_uniform_loss).  D <= 256.  Enqueue only.
     uniformity, cross_uniformity, alignment
                       the figures of one call: one host copy each
     covariance_spectrum, effective_rank, participation_ratio, modality_gap
@@ -12,12 +15,12 @@ al. 2022), effective rank / RankMe (Garrido et al. 2023), and recall@k, MRR and 
     recall_at_k, mean_reciprocal_rank, median_rank, retrieval_metrics
                       over the integer ranks of utils.retrieval_ranks
     EmbeddingMetrics  reset / update(e1, e2) / compute() over a validation epoch
-    pair_potential_reference, pair_alignment_reference
-                      numpy longdouble restatements of the two kernels, importable without a GPU
+    pair_potential_reference, pair_alignment_reference, pair_field_reference
+                      numpy longdouble restatements of the kernels, importable without a GPU
 
 No scipy or scikit-learn at run time.  Nothing here issues a collective: with several ranks, gather the embeddings before the
-call, as for a kNN probe.  Not built: CKA, gradients of the alignment and uniformity losses, collectives, sample weights,
-D > 1024.
+call, as for a kNN probe.  Not built: CKA, collectives, sample weights, D > 1024; of the alignment + uniformity loss
+(loss.align_uniform_loss): D > 256, global negatives across ranks, alpha other than 1 and 2.
 """
 import numpy as np
 import torch
@@ -164,6 +167,35 @@ def pair_alignment_reference(X, Y):
     return d2.sum(), np.sqrt(d2).sum(), d2
 
 
+def _self_offset(exclude_self, self_offset):
+    off = (0 if exclude_self else -1) if self_offset is None else int(self_offset)
+    if off < -1:
+        raise ValueError(f"pair_field: self_offset must be -1 (no pair left out) or >= 0 (got {off})")
+    return off
+
+
+def pair_field_reference(X, Y=None, t=2.0, exclude_self=True, self_offset=None):
+    """numpy longdouble restatement of msn_pair_field in the direct form: r_i = sum_j w_ij and F_i = sum_j w_ij (x_i - y_j),
+    w_ij = exp(-t sum_c (x_ic - y_jc)^2), over the rows j of Y (X itself when None) but j == i + self_offset.  -> (r (Nx),
+    F (Nx, D))."""
+    X = np.asarray(X, dtype=np.float32).astype(np.longdouble)
+    Y = X if Y is None else np.asarray(Y, dtype=np.float32).astype(np.longdouble)
+    if X.ndim != 2 or Y.ndim != 2 or X.shape[1] != Y.shape[1]:
+        raise ValueError(f"pair_field_reference: X (Nx, D) and Y (Ny, D) needed (got {X.shape} and {Y.shape})")
+    off = _self_offset(exclude_self, self_offset)
+    t = np.longdouble(t)
+    r = np.zeros(len(X), dtype=np.longdouble)
+    F = np.zeros(X.shape, dtype=np.longdouble)
+    for i, x in enumerate(X):
+        diff = x - Y
+        w = np.exp(-t * (diff ** 2).sum(axis=1))
+        if off >= 0 and i + off < len(Y):
+            w[i + off] = 0
+        r[i] = w.sum()
+        F[i] = (w[:, None] * diff).sum(axis=0)
+    return r, F
+
+
 # ------------------------------------------------------------------------------------------------------ device halves
 def _out2(out, device, who):
     if out is None:
@@ -220,6 +252,35 @@ def pair_alignment(X, Y, out=None, rows=False):
     check(L.msn_pair_alignment(ptr(X), ld(X), ptr(Y), ld(Y), N, D, ptr(out), ptr(d2), ptr(ws), ws.numel(), stream_ptr()),
           "msn_pair_alignment")
     return (out, d2) if rows else out
+
+
+def pair_field(X, Y=None, t=2.0, exclude_self=True, *, self_offset=None, out=None):
+    """(r (Nx) fp64, F (Nx, D) fp64) on the device: r_i = sum_j w_ij and F_i = r_i x_i - sum_j w_ij y_j = sum_j w_ij (x_i - y_j)
+    with w_ij = exp(-t d2_ij) over the rows j of Y (X itself when None), d2 as pair_potential forms it (msn_pair_field).
+    exclude_self leaves the pair (i, i) out; self_offset, where given, overrides it: the pair (i, i + self_offset), -1 for none.
+    out: (r, F) to write into; rows of F past Nx are left alone.  D <= 256.  Enqueue only."""
+    X = rows_on_gpu(X, "pair_field", "embeddings")
+    Y = X if Y is None else rows_on_gpu(Y, "pair_field", "embeddings")
+    if Y.device != X.device:
+        raise _lib.MsnHipError("pair_field: X and Y must live on the same GPU")
+    if Y.shape[1] != X.shape[1]:
+        raise ValueError(f"pair_field: X has {X.shape[1]} columns, Y {Y.shape[1]}")
+    off = _self_offset(exclude_self, self_offset)
+    (Nx, D), Ny = X.shape, Y.shape[0]
+    if out is None:
+        r = torch.empty(Nx, dtype=torch.float64, device=X.device)
+        F = torch.empty((Nx, D), dtype=torch.float64, device=X.device)
+    else:
+        r, F = out
+        for name, a, shape in (("r", r, (Nx,)), ("F", F, (Nx, D))):
+            if a.dtype != torch.float64 or a.device != X.device or not a.is_contiguous() or a.dim() != len(shape) or \
+                    a.shape[0] < Nx or tuple(a.shape[1:]) != shape[1:]:
+                raise ValueError(f"pair_field: out {name} must be a contiguous float64 tensor of at least {shape} on {X.device}")
+    L = lib()
+    ws = workspace(L.msn_pair_field_workspace_bytes(Nx, Ny, D), X.device)
+    check(L.msn_pair_field(ptr(X), ld(X), Nx, ptr(Y), ld(Y), Ny, D, float(t), off, ptr(r), ptr(F), ptr(ws), ws.numel(),
+                           stream_ptr()), "msn_pair_field")
+    return r, F
 
 
 def _unit_rows(X, who):

@@ -2,6 +2,8 @@
 
     clip_loss(embs1, embs2, logit_scale, logit_bias)               -- ref src/loss.py:14-38
     clip_loss_multimodal(embeddings, logit_scales, logit_biases)   -- ref src/loss.py:41-65
+    align_uniform_loss(embs1, embs2, alpha, t, lam), align_uniform_loss_multimodal(embeddings, alpha, t, lam)
+                                                                   -- Wang & Isola 2020: no scale, no bias (below)
 
 `logit_scale` is the LOG of the scale (the kernel exponentiates it, ref :22).  Tensors in,
 0-dim tensor out, differentiable w.r.t. both embedding matrices, the scale and the bias.
@@ -332,3 +334,147 @@ def sigmoid_loss_multimodal(embeds, logit_scales=1.0, logit_biases=2.73, *, glob
         total = total + _SigmoidPair.apply(embeds[i], embeds[j], s, b, group, sharded,
                                            (alls[i], alls[j]) if sharded else None)
     return _AllReduceSum.apply(total, group) if sharded else total
+
+
+# --------------------------------------------------------------------------- alignment + uniformity (Wang & Isola 2020)
+ALIGN_UNIFORM_MAX_D = 256
+
+
+def _align_uniform_args(embs, alpha, t, lam):
+    """The refusals of the C-ABI (msn_pair_field, msn_align_uniform_fwd / _bwd), made before anything is enqueued."""
+    import math
+    if alpha not in (1, 2):
+        raise ValueError(f"align_uniform_loss: alpha must be 2 or 1 (got {alpha!r})")
+    t, lam = float(t), float(lam)
+    if not (t > 0 and math.isfinite(t)):
+        raise ValueError(f"align_uniform_loss: t must be finite and positive (got {t})")
+    if not (lam >= 0 and math.isfinite(lam)):
+        raise ValueError(f"align_uniform_loss: lam must be finite and not negative (got {lam})")
+    if len(embs) < 2:
+        raise ValueError("align_uniform_loss_multimodal needs at least two modalities")
+    _lib.require_gpu()
+    _device_f32(*[(f"embeddings[{k}]", e) for k, e in enumerate(embs)])
+    shape = tuple(embs[0].shape)
+    if len(shape) != 2 or any(tuple(e.shape) != shape for e in embs):
+        raise ValueError(f"align_uniform_loss: (N, D) partner sets of one shape needed (got {[tuple(e.shape) for e in embs]})")
+    if shape[0] < 2:
+        raise _lib.MsnHipError(f"align_uniform_loss: N must be at least 2 (got {shape[0]}): one row has no pair")
+    if not 1 <= shape[1] <= ALIGN_UNIFORM_MAX_D:
+        raise _lib.MsnHipError(f"align_uniform_loss: D must be in 1..{ALIGN_UNIFORM_MAX_D} (got {shape[1]}); wider embeddings are "
+                               "not built")
+    return int(alpha), t, lam
+
+
+class _AlignUniform(torch.autograd.Function):
+    """Every modality pair i < j of one step as ONE node.  The row field (r, F) of each tower against itself runs once
+    (msn_pair_field); each pair adds its alignment term and lam / 2 (U_i + U_j), so a tower's uniformity and its field carry the
+    weight (m - 1) lam / 2.  Nothing is read back: the scalars S and the incoming gradient stay on the device."""
+
+    @staticmethod
+    def forward(ctx, alpha, t, lam, *embs):
+        from ._device_args import workspace
+        from .embedding_metrics import pair_field
+        m = len(embs)
+        pairs = list(_pairs(range(m), 2))
+        embs = [e.detach().contiguous() for e in embs]
+        N, D = embs[0].shape
+        dev = embs[0].device
+        L = lib()
+        fields = [pair_field(e, None, t, True) for e in embs]
+        losses, comps, d2s = [], [], []
+        for i, j in pairs:
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            comp = torch.empty(5, dtype=torch.float64, device=dev)
+            d2 = torch.empty(N, dtype=torch.float64, device=dev)
+            ws = workspace(L.msn_align_uniform_workspace_bytes(N), dev)
+            check(L.msn_align_uniform_fwd(ptr(embs[i]), embs[i].stride(0), ptr(embs[j]), embs[j].stride(0), N, D,
+                                          ptr(fields[i][0]), ptr(fields[j][0]), alpha, lam, ptr(loss), ptr(comp), ptr(d2),
+                                          ptr(ws), ws.numel(), stream_ptr()), "msn_align_uniform_fwd")
+            losses.append(loss)
+            comps.append(comp)
+            d2s.append(d2)
+        ctx.m, ctx.pairs, ctx.args = m, pairs, (alpha, t, lam)
+        ctx.save_for_backward(*embs, *[f[1] for f in fields], *comps, *d2s)
+        ctx.mark_non_differentiable(*comps)
+        total = losses[0] if len(losses) == 1 else torch.stack(losses).sum()
+        return (total, *comps)
+
+    @staticmethod
+    def backward(ctx, grad_out, *_):
+        m, pairs = ctx.m, ctx.pairs
+        P = len(pairs)
+        alpha, t, lam = ctx.args
+        s = ctx.saved_tensors
+        embs, Fs, comps, d2s = s[:m], s[m:2 * m], s[2 * m:2 * m + P], s[2 * m + P:]
+        g = grad_out.to(torch.float32).reshape(()).contiguous()
+        N, D = embs[0].shape
+        L = lib()
+        d_emb = [None] * m
+        for k, (i, j) in enumerate(pairs):
+            d1, d2 = torch.empty_like(embs[i]), torch.empty_like(embs[j])
+            check(L.msn_align_uniform_bwd(ptr(embs[i]), embs[i].stride(0), ptr(embs[j]), embs[j].stride(0), N, D, ptr(Fs[i]),
+                                          ptr(Fs[j]), ptr(d2s[k]), ptr(comps[k]), ptr(g), alpha, t, lam, ptr(d1), D, ptr(d2), D,
+                                          stream_ptr()), "msn_align_uniform_bwd")
+            d_emb[i] = d1 if d_emb[i] is None else d_emb[i].add_(d1)
+            d_emb[j] = d2 if d_emb[j] is None else d_emb[j].add_(d2)
+        return (None, None, None, *d_emb)
+
+
+def align_uniform_loss_multimodal(embeddings, alpha=2, t=2.0, lam=1.0, *, global_negatives=True, group=None,
+                                  return_components=False):
+    """Alignment + uniformity (Wang & Isola 2020) summed over the modality pairs i < j, as clip_loss_multimodal sums:
+
+        L(X, Y) = (1 / N) sum_i |x_i - y_i|^alpha + lam / 2 (U(X) + U(Y)),  U(X) = log mean_{i < j} exp(-t |x_i - x_j|^2)
+
+    for unit-norm (N, D) partner sets, N >= 2, D <= 256, alpha 2 or 1, t > 0, lam >= 0; no logit scale, no bias.  float32
+    0-dim tensor, differentiable w.r.t. every set; the gradient is the plain one (no projection onto the sphere: the
+    normalisation that made the rows has its own backward).  return_components=True adds, per pair, the fp64 device block
+    (align, U_x, U_y, S_x, S_y).
+    Data parallel: each rank's own batch is one loss under the ordinary all-reduce of the gradients (global_negatives=False);
+    uniformity over the rows gathered from every rank is not built and is refused."""
+    embeddings = list(embeddings)
+    alpha, t, lam = _align_uniform_args(embeddings, alpha, t, lam)
+    if _is_sharded(global_negatives, group):
+        raise NotImplementedError("align_uniform_loss: uniformity over the rows of every rank is not built; pass "
+                                  "global_negatives=False (each rank's batch is its own loss; the gradients are all-reduced as usual)")
+    out = _AlignUniform.apply(alpha, t, lam, *embeddings)
+    return (out[0], list(out[1:])) if return_components else out[0]
+
+
+def align_uniform_loss(e1, e2, alpha=2, t=2.0, lam=1.0, *, global_negatives=True, group=None):
+    """align_uniform_loss_multimodal of one modality pair."""
+    return align_uniform_loss_multimodal([e1, e2], alpha, t, lam, global_negatives=global_negatives, group=group)
+
+
+def align_uniform_reference(embs, alpha=2, t=2.0, lam=1.0):
+    """numpy longdouble restatement: (loss, [gradient per set]) of align_uniform_loss_multimodal, the uniformity through
+    embedding_metrics.pair_field_reference (dU/dx_i = -2 t F_i / S, S = sum_i r_i / 2).  No GPU needed."""
+    import numpy as np
+    from .embedding_metrics import pair_field_reference
+    if alpha not in (1, 2):
+        raise ValueError(f"align_uniform_reference: alpha must be 2 or 1 (got {alpha!r})")
+    X = [np.asarray(e, dtype=np.float32).astype(np.longdouble) for e in embs]
+    m, (N, _) = len(X), X[0].shape
+    if m < 2 or N < 2 or any(x.shape != X[0].shape for x in X):
+        raise ValueError("align_uniform_reference: at least two (N, D) sets of one shape with N >= 2 needed")
+    t, lam = np.longdouble(t), np.longdouble(lam)
+    loss = np.longdouble(0)
+    grads = [np.zeros(x.shape, dtype=np.longdouble) for x in X]
+    for x, g in zip(X, grads):
+        r, F = pair_field_reference(x, None, t, True)
+        S = r.sum() / 2
+        loss += (m - 1) * lam / 2 * np.log(S / (np.longdouble(N) * (N - 1) / 2))
+        g -= (m - 1) * lam * t * F / S
+    for i, j in _pairs(range(m), 2):
+        diff = X[i] - X[j]
+        d2 = (diff ** 2).sum(axis=1)
+        if alpha == 2:
+            loss += d2.sum() / N
+            k = np.full(N, np.longdouble(2) / N)
+        else:
+            d = np.sqrt(d2)
+            loss += d.sum() / N
+            k = np.where(d > 0, 1 / (N * np.where(d > 0, d, 1)), 0)
+        grads[i] += k[:, None] * diff
+        grads[j] -= k[:, None] * diff
+    return loss, grads

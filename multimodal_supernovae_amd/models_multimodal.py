@@ -113,8 +113,14 @@ class LightCurveImageCLIP(nn.Module):
                  combinations: List[str] = ("host_galaxy", "spectral"), optimizer_kwargs: Optional[Dict] = None,
                  lr: float = 1e-4, loss: str = "sigmoid", regression: bool = False, classification: bool = False,
                  n_classes: int = 5, global_negatives: bool = True, optimizer: str = "radam",
-                 embedding_metrics: bool = False):
+                 embedding_metrics: bool = False, loss_kwargs: Optional[Dict] = None):
         super().__init__()
+        loss_kwargs = dict(loss_kwargs or {})
+        if loss_kwargs and loss != "align_uniform":
+            raise ValueError(f"loss_kwargs belongs to loss='align_uniform' (got loss={loss!r})")
+        unknown = set(loss_kwargs) - {"alpha", "t", "lam"}
+        if unknown:
+            raise ValueError(f"loss_kwargs takes alpha, t and lam (got {sorted(unknown)})")
         if regression or classification:
             raise NotImplementedError("this class is the contrastive model; the supervised regression / classification "
                                       "heads are models_finetune.ClipMLP(clip_model, regression=... / classification=...)")
@@ -148,6 +154,12 @@ class LightCurveImageCLIP(nn.Module):
             meta_kwargs.setdefault("dropout", 0.0)
             self.meta_encoder = MLP(output_dim=enc_dim, **meta_kwargs)
         self.loss = loss
+        self.loss_kwargs = loss_kwargs                        # alpha, t, lam of loss="align_uniform" (loss.align_uniform_loss)
+        if loss == "align_uniform":
+            # the loss has no scale and no bias: both stay (the state_dict keeps its names) and take no gradient, so the
+            # optimizers, the accumulator, the clipper and the averager pass them by
+            self.logit_scale.requires_grad_(False)
+            self.logit_bias.requires_grad_(False)
         self.embedding_metrics = bool(embedding_metrics)      # also log alignment, uniformity, gap, rank and recall@1 per pair
         self.embs_list = None
         self.logged = {}
@@ -232,6 +244,10 @@ class LightCurveImageCLIP(nn.Module):
             from .loss import sigmoid_loss_multimodal
             return sigmoid_loss_multimodal(embs, self.logit_scale, self.logit_bias,
                                            global_negatives=self.global_negatives)
+        if self.loss == "align_uniform":
+            from .loss import align_uniform_loss_multimodal
+            with markers.range("alignment + uniformity forward"):
+                return align_uniform_loss_multimodal(embs, **self.loss_kwargs, global_negatives=self.global_negatives)
         raise ValueError(f"unknown loss {self.loss!r}")
 
     def training_step(self, batch, batch_idx):

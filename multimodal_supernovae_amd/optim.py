@@ -27,6 +27,7 @@ AveragedWeights keeps an EMA or the SWA mean of the trainable weights with one m
 (csrc/weight_avg.hip) -- what checkpoint.WeightAveraging drives from the Trainer; update_bn is torch.optim.swa_utils.update_bn.
 """
 import ctypes
+import gc
 import math
 
 import torch
@@ -648,6 +649,10 @@ class _FusedStep(torch.optim.Optimizer):
     def graph_prepare(self):
         """Call BEFORE the capture (eager): per group the device block of the hyper-parameters, the device step count and the
         pinned buffer the capture fills with the descriptor table."""
+        # A CUDAGraph that is garbage in a reference cycle is destroyed by whichever collection finds it, and torch's
+        # destructor is refused while a stream is capturing: the exception leaves a destructor and aborts the process.
+        # Collect now, as torch.cuda.graph does on entry and GraphedTrainStep before it records.
+        gc.collect()
         self._graph_ready, self._graph_hyper_captured = {}, {}
         for gi, group in enumerate(self.param_groups):
             ps = [p for p in group["params"] if p.device.type == "cuda"]
