@@ -888,6 +888,30 @@ int msn_cross_entropy_fwd(const float* logits, int64_t ld, const int64_t* target
                           msn_stream_t stream);
 int msn_cross_entropy_bwd(const float* logits, int64_t ld, const int64_t* target, const float* weight, int64_t N, int C,
                           const float* denom, const float* grad_out, float* dlogits, int64_t lddx, msn_stream_t stream);
+/* Focal loss with label smoothing (csrc/focal_loss.hip; models_finetune.py: focal_loss, cross_entropy(label_smoothing > 0)).
+ * Arguments as msn_cross_entropy_*: logits (N, C) fp32 with row stride ld, target int64 (N), weight (C) fp32 or NULL (= ones).
+ * With p = softmax(x_i), u_c = 1 - p_c and q_c = (1 - label_smoothing) [c == y_i] + label_smoothing / C,
+ *   numerator = sum_i sum_c q_c w_c u_c^gamma (-log p_c),   denom = sum_i w[y_i]      (rows with 0 <= y_i < C only)
+ * gamma = 0 is torch's cross_entropy(weight=w, label_smoothing=, reduction="mean"); label_smoothing = 0 is the multiclass
+ * focal loss w_y (1 - p_y)^gamma (-log p_y).  A target outside [0, C) takes no part and is never used as an index.
+ *   fwd: out[3] (DEVICE, fp32) = {numerator / (denom_in ? denom_in[0] : denom), denom, numerator}; all rows ignored gives nan.
+ *        pred[i] = argmax_c x[i, c] (int32; a NaN beats every number, the first index wins a tie).  ONE launch up to
+ *        N = 256 (C <= 16) / N = 4 (wider rows) -- one row per lane / wave of a 256-thread workgroup; the fp64 rows make a
+ *        larger single workgroup slower than several -- else per-block fp64 partials in `ws`
+ *        (msn_focal_loss_workspace_bytes) + one finishing block that adds them in a fixed order.
+ *   bwd: dlogits (N, C) fp32 with row stride lddx = grad_out[0] * d numerator / d logits / denom[0] (DEVICE scalars); the
+ *        rows are recomputed from the logits, rows of an ignored target are zeroed; one launch.
+ * Row arithmetic in fp64 from the fp32 logits, u and log p formed without cancellation; out and dlogits are rounded to fp32
+ * once.  No atomics: bitwise reproducible, for every row stride.
+ * MSN_ERR_SHAPE before any launch (the workspace query returns 0): C outside 2..1024, N outside 1..2^31 - 1, gamma not finite
+ * or < 0, label_smoothing outside [0, 1], a row stride below C, a null or misaligned pointer, a workspace that is too small. */
+size_t msn_focal_loss_workspace_bytes(int64_t N, int C);
+int msn_focal_loss_fwd(const float* logits, int64_t ld, const int64_t* target, const float* weight, int64_t N, int C,
+                       double gamma, double label_smoothing, const float* denom_in, int* pred, float* out, void* ws,
+                       size_t ws_bytes, msn_stream_t stream);
+int msn_focal_loss_bwd(const float* logits, int64_t ld, const int64_t* target, const float* weight, int64_t N, int C,
+                       double gamma, double label_smoothing, const float* denom, const float* grad_out, float* dlogits,
+                       int64_t lddx, msn_stream_t stream);
 /* cm[target[i], pred[i]] += 1 for every row with both in [0, C): cm a caller-owned (C, C) int32 DEVICE matrix that
  * accumulates over calls (MulticlassFBetaScore / accuracy are formed from it on the host).  Integer adds only; up to
  * C = 64 every workgroup counts in its own LDS copy and adds each non-zero cell once. */

@@ -133,6 +133,9 @@ SIGNATURES = {
     "msn_cross_entropy_workspace_bytes": (c_size, [c_i64, c_int]),
     "msn_cross_entropy_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "msn_cross_entropy_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    "msn_focal_loss_workspace_bytes": (c_size, [c_i64, c_int]),
+    "msn_focal_loss_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_f64, c_f64, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "msn_focal_loss_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_f64, c_f64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     "msn_confusion_matrix": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr]),
     "msn_regression_stats_workspace_bytes": (c_size, [c_i64]),
     "msn_regression_stats": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr]),

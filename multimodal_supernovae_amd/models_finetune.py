@@ -4,6 +4,11 @@ names where SURVEY records them.  The reference's source is not pinned line by l
 checked against a plain-PyTorch restatement in tests/test_supervised_gpu.py.
 
     cross_entropy(logits, target, weight=None)      -- F.cross_entropy(..., reduction="mean") on csrc/supervised.hip
+    focal_loss(logits, target, weight, gamma, label_smoothing)
+                                                    -- focal loss with label smoothing on csrc/focal_loss.hip (fp64 row
+                                                       arithmetic); cross_entropy(label_smoothing > 0) is its gamma = 0;
+                                                       focal_loss_reference restates it in longdouble
+    class_balanced_weights(counts, beta)            -- class weights from the effective number of samples (host)
     ClassificationMetrics / RegressionMetrics       -- device accumulators (confusion matrix / six fp64 sums); compute()
                                                        is the one host copy, its arithmetic a pure function
     ClipMLP(clip_model, classification=True | regression=True, ...)
@@ -30,28 +35,36 @@ _TOWER_ORDER = ("host_galaxy", "lightcurve", "spectral")      # LightCurveImageC
 
 
 # ------------------------------------------------------------------------------------------- cross-entropy
+def _loss_args(who, logits, target, weight):
+    """The checked (logits, target, weight) of a classification loss: float32 (N, C) logits with unit column stride on the
+    GPU, contiguous int64 targets, contiguous float32 weights or None."""
+    _lib.require_gpu()
+    if logits.dim() != 2:
+        raise ValueError(f"{who}: logits must be (N, C) (got {tuple(logits.shape)})")
+    if logits.device.type != "cuda" or logits.dtype != torch.float32:
+        raise _lib.MsnHipError(f"{who}: logits must be float32 on the GPU (got {logits.dtype} on {logits.device}); "
+                               "there is no CPU path")
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    N, C = logits.shape
+    if target.shape != (N,) or target.dtype != torch.int64 or target.device != logits.device:
+        raise ValueError(f"{who}: target must be int64 of shape ({N},) on {logits.device}")
+    target = target.contiguous()
+    if weight is not None:
+        if weight.shape != (C,):
+            raise ValueError(f"{who}: weight must have shape ({C},)")
+        weight = _f32c(weight.detach(), "weight")
+    return logits, target, weight
+
+
 class _CrossEntropy(torch.autograd.Function):
     """Returns (loss, pred): loss = this process's numerator over the denominator (its own, or the ranks' sum when
     `sharded`); pred = row arg-max (int32, no gradient)."""
 
     @staticmethod
     def forward(ctx, logits, target, weight, group, sharded):
-        _lib.require_gpu()
-        if logits.dim() != 2:
-            raise ValueError(f"cross_entropy: logits must be (N, C) (got {tuple(logits.shape)})")
-        if logits.device.type != "cuda" or logits.dtype != torch.float32:
-            raise _lib.MsnHipError(f"cross_entropy: logits must be float32 on the GPU (got {logits.dtype} on {logits.device}); "
-                                   "there is no CPU path")
-        if logits.stride(1) != 1:
-            logits = logits.contiguous()
+        logits, target, weight = _loss_args("cross_entropy", logits, target, weight)
         N, C = logits.shape
-        if target.shape != (N,) or target.dtype != torch.int64 or target.device != logits.device:
-            raise ValueError(f"cross_entropy: target must be int64 of shape ({N},) on {logits.device}")
-        target = target.contiguous()
-        if weight is not None:
-            if weight.shape != (C,):
-                raise ValueError(f"cross_entropy: weight must have shape ({C},)")
-            weight = _f32c(weight.detach(), "weight")
         dev = logits.device
         L = lib()
         lse = torch.empty(N, dtype=torch.float32, device=dev)
@@ -91,18 +104,146 @@ def _cross_entropy(logits, target, weight=None, group=None, sharded=None):
     return (_AllReduceSum.apply(share, group) if sharded else share), pred
 
 
-def cross_entropy(logits, target, weight=None, *, group=None):
-    """torch.nn.functional.cross_entropy(logits, target, weight=weight, reduction="mean") for float32 (N, C) logits on the
-    GPU (2 <= C <= 1024), int64 targets, default ignore_index -100 (any target outside [0, C) is ignored likewise).  With
-    torch.distributed initialised over more than one rank every rank passes its LOCAL rows and gets the global mean (see the
-    module docstring); gradients of the ranks are then to be summed."""
-    return _cross_entropy(logits, target, weight, group)[0]
+def cross_entropy(logits, target, weight=None, *, label_smoothing=0.0, group=None):
+    """torch.nn.functional.cross_entropy(logits, target, weight=weight, label_smoothing=label_smoothing, reduction="mean")
+    for float32 (N, C) logits on the GPU (2 <= C <= 1024), int64 targets, default ignore_index -100 (any target outside
+    [0, C) is ignored likewise).  label_smoothing = 0 takes the kernels of csrc/supervised.hip, label_smoothing > 0 the
+    focal-loss kernel at gamma = 0.  With torch.distributed initialised over more than one rank every rank passes its LOCAL
+    rows and gets the global mean (see the module docstring); gradients of the ranks are then to be summed."""
+    if float(label_smoothing) == 0.0:
+        return _cross_entropy(logits, target, weight, group)[0]
+    return _focal_loss(logits, target, weight, 0.0, label_smoothing, group)[0]
 
 
 def argmax_rows(logits):
     """Row arg-max of (N, C) logits as int32 (first maximal index, as torch.argmax) from the cross-entropy forward kernel."""
     fake = torch.zeros(logits.shape[0], dtype=torch.int64, device=logits.device)
     return _cross_entropy(logits.detach(), fake, sharded=False)[1]
+
+
+# ------------------------------------------------------------------------- focal loss and label smoothing
+def _focal_params(who, gamma, label_smoothing):
+    gamma, label_smoothing = float(gamma), float(label_smoothing)
+    if not (0.0 <= gamma < float("inf")):
+        raise ValueError(f"{who}: gamma must be finite and >= 0 (got {gamma})")
+    if not (0.0 <= label_smoothing <= 1.0):
+        raise ValueError(f"{who}: label_smoothing must be in [0, 1] (got {label_smoothing})")
+    return gamma, label_smoothing
+
+
+class _FocalLoss(torch.autograd.Function):
+    """_CrossEntropy's contract on csrc/focal_loss.hip: returns (loss, pred), loss = this process's numerator over the
+    denominator (its own, or the ranks' sum when `sharded`).  Backward recomputes the rows: nothing per row is saved."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, gamma, label_smoothing, group, sharded):
+        logits, target, weight = _loss_args("focal_loss", logits, target, weight)
+        N, C = logits.shape
+        dev = logits.device
+        L = lib()
+        pred = torch.empty(N, dtype=torch.int32, device=dev)
+        out = torch.empty(3, dtype=torch.float32, device=dev)              # {loss, denominator, numerator}
+        nb = L.msn_focal_loss_workspace_bytes(N, C)
+        ws = workspace(nb, dev) if nb else None
+        check(L.msn_focal_loss_fwd(ptr(logits), logits.stride(0), ptr(target), ptr(weight), N, C, gamma, label_smoothing,
+                                   ptr(None), ptr(pred), ptr(out), ptr(ws), nb, stream_ptr()), "msn_focal_loss_fwd")
+        if sharded:
+            denom = D.all_reduce_sum(out[1].clone(), group, kind="loss_denominator_all_reduce")
+            loss = out[2] / denom                                          # this rank's share of the global mean
+        else:
+            denom, loss = out[1], out[0]
+        ctx.save_for_backward(logits, target, weight, denom)
+        ctx.focal = (gamma, label_smoothing)
+        ctx.mark_non_differentiable(pred)
+        ctx.set_materialize_grads(False)
+        return loss, pred
+
+    @staticmethod
+    def backward(ctx, g, _gpred):
+        if g is None:
+            return (None,) * 7
+        logits, target, weight, denom = ctx.saved_tensors
+        N, C = logits.shape
+        g = g.to(torch.float32).reshape(()).contiguous()
+        dx = torch.empty((N, C), dtype=torch.float32, device=logits.device)
+        check(lib().msn_focal_loss_bwd(ptr(logits), logits.stride(0), ptr(target), ptr(weight), N, C, *ctx.focal, ptr(denom),
+                                       ptr(g), ptr(dx), C, stream_ptr()), "msn_focal_loss_bwd")
+        return (dx,) + (None,) * 6
+
+
+def _focal_loss(logits, target, weight, gamma, label_smoothing, group=None, sharded=None):
+    gamma, label_smoothing = _focal_params("focal_loss", gamma, label_smoothing)
+    if sharded is None:
+        sharded = D.world_size(group) > 1
+    share, pred = _FocalLoss.apply(logits, target, weight, gamma, label_smoothing, group, bool(sharded))
+    return (_AllReduceSum.apply(share, group) if sharded else share), pred
+
+
+def focal_loss(logits, target, weight=None, gamma=2.0, label_smoothing=0.0, *, group=None):
+    """Multiclass focal loss (Lin et al. 2017) with label smoothing, mean over the rows with a target in [0, C):
+
+        sum_i sum_c q_ic w_c (1 - p_ic)^gamma (-log p_ic) / sum_i w[y_i],    q_ic = (1 - label_smoothing) [c == y_i] + label_smoothing / C
+
+    for float32 (N, C) logits on the GPU (2 <= C <= 1024), int64 targets and optional class weights.  gamma = 0 is
+    cross_entropy(..., label_smoothing=label_smoothing); label_smoothing = 0 is w_y (1 - p_y)^gamma (-log p_y).  Data parallel
+    as cross_entropy.  Not built: soft targets, per-sample weights, the sigmoid (binary) form, reductions other than the mean."""
+    return _focal_loss(logits, target, weight, gamma, label_smoothing, group)[0]
+
+
+def focal_loss_reference(x, y, w=None, gamma=2.0, label_smoothing=0.0):
+    """(loss, dlogits) of focal_loss restated in numpy longdouble, returned as a float and a float64 (N, C) array.  u = 1 - p
+    and log p are formed as the kernel forms them -- from t = sum_{c != a} exp(x_c - m) with the leading 1 of the softmax
+    denominator kept apart -- and the target's gradient entry takes u_y itself, so a row whose target wins by 40 keeps its
+    (tiny) loss and gradient instead of rounding them to zero.  A column with coefficient q_c = 0 takes no part."""
+    import numpy as np
+    ld = np.longdouble
+    x = np.asarray(x.detach().cpu() if torch.is_tensor(x) else x, dtype=ld)
+    y = np.asarray(y.cpu() if torch.is_tensor(y) else y).astype(np.int64)
+    N, C = x.shape
+    w = np.ones(C, dtype=ld) if w is None else np.asarray(w.detach().cpu() if torch.is_tensor(w) else w, dtype=ld)
+    gamma, eps = _focal_params("focal_loss_reference", gamma, label_smoothing)
+    gamma, keep, smooth = ld(gamma), ld(1.0) - ld(eps), ld(eps) / ld(C)
+    valid = (y >= 0) & (y < C)
+    ys = np.where(valid, y, 0)
+    rows = np.arange(N)
+    with np.errstate(all="ignore"):
+        a = np.argmax(x, axis=1)                                          # first maximal index
+        m = x[rows, a]
+        top = np.arange(C)[None, :] == a[:, None]
+        d = np.where(top, ld(0), x - m[:, None])
+        e = np.where(top, ld(1), np.exp(d))
+        t = np.where(top, ld(0), e).sum(axis=1)
+        S = (ld(1) + t)[:, None]
+        nlp = np.log1p(t)[:, None] - d
+        u = np.where(top, t[:, None], S - e) / S
+        p = e / S
+        pw = np.ones_like(u) if gamma == 0 else np.power(u, gamma)
+        F = pw * (ld(1) + gamma * p * np.where(u == 0, ld(1), nlp / np.where(u == 0, ld(1), u)))
+        hot = (np.arange(C)[None, :] == ys[:, None]) & valid[:, None]
+        q = np.where(hot, keep, ld(0)) + smooth
+        den = w[ys][valid].sum()
+        terms = np.where((q != 0) & valid[:, None], q * w[None, :] * pw * nlp, ld(0))
+        loss = terms.sum() / den
+        b = -keep * w[ys] * F[rows, ys] if keep != 0 else np.zeros(N, dtype=ld)
+        s = -smooth * w[None, :] * F if smooth != 0 else np.zeros_like(F)
+        dx = b[:, None] * np.where(hot, u, -p) + s - p * s.sum(axis=1, keepdims=True)
+        dx = np.where(valid[:, None], dx, ld(0)) / den
+    return float(loss), dx.astype(np.float64)
+
+
+def class_balanced_weights(counts, beta=0.999):
+    """Class weights from the effective number of samples (Cui et al. 2019): w_c = (1 - beta) / (1 - beta^n_c), scaled to sum
+    to the number of classes; a class without samples gets weight 0.  beta = 0 weighs every class that occurs alike.  Pure
+    host function; returns a float64 tensor for ClipMLP(class_weights=) / focal_loss(weight=)."""
+    n = torch.as_tensor(counts, dtype=torch.float64).reshape(-1)
+    beta = float(beta)
+    if not (0.0 <= beta < 1.0):
+        raise ValueError(f"class_balanced_weights: beta must be in [0, 1) (got {beta})")
+    if bool((n < 0).any()) or not bool((n > 0).any()):
+        raise ValueError("class_balanced_weights: counts must be >= 0 with at least one class present")
+    seen = n > 0
+    w = torch.where(seen, (1.0 - beta) / (1.0 - torch.pow(torch.full_like(n, beta), n.clamp(min=1.0))), torch.zeros_like(n))
+    return w * (n.numel() / w.sum())
 
 
 # ------------------------------------------------------------------------------------------------- metrics
@@ -212,14 +353,30 @@ class ClipMLP(nn.Module):
     ranking_metrics=True (classification only) also feeds the validation logits to a metrics.RankingMetrics and logs
     auroc_val, ap_val (macro one-vs-rest AUROC / average precision) and top2_acc_val beside f1_val, f1_micro_val and acc_val; without it the logged keys are those three and val_loss.
     calibration_metrics=True (classification only) also feeds them to a calibration.CalibrationMetrics (softmax of the logits,
-    15 bins) and logs ece_val and brier_val (top-label expected calibration error, multi-class Brier score)."""
+    15 bins) and logs ece_val and brier_val (top-label expected calibration error, multi-class Brier score).
+    loss="focal" (classification only) trains and validates on focal_loss with loss_kwargs {"gamma": 2.0, "label_smoothing": 0.0};
+    loss="cross_entropy" (the default) takes loss_kwargs {"label_smoothing"}.  val_loss is the configured loss; the metrics and
+    the state_dict do not depend on it."""
 
     def __init__(self, clip_model, learning_rate=1e-3, regression=False, classification=False, n_classes=5, hidden_dim=128,
                  num_layers=2, dropout=0.0, freeze_backbone=False, class_weights=None, optimizer_kwargs=None,
-                 optimizer="radam", ranking_metrics=False, calibration_metrics=False):
+                 optimizer="radam", ranking_metrics=False, calibration_metrics=False, loss=None, loss_kwargs=None):
         super().__init__()
         if bool(regression) == bool(classification):
             raise ValueError("ClipMLP needs exactly one of regression=True / classification=True")
+        if regression and (loss is not None or loss_kwargs is not None):
+            raise ValueError("ClipMLP: loss / loss_kwargs belong to classification (regression trains on the MSE)")
+        loss = "cross_entropy" if loss is None else loss
+        if loss not in ("cross_entropy", "focal"):
+            raise ValueError(f"ClipMLP: loss must be 'cross_entropy' or 'focal' (got {loss!r})")
+        loss_kwargs = dict(loss_kwargs or {})
+        allowed = ("gamma", "label_smoothing") if loss == "focal" else ("label_smoothing",)
+        unknown = sorted(set(loss_kwargs) - set(allowed))
+        if unknown:
+            raise ValueError(f"ClipMLP: loss={loss!r} takes the loss_kwargs {allowed} (got {unknown})")
+        self.loss_name = loss
+        self.loss_gamma, self.label_smoothing = _focal_params("ClipMLP", loss_kwargs.get("gamma", 2.0 if loss == "focal" else 0.0),
+                                                              loss_kwargs.get("label_smoothing", 0.0))
         if "meta" in clip_model.combinations:
             raise ValueError("ClipMLP: a clip_model with the 'meta' tower reads redshift and class -- the labels; build it "
                              "without 'meta' and load the pretrained state_dict with strict=False")
@@ -318,7 +475,10 @@ class ClipMLP(nn.Module):
         out = self(*batch)
         if self.classification:
             target = batch[8].to(torch.int64).reshape(-1)
-            loss, pred = _cross_entropy(out, target, self.class_weights, self.group, sharded)
+            if self.loss_name == "focal" or self.label_smoothing != 0.0:
+                loss, pred = _focal_loss(out, target, self.class_weights, self.loss_gamma, self.label_smoothing, self.group, sharded)
+            else:
+                loss, pred = _cross_entropy(out, target, self.class_weights, self.group, sharded)
             return loss, pred, target, out
         target = batch[7].to(torch.float32).reshape(-1)
         pred = out.squeeze(1)
