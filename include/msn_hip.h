@@ -190,6 +190,34 @@ int msn_infonce_bwd(const float* E1_loc, int64_t ld1, int b1, const float* E2_lo
                     float* dE1_loc, int64_t ldd1, float* dE2_loc, int64_t ldd2, float* dscale_dbias,
                     void* ws, size_t ws_bytes, msn_stream_t stream);
 
+/* Label-aware (supervised) contrastive loss of one modality pair: SupCon (Khosla et al. 2020) in its cross-modal form, the
+ * bidirectional loss of UniCL (Yang et al. 2022).  labels_all holds the int32 label of every gathered row (n of them); a
+ * negative label is "class unknown" and makes the row a singleton class.  With S = exp(log_scale) * E2 . E1^T + bias,
+ *   P_ij = [i == j] or (y_i == y_j and y_i >= 0),   c_i = sum_j P_ij >= 1,
+ *   loss = 1/(2n) * sum_i [ LSE_j S_ij - (1/c_i) sum_j P_ij S_ij + LSE_j S_ji - (1/c_i) sum_j P_ji S_ji ]
+ *   G_ij = dloss/dS_ij = ( softmax_row(S)_ij + softmax_col(S)_ij - 2 P_ij / c_i ) / (2n)
+ *   dE2 = s G E1, dE1 = s G^T E2, dlog_scale = sum_ij G_ij (S_ij - bias), dbias = sum_ij G_ij.
+ * With all labels distinct this is msn_infonce_*.  Same row-sharded calling convention as msn_infonce_*, with b1 == b2,
+ * n1 == n2 and q_offset + b <= n (anything else is refused) and 1 <= D <= 256 (wider embeddings are not built).
+ *   fwd: lse_row, lse_col (b values each) as msn_infonce_fwd; cnt[i] = c of local row i (b int32 values, exact);
+ *        loss[0] = 1/(2n) * sum_{local i} (lse_row_i + lse_col_i - the two positive means): this rank's share.
+ *   bwd: the LSE vectors of ALL rows, the counts of the LOCAL rows and grad_out (device scalar); writes dE1_loc, dE2_loc
+ *        (complete for the local rows) and dscale_dbias[2] = this rank's share of (dlog_scale, dbias).
+ * No atomics, no zeroed scratch, the same bits on every run, no host read.  Workspace: msn_supcon_workspace_bytes (0 for
+ * a shape that is refused). */
+size_t msn_supcon_workspace_bytes(int b1, int b2, int n1, int n2, int D);
+int msn_supcon_fwd(const float* E1_loc, int64_t ld1, int b1, const float* E2_loc, int64_t ld2, int b2,
+                   const float* E1_all, int64_t ld1a, int n1, const float* E2_all, int64_t ld2a, int n2, int D,
+                   int q_offset, const int32_t* labels_all, const float* log_scale, const float* bias,
+                   float* lse_row, float* lse_col, int32_t* cnt, float* loss, void* ws, size_t ws_bytes,
+                   msn_stream_t stream);
+int msn_supcon_bwd(const float* E1_loc, int64_t ld1, int b1, const float* E2_loc, int64_t ld2, int b2,
+                   const float* E1_all, int64_t ld1a, int n1, const float* E2_all, int64_t ld2a, int n2, int D,
+                   int q_offset, const int32_t* labels_all, const float* log_scale, const float* bias,
+                   const float* lse_row_all, const float* lse_col_all, const int32_t* cnt, const float* grad_out,
+                   float* dE1_loc, int64_t ldd1, float* dE2_loc, int64_t ldd2, float* dscale_dbias, void* ws,
+                   size_t ws_bytes, msn_stream_t stream);
+
 /* SigLIP-style loss with the reference's sign convention -- sigmoid_loss, src/loss.py:68-83:
  *   Z = -(E2 . E1^T) exp(log_scale) + bias (fp32);  loss = mean_ij softplus(z_ij Z_ij) evaluated in fp64,
  *   z = +1 on the diagonal, -1 elsewhere (mean over all n x n entries).  Same row-sharded calling

@@ -4,6 +4,8 @@
     clip_loss_multimodal(embeddings, logit_scales, logit_biases)   -- ref src/loss.py:41-65
     align_uniform_loss(embs1, embs2, alpha, t, lam), align_uniform_loss_multimodal(embeddings, alpha, t, lam)
                                                                    -- Wang & Isola 2020: no scale, no bias (below)
+    supcon_loss(embs1, embs2, labels, logit_scale, logit_bias), supcon_loss_multimodal(embeddings, labels, ...)
+                                                                   -- label-aware InfoNCE (SupCon / UniCL), csrc/supcon.hip (below)
 
 `logit_scale` is the LOG of the scale (the kernel exponentiates it, ref :22).  Tensors in,
 0-dim tensor out, differentiable w.r.t. both embedding matrices, the scale and the bias.
@@ -478,3 +480,245 @@ def align_uniform_reference(embs, alpha=2, t=2.0, lam=1.0):
         grads[i] += k[:, None] * diff
         grads[j] -= k[:, None] * diff
     return loss, grads
+
+
+# --------------------------------------------------------------------------- label-aware contrastive loss (SupCon / UniCL)
+SUPCON_MAX_D = 256
+
+
+class HipSupConKernels:
+    """msn_supcon_fwd / msn_supcon_bwd through the C-ABI (the interface of HipPairKernels plus the gathered int32 labels and the
+    counts of positives of the local rows)."""
+
+    @staticmethod
+    def _ws(e1_loc, e1_all):
+        b, D = e1_loc.shape
+        n = e1_all.shape[0]
+        nb = lib().msn_supcon_workspace_bytes(b, b, n, n, D)
+        return nb, torch.empty(max(nb, 16) // 4 + 1, dtype=torch.float32, device=e1_loc.device)
+
+    @staticmethod
+    def _check(e1_loc, e2_loc, e1_all, e2_all, labels_all):
+        if labels_all.device != e1_loc.device or labels_all.dtype != torch.int32 or labels_all.dim() != 1 or labels_all.stride(0) != 1:
+            raise _lib.MsnHipError("labels (gathered) must be contiguous int32 on the embeddings' device")
+        D = e1_loc.shape[1]
+        if e2_loc.shape[1] != D or e1_all.shape[1] != D or e2_all.shape[1] != D:
+            raise _lib.MsnHipError("both modalities must share the embedding width")
+        if e1_loc.shape[0] != e2_loc.shape[0] or e1_all.shape[0] != e2_all.shape[0]:
+            raise _lib.MsnHipError("embs1 and embs2 must have the same number of rows (the label-aware loss needs b1 == b2, n1 == n2)")
+        if labels_all.numel() != e1_all.shape[0]:
+            raise _lib.MsnHipError(f"labels (gathered): {labels_all.numel()} labels for {e1_all.shape[0]} rows")
+
+    @staticmethod
+    def forward(e1_loc, e2_loc, e1_all, e2_all, labels_all, q_offset, log_scale, bias):
+        _lib.require_gpu()
+        _device_f32(("embs1", e1_loc), ("embs2", e2_loc), ("embs1 (gathered)", e1_all), ("embs2 (gathered)", e2_all),
+                    ("logit_scale", log_scale), ("logit_bias", bias))
+        HipSupConKernels._check(e1_loc, e2_loc, e1_all, e2_all, labels_all)
+        b, D = e1_loc.shape
+        n = e1_all.shape[0]
+        dev = e1_loc.device
+        nb, ws = HipSupConKernels._ws(e1_loc, e1_all)
+        lse_row = torch.empty(b, dtype=torch.float32, device=dev)
+        lse_col = torch.empty(b, dtype=torch.float32, device=dev)
+        cnt = torch.empty(b, dtype=torch.int32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        check(lib().msn_supcon_fwd(ptr(e1_loc), e1_loc.stride(0), b, ptr(e2_loc), e2_loc.stride(0), b,
+                                   ptr(e1_all), e1_all.stride(0), n, ptr(e2_all), e2_all.stride(0), n, D, q_offset,
+                                   ptr(labels_all), ptr(log_scale), ptr(bias), ptr(lse_row), ptr(lse_col), ptr(cnt), ptr(loss),
+                                   ptr(ws), nb, stream_ptr()), "msn_supcon_fwd")
+        return lse_row, lse_col, cnt, loss
+
+    @staticmethod
+    def backward(e1_loc, e2_loc, e1_all, e2_all, labels_all, q_offset, log_scale, bias, lse_row_all, lse_col_all, cnt, grad_out):
+        _lib.require_gpu()
+        _device_f32(("embs1", e1_loc), ("embs2", e2_loc), ("embs1 (gathered)", e1_all), ("embs2 (gathered)", e2_all),
+                    ("logit_scale", log_scale), ("logit_bias", bias), ("lse_row", lse_row_all), ("lse_col", lse_col_all),
+                    ("grad_out", grad_out))
+        HipSupConKernels._check(e1_loc, e2_loc, e1_all, e2_all, labels_all)
+        b, D = e1_loc.shape
+        n = e1_all.shape[0]
+        if lse_row_all.numel() < n or lse_col_all.numel() < n:
+            raise _lib.MsnHipError("backward needs the log-sum-exp of every gathered row")
+        if cnt.device != e1_loc.device or cnt.dtype != torch.int32 or cnt.numel() != b:
+            raise _lib.MsnHipError("cnt must hold one int32 count per local row on the embeddings' device")
+        lse_row_all, lse_col_all, cnt = lse_row_all.contiguous(), lse_col_all.contiguous(), cnt.contiguous()
+        dev = e1_loc.device
+        nb, ws = HipSupConKernels._ws(e1_loc, e1_all)
+        d1 = torch.empty((b, D), dtype=torch.float32, device=dev)
+        d2 = torch.empty((b, D), dtype=torch.float32, device=dev)
+        dsb = torch.empty(2, dtype=torch.float32, device=dev)
+        check(lib().msn_supcon_bwd(ptr(e1_loc), e1_loc.stride(0), b, ptr(e2_loc), e2_loc.stride(0), b,
+                                   ptr(e1_all), e1_all.stride(0), n, ptr(e2_all), e2_all.stride(0), n, D, q_offset,
+                                   ptr(labels_all), ptr(log_scale), ptr(bias), ptr(lse_row_all), ptr(lse_col_all), ptr(cnt),
+                                   ptr(grad_out), ptr(d1), D, ptr(d2), D, ptr(dsb), ptr(ws), nb, stream_ptr()),
+              "msn_supcon_bwd")
+        return d1, d2, dsb[0], dsb[1]
+
+
+def _supcon_args(embs, labels, world=1):
+    """The refusals of supcon_loss / supcon_loss_multimodal, made before anything is enqueued; each message names the argument.
+    -> the labels as they go to the device conversion.  Shapes first, label values next, devices last, so that every refusal can
+    be met without a GPU.  The value check of FLOATING labels reads the tensor and is skipped while a graph is being captured
+    (integer labels are never read)."""
+    if len(embs) < 2:
+        raise ValueError("supcon_loss_multimodal: embeddings must hold at least two modalities")
+    for k, e in enumerate(embs):
+        if not torch.is_tensor(e) or e.dim() != 2:
+            raise ValueError(f"supcon_loss: embeddings[{k}] must be a (b, D) tensor")
+    b, D = embs[0].shape
+    if any(e.shape[0] != b for e in embs):
+        raise ValueError(f"supcon_loss: embeddings must have the same batch size in every modality (got {[e.shape[0] for e in embs]}); "
+                         "a label belongs to one row of each")
+    if any(e.shape[1] != D for e in embs):
+        raise ValueError(f"supcon_loss: embeddings must share the width D (got {[e.shape[1] for e in embs]})")
+    if not 1 <= D <= SUPCON_MAX_D:
+        raise _lib.MsnHipError(f"supcon_loss: embeddings: D must be in 1..{SUPCON_MAX_D} (got {D}); wider embeddings are not built")
+    if b < 1:
+        raise ValueError("supcon_loss: embeddings must have at least one row")
+    if b * world >= 2 ** 31:
+        raise _lib.MsnHipError(f"supcon_loss: embeddings: N = {b * world} rows; N must be below 2^31")
+    if not torch.is_tensor(labels):
+        raise TypeError("supcon_loss: labels must be a tensor of b integers")
+    if labels.dim() != 1 or labels.shape[0] != b:
+        raise ValueError(f"supcon_loss: labels must have shape ({b},), one per row of the embeddings (got {tuple(labels.shape)})")
+    if labels.dtype == torch.bool or labels.is_complex():
+        raise TypeError(f"supcon_loss: labels must have an integer or floating dtype holding integers (got {labels.dtype})")
+    if labels.is_floating_point():
+        capturing = labels.is_cuda and torch.cuda.is_current_stream_capturing()
+        if not capturing and not bool(((labels == labels.round()) & (labels.abs() < 2 ** 31)).all()):
+            raise ValueError("supcon_loss: labels must hold integer values (a negative integer marks an unknown class)")
+    for k, e in enumerate(embs):
+        if e.device.type != "cuda":
+            raise _lib.MsnHipError(f"supcon_loss: embeddings[{k}] must live on the GPU (got {e.device}); the loss has no CPU path")
+        if e.dtype != torch.float32:
+            raise _lib.MsnHipError(f"supcon_loss: embeddings[{k}] must be float32 (got {e.dtype})")
+    if labels.device != embs[0].device:
+        raise _lib.MsnHipError(f"supcon_loss: labels must live on the embeddings' device {embs[0].device} (got {labels.device})")
+    return labels
+
+
+class _SupConLoss(torch.autograd.Function):
+    """supcon_loss_multimodal as ONE node, built like _MultiPairLoss: every modality pair i < j of one step with the same labels,
+    single process or row-sharded over `group`.  Sharded, the labels travel in one extra all-gather; the embeddings, the
+    log-sum-exps and the loss share travel exactly as in _MultiPairLoss, the counts stay local, and each rank ends with the
+    complete dE of its own rows."""
+
+    @staticmethod
+    def forward(ctx, scales, biases, labels, kernels, group, sharded, *embs):
+        m = len(embs)
+        pairs = list(_pairs(range(m), 2))
+        embs = [e.contiguous() for e in embs]
+        scales = scales.detach().to(torch.float32)
+        biases = biases.detach().to(torch.float32)
+        if scales.dim() > 0 and scales.numel() < len(pairs) or biases.dim() > 0 and biases.numel() < len(pairs):
+            raise ValueError(f"{len(pairs)} modality pairs need {len(pairs)} logit scales / biases (or one shared scalar)")
+        s_k = [(scales if scales.dim() == 0 else scales[k]).reshape(()).contiguous() for k in range(len(pairs))]
+        b_k = [(biases if biases.dim() == 0 else biases[k]).reshape(()).contiguous() for k in range(len(pairs))]
+        labels = labels.detach().to(torch.int32).contiguous()          # on the device: nothing is read
+        if sharded:
+            alls = gather_embeddings(embs, group)
+            labels_all = D.all_gather_rows(labels, group, kind="label_all_gather")
+            q_offset = dist.get_rank(group) * embs[0].shape[0]
+        else:
+            alls, labels_all, q_offset = embs, labels, 0
+        lses, cnts, losses = [], [], []
+        for k, (i, j) in enumerate(pairs):
+            lse_row, lse_col, cnt, loss = kernels.forward(embs[i], embs[j], alls[i], alls[j], labels_all, q_offset, s_k[k], b_k[k])
+            lses += [lse_row, lse_col]
+            cnts.append(cnt)
+            losses.append(loss)
+        total = losses[0] if len(losses) == 1 else torch.stack(losses).sum()
+        if sharded:
+            b = embs[0].shape[0]
+            world = dist.get_world_size(group)
+            pack = torch.stack(lses)                                                        # (2P, b)
+            g = D.all_gather_rows(pack.view(1, 2 * len(pairs), b), group, kind="lse_all_gather")   # (world, 2P, b)
+            lse_all = g.permute(1, 0, 2).reshape(2 * len(pairs), world * b)
+            lses = [lse_all[r] for r in range(2 * len(pairs))]
+            total = D.all_reduce_sum(total.clone(), group, kind="loss_all_reduce")
+        ctx.kernels, ctx.q_offset, ctx.pairs, ctx.m = kernels, q_offset, pairs, m
+        ctx.shapes = (scales.shape, biases.shape)
+        ctx.save_for_backward(*embs, *alls, *s_k, *b_k, *lses, *cnts, labels_all)
+        return total
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        m, pairs = ctx.m, ctx.pairs
+        P = len(pairs)
+        t = ctx.saved_tensors
+        embs, alls = t[:m], t[m:2 * m]
+        s_k, b_k = t[2 * m:2 * m + P], t[2 * m + P:2 * m + 2 * P]
+        lses, cnts, labels_all = t[2 * m + 2 * P:2 * m + 4 * P], t[2 * m + 4 * P:2 * m + 5 * P], t[-1]
+        g = grad_out.to(torch.float32).reshape(()).contiguous()
+        d_emb = [None] * m
+        d_s, d_b = [], []
+        for k, (i, j) in enumerate(pairs):
+            d1, d2, ds, db = ctx.kernels.backward(embs[i], embs[j], alls[i], alls[j], labels_all, ctx.q_offset, s_k[k], b_k[k],
+                                                  lses[2 * k], lses[2 * k + 1], cnts[k], g)
+            d_emb[i] = d1 if d_emb[i] is None else d_emb[i].add_(d1)
+            d_emb[j] = d2 if d_emb[j] is None else d_emb[j].add_(d2)
+            d_s.append(ds)
+            d_b.append(db)
+        s_shape, b_shape = ctx.shapes
+        if P == 1:
+            gs, gb = d_s[0].reshape(s_shape), d_b[0].reshape(b_shape)
+        else:
+            gs, gb = torch.stack(d_s), torch.stack(d_b)
+            gs = gs.sum() if len(s_shape) == 0 else gs
+            gb = gb.sum() if len(b_shape) == 0 else gb
+        return (gs, gb, None, None, None, None, *d_emb)
+
+
+def supcon_loss_multimodal(embeddings, labels, logit_scales=1.0, logit_biases=0.0, *, global_negatives=True, group=None,
+                           kernels=HipSupConKernels):
+    """Label-aware contrastive loss (SupCon, Khosla et al. 2020, in the cross-modal form of UniCL, Yang et al. 2022) summed over
+    the modality pairs i < j with the same labels, as clip_loss_multimodal sums.  Per pair, with S = s E_j E_i^T + b:
+
+        P_ij = [i == j] or (y_i == y_j and y_i >= 0),   c_i = sum_j P_ij
+        loss = 1/(2N) sum_i [ LSE_j S_ij - (1/c_i) sum_j P_ij S_ij  +  LSE_j S_ji - (1/c_i) sum_j P_ji S_ji ]
+
+    `labels`: (b,) integers (any integer dtype, or a floating dtype holding integers) on the embeddings' device, converted to int32
+    there (the values must fit int32).  A negative label is "class unknown": the row is a singleton class whose only positive is its partner, so it trains as a
+    plain InfoNCE row; with all labels distinct the loss is clip_loss.  `logit_scales` is the LOG of the scale.  float32 0-dim
+    tensor, differentiable w.r.t. every embedding matrix, the scales and the biases; `labels` gets no gradient.  Every modality
+    needs the same batch size, D <= 256, N < 2^31.  Data parallel with global_negatives: every rank passes its local rows and
+    labels; the labels travel in one extra all-gather."""
+    embeddings = list(embeddings)
+    sharded = _is_sharded(global_negatives, group)
+    labels = _supcon_args(embeddings, labels, dist.get_world_size(group) if sharded else 1)
+    dev = embeddings[0].device
+    scales = torch.as_tensor(logit_scales, dtype=torch.float32, device=dev)
+    biases = torch.as_tensor(logit_biases, dtype=torch.float32, device=dev)
+    return _SupConLoss.apply(scales, biases, labels, kernels, group, sharded, *embeddings)
+
+
+def supcon_loss(embs1, embs2, labels, logit_scale=1.0, logit_bias=0.0, *, global_negatives=True, group=None,
+                kernels=HipSupConKernels):
+    """supcon_loss_multimodal of one modality pair: rows of S from embs2, columns from embs1, as clip_loss forms it."""
+    return supcon_loss_multimodal([embs1, embs2], labels, logit_scale, logit_bias, global_negatives=global_negatives, group=group,
+                                  kernels=kernels)
+
+
+def supcon_reference(embs, labels, logit_scales=1.0, logit_biases=0.0):
+    """torch fp64 restatement of supcon_loss_multimodal from log_softmax and a boolean mask, on any device:
+    -> (loss, [dloss/dE per modality], dloss/dlogit_scales, dloss/dlogit_biases), the last two in the shape given (a scalar
+    shared by every pair, or one value per pair)."""
+    E = [torch.as_tensor(e).detach().to(torch.float64).requires_grad_(True) for e in embs]
+    dev = E[0].device
+    y = torch.as_tensor(labels).to(dev).to(torch.float64).round().to(torch.int64)
+    ls = torch.as_tensor(logit_scales).detach().to(dev).to(torch.float64).requires_grad_(True)
+    lb = torch.as_tensor(logit_biases).detach().to(dev).to(torch.float64).requires_grad_(True)
+    N = E[0].shape[0]
+    mask = (y[:, None] == y[None, :]) & (y >= 0)[:, None] | torch.eye(N, dtype=torch.bool, device=dev)
+    w = mask.to(torch.float64) / mask.sum(1, keepdim=True)
+    total = 0.0
+    for k, (i, j) in enumerate(_pairs(range(len(E)), 2)):
+        s = ls if ls.dim() == 0 else ls[k]
+        b = lb if lb.dim() == 0 else lb[k]
+        S = torch.exp(s) * (E[j] @ E[i].T) + b
+        rows = -(w * torch.log_softmax(S, dim=1)).sum()
+        cols = -(w * torch.log_softmax(S.T, dim=1)).sum()
+        total = total + (rows + cols) / (2 * N)
+    grads = torch.autograd.grad(total, [*E, ls, lb])
+    return total.detach(), list(grads[:len(E)]), grads[-2], grads[-1]

@@ -153,7 +153,7 @@ class LightCurveImageCLIP(nn.Module):
             self.class_emb = nn.Embedding(n_classes, self.len_meta_input // 2)
             meta_kwargs.setdefault("dropout", 0.0)
             self.meta_encoder = MLP(output_dim=enc_dim, **meta_kwargs)
-        self.loss = loss
+        self.loss = loss                                      # "softmax", "sigmoid", "align_uniform" or "supcon" (reads the batch's class labels)
         self.loss_kwargs = loss_kwargs                        # alpha, t, lam of loss="align_uniform" (loss.align_uniform_loss)
         if loss == "align_uniform":
             # the loss has no scale and no bias: both stay (the state_dict keeps its names) and take no gradient, so the
@@ -235,7 +235,15 @@ class LightCurveImageCLIP(nn.Module):
         from .optim import build_optimizer
         return {"optimizer": build_optimizer(self.optimizer, self.parameters(), lr=self.lr, **self.optimizer_kwargs)}
 
-    def _loss(self, embs):
+    def _loss(self, embs, labels=None):
+        """`labels`: the batch's class labels (batch[8]); only loss="supcon" reads them."""
+        if self.loss == "supcon":
+            from .loss import supcon_loss_multimodal
+            if labels is None:
+                raise ValueError("loss='supcon' needs the class labels: the batch field `classification` (batch[8]) is None")
+            with markers.range("label-aware contrastive forward (+ exchange)"):
+                return supcon_loss_multimodal(embs, labels, self.logit_scale, self.logit_bias,
+                                              global_negatives=self.global_negatives)
         if self.loss == "softmax":
             with markers.range("InfoNCE forward (+ exchange)"):
                 return clip_loss_multimodal(embs, self.logit_scale, self.logit_bias,
@@ -252,7 +260,7 @@ class LightCurveImageCLIP(nn.Module):
 
     def training_step(self, batch, batch_idx):
         embs = self(*batch)
-        loss = self._loss(embs)
+        loss = self._loss(embs, batch[8] if len(batch) > 8 else None)
         self.log("train_loss", loss, on_epoch=True, on_step=False, prog_bar=True, logger=True)
         return loss
 
@@ -269,7 +277,7 @@ class LightCurveImageCLIP(nn.Module):
         embs = self(*batch)
         for i, e in enumerate(embs):
             self.embs_list[i].append(e.detach())
-        loss = self._loss(embs)
+        loss = self._loss(embs, batch[8] if len(batch) > 8 else None)
         self.log("val_loss", loss, on_epoch=True, on_step=False, prog_bar=True, logger=True)
         return loss
 
