@@ -950,6 +950,58 @@ int msn_confusion_matrix(const int64_t* target, const int* pred, int64_t N, int 
 size_t msn_regression_stats_workspace_bytes(int64_t N);
 int msn_regression_stats(const float* pred, const float* target, int64_t N, double* acc, void* ws, size_t ws_bytes,
                          msn_stream_t stream);
+/* Robust, Gaussian-NLL and quantile losses for the redshift head (csrc/regression_loss.hip; models_finetune.py:
+ * regression_loss).  pred (N, K) fp32 with row stride ld >= K, target (N) fp32.  A row is VALID when its target is finite: a
+ * NaN or infinite target (an object without a spectroscopic redshift) adds nothing to numerator or denominator and its
+ * gradient row is exactly zero.  With d = pred - y, per valid row:
+ *   MSE (K = 1) d^2 | L1 (K = 1) |d|, gradient 0 at d = 0 | HUBER (K = 1, delta > 0) d^2 / 2 up to |d| = delta, else
+ *   delta (|d| - delta / 2) | LOG_COSH (K = 1) log cosh d = log1p(2 sinh^2(d / 2)) up to |d| = 1, |d| + log1p(e^{-2|d|}) - ln 2
+ *   beyond | GAUSSIAN_NLL (K = 2: mu, s = log variance) (s + (mu - y)^2 e^-s) / 2 | PINBALL (1 <= K <= 16, levels taus[K],
+ *   DEVICE fp64, strictly increasing inside (0, 1) -- checked by the caller, not here) (1 / K) sum_q max(tau_q e_q,
+ *   (tau_q - 1) e_q) with e_q = y - pred_q, gradient 0 at e_q = 0.  delta is read by HUBER and taus by PINBALL only.
+ *   fwd: out[3] (DEVICE, fp32) = {numerator / (denom_in ? denom_in[0] : denom), denom, numerator}, denom = the number of valid
+ *        rows (an exact integer carried in fp64); no valid row gives nan.  ONE launch up to N = 256 (one row per lane of a
+ *        256-thread workgroup), else per-block fp64 partials in `ws` (msn_regression_loss_workspace_bytes) + one finishing
+ *        block that adds them in a fixed order.
+ *   bwd: dpred (N, K) fp32 with row stride lddx = grad_out[0] * d numerator / d pred / denom[0] (DEVICE scalars); the rows
+ *        are recomputed, rows of an ignored target are zeroed; one launch.
+ * Row arithmetic in fp64 from the fp32 inputs; out and dpred are rounded to fp32 once.  Non-finite predictions propagate;
+ * e^-s overflows for s < -709 and propagates too.  No atomics, 4-byte loads of pred and target: bitwise reproducible, for
+ * every row stride and every 4-byte alignment.
+ * MSN_ERR_SHAPE before any launch (the workspace query returns 0): an unknown kind, K not matching the kind or outside 1..16,
+ * N outside 1..2^31 - 1, delta not finite or <= 0 for HUBER, null taus for PINBALL, a row stride below K, a null or
+ * misaligned pointer, a workspace that is too small. */
+#define MSN_REGLOSS_MSE 0
+#define MSN_REGLOSS_L1 1
+#define MSN_REGLOSS_HUBER 2
+#define MSN_REGLOSS_LOG_COSH 3
+#define MSN_REGLOSS_GAUSSIAN_NLL 4
+#define MSN_REGLOSS_PINBALL 5
+size_t msn_regression_loss_workspace_bytes(int64_t N, int K);
+int msn_regression_loss_fwd(const float* pred, int64_t ld, const float* target, int64_t N, int K, int kind, double delta,
+                            const double* taus, const float* denom_in, float* out, void* ws, size_t ws_bytes,
+                            msn_stream_t stream);
+int msn_regression_loss_bwd(const float* pred, int64_t ld, const float* target, int64_t N, int K, int kind, double delta,
+                            const double* taus, const float* denom, const float* grad_out, float* dpred, int64_t lddx,
+                            msn_stream_t stream);
+/* Validation statistics of those heads over the valid rows, added to two caller-owned DEVICE buffers that persist over calls:
+ * acc[8] fp64 and cnt[19] int64.  acc[0..5] are msn_regression_stats' six sums {n, sum|d|, sum d^2, sum y, sum y^2, n_out} of
+ * the point prediction; cnt[0] = n.
+ *   POINT (K = 1):     the point prediction is pred itself; acc[6], acc[7] stay.
+ *   GAUSSIAN (K = 2):  the point prediction is mu; acc[6] += sum sigma, acc[7] += sum z^2 (sigma = e^{s / 2}, z = d / sigma);
+ *                      cnt[k] += rows with |d| <= k sigma, k = 1, 2, 3 (fp64 compare).
+ *   QUANTILE (K <= 16): the point prediction is column `mid`; acc[6] += sum (pred_{K-1} - pred_0), acc[7] += sum of the row
+ *                      pinball terms (taus as above); cnt[1] += rows with pred_0 <= y <= pred_{K-1}, cnt[2] += rows with some
+ *                      pred_q > pred_{q+1}, cnt[3 + q] += rows with y <= pred_q (IEEE fp32 compares: a NaN is below nothing).
+ * One launch up to N = 256, else per-block fp64 partials in `ws` + one finishing block (fixed order); the counts are integer
+ * adds, which commute: workgroup order, the cut of an epoch into calls and a SUM all-reduce change no bit of them. */
+#define MSN_REGSTATS_POINT 0
+#define MSN_REGSTATS_GAUSSIAN 1
+#define MSN_REGSTATS_QUANTILE 2
+size_t msn_regression_interval_stats_workspace_bytes(int64_t N);
+int msn_regression_interval_stats(const float* pred, int64_t ld, const float* target, int64_t N, int K, int mode, int mid,
+                                  const double* taus, int64_t* cnt, double* acc, void* ws, size_t ws_bytes,
+                                  msn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Linear probes on frozen embeddings (probes.py; csrc/probes.hip): the two fp64 reductions a probe fit needs.  An fp32

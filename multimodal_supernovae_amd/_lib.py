@@ -139,6 +139,11 @@ SIGNATURES = {
     "msn_confusion_matrix": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr]),
     "msn_regression_stats_workspace_bytes": (c_size, [c_i64]),
     "msn_regression_stats": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
+    "msn_regression_loss_workspace_bytes": (c_size, [c_i64, c_int]),
+    "msn_regression_loss_fwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_f64, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "msn_regression_loss_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_f64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    "msn_regression_interval_stats_workspace_bytes": (c_size, [c_i64]),
+    "msn_regression_interval_stats": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "msn_probe_gram_slab_rows": (c_i64, [c_i64, c_int, c_int]),
     "msn_probe_gram_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
     "msn_probe_gram": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr, c_int, c_ptr, c_size, c_ptr]),

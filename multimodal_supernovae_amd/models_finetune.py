@@ -11,6 +11,12 @@ checked against a plain-PyTorch restatement in tests/test_supervised_gpu.py.
     class_balanced_weights(counts, beta)            -- class weights from the effective number of samples (host)
     ClassificationMetrics / RegressionMetrics       -- device accumulators (confusion matrix / six fp64 sums); compute()
                                                        is the one host copy, its arithmetic a pure function
+    regression_loss(pred, target, kind, delta=, quantiles=)
+                                                    -- mse / l1 / huber / log_cosh / gaussian_nll / pinball over the rows
+                                                       with a finite target on csrc/regression_loss.hip (fp64 rows);
+                                                       regression_loss_reference restates it in longdouble
+    IntervalMetrics(mode, quantiles)                -- point metrics + calibration of the predicted sigma / coverage of the
+                                                       predicted quantiles from integer counts (interval_metrics on the host)
     ClipMLP(clip_model, classification=True | regression=True, ...)
                                                     -- MLP head on the concatenated unit-norm embeddings of a
                                                        LightCurveImageCLIP, optionally with a frozen backbone
@@ -345,6 +351,274 @@ class RegressionMetrics:
         return regression_metrics(self.sums.cpu().tolist() if self.sums is not None else [0.0] * 6)
 
 
+# ------------------------------------------------------------- robust, Gaussian-NLL and quantile regression
+REGRESSION_KINDS = {"mse": 0, "l1": 1, "huber": 2, "log_cosh": 3, "gaussian_nll": 4, "pinball": 5}     # MSN_REGLOSS_*
+_INTERVAL_MODES = {"point": 0, "gaussian": 1, "quantile": 2}                                           # MSN_REGSTATS_*
+_MAX_LEVELS = 16
+_N_CNT, _N_ACC = 3 + _MAX_LEVELS, 8
+_LEVELS = {}                 # (levels, device) -> float64 device tensor, uploaded once outside graph capture
+
+
+def _check_quantiles(who, quantiles):
+    """The levels as a tuple of floats: 1..16 of them, strictly increasing inside (0, 1).  Checked here, on the host: the
+    kernels never read them for validation."""
+    try:
+        q = tuple(float(v) for v in quantiles)
+    except TypeError:
+        raise ValueError(f"{who}: quantiles must be a sequence of levels (got {quantiles!r})") from None
+    if not (1 <= len(q) <= _MAX_LEVELS):
+        raise ValueError(f"{who}: quantiles must hold 1..{_MAX_LEVELS} levels (got {len(q)})")
+    if not all(0.0 < v < 1.0 for v in q) or any(b <= a for a, b in zip(q, q[1:])):
+        raise ValueError(f"{who}: quantiles must be strictly increasing inside (0, 1) (got {q})")
+    return q
+
+
+def _regression_params(who, kind, delta, quantiles):
+    """-> (kind id, K, delta, levels or None), refusing what the kernels would refuse with a ValueError naming the argument."""
+    if kind not in REGRESSION_KINDS:
+        raise ValueError(f"{who}: kind must be one of {sorted(REGRESSION_KINDS)} (got {kind!r})")
+    delta = float(delta)
+    if kind == "huber" and not (0.0 < delta < float("inf")):
+        raise ValueError(f"{who}: delta must be finite and > 0 (got {delta})")
+    levels = None
+    if kind == "pinball":
+        if quantiles is None:
+            raise ValueError(f"{who}: the pinball loss needs quantiles")
+        levels = _check_quantiles(who, quantiles)
+    elif quantiles is not None:
+        raise ValueError(f"{who}: quantiles belong to the pinball loss (kind is {kind!r})")
+    K = len(levels) if levels is not None else 2 if kind == "gaussian_nll" else 1
+    return REGRESSION_KINDS[kind], K, delta, levels
+
+
+def _levels_on(levels, device):
+    """The levels as float64 on `device`, cached per (levels, device): a replayed graph must not contain the upload."""
+    if levels is None:
+        return None
+    key = (levels, str(device))
+    if key not in _LEVELS:
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.MsnHipError("regression_loss: the quantile levels reach the device outside graph capture -- run one eager "
+                                   "step (GraphedTrainStep's warm-up does) before recording")
+        _LEVELS[key] = torch.tensor(levels, dtype=torch.float64, device=device)
+    return _LEVELS[key]
+
+
+def _regression_args(who, pred, target, K):
+    """The checked (pred, target): float32 (N, K) predictions with unit column stride on the GPU, float32 (N) targets."""
+    _lib.require_gpu()
+    if pred.device.type != "cuda" or pred.dtype != torch.float32:
+        raise _lib.MsnHipError(f"{who}: pred must be float32 on the GPU (got {pred.dtype} on {pred.device}); there is no CPU path")
+    if pred.dim() == 1 and K == 1:
+        pred = pred.unsqueeze(1)
+    if pred.dim() != 2 or pred.shape[1] != K:
+        raise ValueError(f"{who}: pred must be (N, {K}) for this loss (got {tuple(pred.shape)})")
+    N = pred.shape[0]
+    if N and ((K > 1 and pred.stride(1) != 1) or pred.stride(0) < K):
+        pred = pred.contiguous()
+    if target.shape != (N,) or target.device != pred.device or not target.is_floating_point():
+        raise ValueError(f"{who}: target must be floating point of shape ({N},) on {pred.device}")
+    return pred, target.detach().to(torch.float32).contiguous()
+
+
+class _RegressionLoss(torch.autograd.Function):
+    """_CrossEntropy's contract on csrc/regression_loss.hip: this process's numerator over the number of valid rows (its own,
+    or the ranks' sum when `sharded`).  No host read: GraphedTrainStep records it.  Backward recomputes the rows."""
+
+    @staticmethod
+    def forward(ctx, pred, target, kind, delta, taus, group, sharded):
+        N, K = pred.shape
+        dev = pred.device
+        L = lib()
+        out = torch.empty(3, dtype=torch.float32, device=dev)              # {loss, valid rows, numerator}
+        nb = L.msn_regression_loss_workspace_bytes(N, K)
+        ws = workspace(nb, dev) if nb else None
+        check(L.msn_regression_loss_fwd(ptr(pred), pred.stride(0), ptr(target), N, K, kind, delta, ptr(taus), ptr(None), ptr(out),
+                                        ptr(ws), nb, stream_ptr()), "msn_regression_loss_fwd")
+        if sharded:
+            denom = D.all_reduce_sum(out[1].clone(), group, kind="loss_denominator_all_reduce")
+            loss = out[2] / denom                                          # this rank's share of the global mean
+        else:
+            denom, loss = out[1], out[0]
+        ctx.save_for_backward(pred, target, taus, denom)
+        ctx.reg = (kind, delta)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target, taus, denom = ctx.saved_tensors
+        N, K = pred.shape
+        g = g.to(torch.float32).reshape(()).contiguous()
+        dx = torch.empty((N, K), dtype=torch.float32, device=pred.device)
+        check(lib().msn_regression_loss_bwd(ptr(pred), pred.stride(0), ptr(target), N, K, *ctx.reg, ptr(taus), ptr(denom), ptr(g),
+                                            ptr(dx), K, stream_ptr()), "msn_regression_loss_bwd")
+        return (dx,) + (None,) * 6
+
+
+def _regression_loss(pred, target, kind, delta, levels, group=None, sharded=None):
+    """regression_loss on checked parameters (kind id, levels tuple or None)."""
+    K = len(levels) if levels is not None else 2 if kind == REGRESSION_KINDS["gaussian_nll"] else 1
+    pred, target = _regression_args("regression_loss", pred, target, K)
+    if pred.shape[0] == 0:
+        raise ValueError("regression_loss: pred must hold at least one row")
+    if sharded is None:
+        sharded = D.world_size(group) > 1
+    share = _RegressionLoss.apply(pred, target, kind, delta, _levels_on(levels, pred.device), group, bool(sharded))
+    return _AllReduceSum.apply(share, group) if sharded else share
+
+
+def regression_loss(pred, target, kind="mse", *, delta=1.0, quantiles=None, group=None):
+    """Mean over the rows with a FINITE target of one of six row terms (d = pred - target), for float32 predictions on the GPU:
+
+        "mse" d^2 | "l1" |d| | "huber" F.huber_loss(delta=delta) | "log_cosh" log cosh d          -- pred (N,) or (N, 1)
+        "gaussian_nll"  (s + (mu - y)^2 exp(-s)) / 2 for pred (N, 2) = (mu, s = log variance):
+                        F.gaussian_nll_loss(mu, y, var=exp(s), full=False, eps=0)
+        "pinball"       (1 / K) sum_q max(tau_q e_q, (tau_q - 1) e_q), e_q = y - pred_q, for pred (N, K) and the K <= 16 levels
+                        `quantiles` (strictly increasing inside (0, 1))
+
+    A row whose target is NaN or infinite -- an object without a spectroscopic redshift -- is ignored as cross_entropy ignores
+    -100: no term, no count, a gradient row of exact zeros; no valid row at all gives nan.  Subgradients at the kinks are
+    torch's (0 at d = 0, d at |d| = delta, 0 at e_q = 0).  Row arithmetic is fp64 (csrc/regression_loss.hip), bitwise
+    reproducible.  No host read: a graph records it.  Data parallel as cross_entropy: every rank passes its LOCAL rows and
+    gets the global mean over the ranks' valid rows.  Not built: per-sample weights, smooth_l1, a beta-NLL, CRPS, K > 16."""
+    kind_id, _, delta, levels = _regression_params("regression_loss", kind, delta, quantiles)
+    return _regression_loss(pred, target, kind_id, delta, levels, group)
+
+
+def _np_log_cosh(d):
+    """log cosh d in the kernel's split: log1p(2 sinh^2(d / 2)) up to |d| = 1, |d| + log1p(exp(-2|d|)) - ln 2 beyond."""
+    import numpy as np
+    a = np.abs(d)
+    small = a <= 1
+    h = np.sinh(np.where(small, d, 0) / 2)
+    big = np.where(small, 1, a)
+    return np.where(small, np.log1p(2 * h * h), big + np.log1p(np.exp(-2 * big)) - np.log(np.longdouble(2)))
+
+
+def regression_loss_reference(pred, target, kind, delta=1.0, quantiles=None):
+    """(loss, dpred) of regression_loss restated in numpy longdouble, returned as a float and a float64 (N, K) array: the same
+    valid-row rule (finite targets), the same log cosh split and the same subgradients as the kernels."""
+    import numpy as np
+    ld = np.longdouble
+    _, K, delta, levels = _regression_params("regression_loss_reference", kind, delta, quantiles)
+    p = np.asarray(pred.detach().cpu() if torch.is_tensor(pred) else pred)
+    y = np.asarray(target.detach().cpu() if torch.is_tensor(target) else target)
+    p = p.reshape(y.shape[0], K).astype(ld)
+    valid = np.isfinite(y)
+    y = np.where(valid, y, 0).astype(ld)
+    delta = ld(delta)
+    with np.errstate(all="ignore"):
+        if kind == "pinball":
+            tau = np.asarray(levels, dtype=np.float64).astype(ld)[None, :]
+            e = y[:, None] - p
+            rows = np.where(e > 0, tau * e, (tau - 1) * e).sum(axis=1) / K
+            g = np.where(e > 0, -tau, np.where(e < 0, 1 - tau, e)) / K
+        elif kind == "gaussian_nll":
+            d, s = p[:, 0] - y, p[:, 1]
+            w = np.exp(-s)
+            rows = (s + d * d * w) / 2
+            g = np.stack([d * w, (1 - d * d * w) / 2], axis=1)
+        else:
+            d = p[:, 0] - y
+            a = np.abs(d)
+            sign = np.where(d > 0, ld(1), np.where(d < 0, ld(-1), d))
+            if kind == "mse":
+                rows, g = d * d, 2 * d
+            elif kind == "l1":
+                rows, g = a, sign
+            elif kind == "huber":
+                rows, g = np.where(a <= delta, d * d / 2, delta * (a - delta / 2)), np.where(a <= delta, d, delta * sign)
+            else:
+                rows, g = _np_log_cosh(d), np.tanh(d)
+            g = g[:, None]
+        n = ld(int(valid.sum()))
+        loss = np.where(valid, rows, ld(0)).sum() / n if n > 0 else ld("nan")
+        dx = np.where(valid[:, None], g, ld(0)) / (n if n > 0 else ld(1))
+    return float(loss), dx.astype(np.float64)
+
+
+def interval_metrics(cnt, acc, mode, quantiles=None):
+    """Pure host function of the counts and sums of msn_regression_interval_stats.  Every mode: L1, L2, R2, OLF of the point
+    prediction (regression_metrics of acc[0..5]).  "gaussian": sigma_mean, z2_mean (mean squared standardised residual: 1 for
+    a calibrated head) and cov1, cov2, cov3 (fractions of rows with |d| <= k sigma; 0.683, 0.954, 0.997 for a calibrated
+    Gaussian).  "quantile": coverage (y inside [pred_0, pred_{K-1}]), width_mean of that interval, pinball (the mean row term),
+    crossing (fraction of rows with some pred_q > pred_{q+1}) and cov_below (per level, the fraction of rows with
+    y <= pred_q: tau_q for a calibrated head).  The fractions are ratios of integer counts."""
+    if mode not in _INTERVAL_MODES:
+        raise ValueError(f"interval_metrics: mode must be one of {sorted(_INTERVAL_MODES)} (got {mode!r})")
+    cnt = [int(v) for v in cnt]
+    acc = [float(v) for v in acc]
+    res = regression_metrics(acc[:6])
+    n = cnt[0]
+    nan = float("nan")
+    if mode == "gaussian":
+        res.update(sigma_mean=acc[6] / n if n else nan, z2_mean=acc[7] / n if n else nan)
+        for k in (1, 2, 3):
+            res[f"cov{k}"] = cnt[k] / n if n else nan
+    elif mode == "quantile":
+        K = len(_check_quantiles("interval_metrics", quantiles))
+        res.update(coverage=cnt[1] / n if n else nan, width_mean=acc[6] / n if n else nan, pinball=acc[7] / n if n else nan,
+                   crossing=cnt[2] / n if n else nan, cov_below=[cnt[3 + q] / n if n else nan for q in range(K)])
+    return res
+
+
+class IntervalMetrics:
+    """Validation statistics of a regression head over the rows with a finite target, accumulated on the device over the
+    batches of an epoch (msn_regression_interval_stats): `cnt`, int64 counts, and `acc`, fp64 sums.  mode "point" (one
+    prediction per row), "gaussian" ((mu, log variance) per row) or "quantile" (one column per level of `quantiles`; the
+    point prediction is the column whose level is nearest 0.5, the lower index on a tie)."""
+
+    def __init__(self, mode, quantiles=None):
+        if mode not in _INTERVAL_MODES:
+            raise ValueError(f"IntervalMetrics: mode must be one of {sorted(_INTERVAL_MODES)} (got {mode!r})")
+        if (mode == "quantile") != (quantiles is not None):
+            raise ValueError("IntervalMetrics: quantiles belong to mode 'quantile', which needs them")
+        self.mode = mode
+        self.quantiles = _check_quantiles("IntervalMetrics", quantiles) if quantiles is not None else None
+        self.width = len(self.quantiles) if self.quantiles else 2 if mode == "gaussian" else 1
+        self.mid = min(range(self.width), key=lambda q: (abs(self.quantiles[q] - 0.5), q)) if self.quantiles else 0
+        self.cnt = self.acc = None
+
+    def ensure(self, device):
+        """Zeroed buffers on `device` where there are none yet (a rank whose shard was empty still enters the collectives)."""
+        if self.cnt is None or self.cnt.device != torch.device(device):
+            self.cnt = torch.zeros(_N_CNT, dtype=torch.int64, device=device)
+            self.acc = torch.zeros(_N_ACC, dtype=torch.float64, device=device)
+
+    def reset(self):
+        if self.cnt is not None:
+            self.cnt.zero_()
+            self.acc.zero_()
+
+    def update(self, pred, target):
+        """pred (N, K) (or (N,) in point mode), target (N); rows with a non-finite target do not count.  Enqueue only."""
+        pred, target = _regression_args("IntervalMetrics.update", pred.detach(), target.to(pred.device), self.width)
+        N = pred.shape[0]
+        if N == 0:
+            return
+        self.ensure(pred.device)
+        L = lib()
+        nb = L.msn_regression_interval_stats_workspace_bytes(N)
+        ws = workspace(nb, pred.device) if nb else None
+        check(L.msn_regression_interval_stats(ptr(pred), pred.stride(0), ptr(target), N, self.width, _INTERVAL_MODES[self.mode],
+                                              self.mid, ptr(_levels_on(self.quantiles, pred.device)), ptr(self.cnt), ptr(self.acc),
+                                              ptr(ws), nb, stream_ptr()), "msn_regression_interval_stats")
+
+    def all_reduce(self, group=None):
+        if self.cnt is not None and D.world_size(group) > 1:
+            D.all_reduce_sum(self.cnt, group, kind="metric_all_reduce")
+            D.all_reduce_sum(self.acc, group, kind="metric_all_reduce")
+
+    def compute(self):
+        if self.cnt is None:
+            return interval_metrics([0] * _N_CNT, [0.0] * _N_ACC, self.mode, self.quantiles)
+        return interval_metrics(self.cnt.cpu().tolist(), self.acc.cpu().tolist(), self.mode, self.quantiles)
+
+
+_REGRESSION_LOSSES = ("mse", "l1", "huber", "log_cosh", "gaussian_nll", "quantile")
+_DEFAULT_QUANTILES = (0.16, 0.5, 0.84)
+
+
 # -------------------------------------------------------------------------------------------------- module
 class ClipMLP(nn.Module):
     """MLP head on the concatenated embeddings of a (pretrained) LightCurveImageCLIP, trained for classification
@@ -356,7 +630,15 @@ class ClipMLP(nn.Module):
     15 bins) and logs ece_val and brier_val (top-label expected calibration error, multi-class Brier score).
     loss="focal" (classification only) trains and validates on focal_loss with loss_kwargs {"gamma": 2.0, "label_smoothing": 0.0};
     loss="cross_entropy" (the default) takes loss_kwargs {"label_smoothing"}.  val_loss is the configured loss; the metrics and
-    the state_dict do not depend on it."""
+    the state_dict do not depend on it.
+    regression=True takes loss= "mse" | "l1" | "huber" | "log_cosh" | "gaussian_nll" | "quantile" (regression_loss on
+    csrc/regression_loss.hip) with loss_kwargs {"delta"} for huber, {"quantiles"} for quantile (default (0.16, 0.5, 0.84)) and
+    none otherwise.  These ignore rows whose redshift is NaN or infinite.  The head emits 1 value, (mu, log variance) for
+    gaussian_nll, or one value per level for quantile -- only the last layer's shape changes; `metrics` is an IntervalMetrics
+    and validation logs L1_val .. OLF_val of the point prediction (itself, mu, or the level nearest 0.5) plus sigma_val, z2_val,
+    cov1_val, cov2_val (gaussian_nll) or coverage_val, width_val, crossing_val (quantile).  loss=None on a regression model is the
+    masked-MSE path unchanged (same bits, keys and state_dict; a NaN target poisons it); an explicit loss="mse" takes the new
+    kernel instead: it ignores non-finite targets and agrees with the default to fp32 rounding, not bit for bit."""
 
     def __init__(self, clip_model, learning_rate=1e-3, regression=False, classification=False, n_classes=5, hidden_dim=128,
                  num_layers=2, dropout=0.0, freeze_backbone=False, class_weights=None, optimizer_kwargs=None,
@@ -364,19 +646,36 @@ class ClipMLP(nn.Module):
         super().__init__()
         if bool(regression) == bool(classification):
             raise ValueError("ClipMLP needs exactly one of regression=True / classification=True")
-        if regression and (loss is not None or loss_kwargs is not None):
-            raise ValueError("ClipMLP: loss / loss_kwargs belong to classification (regression trains on the MSE)")
-        loss = "cross_entropy" if loss is None else loss
-        if loss not in ("cross_entropy", "focal"):
-            raise ValueError(f"ClipMLP: loss must be 'cross_entropy' or 'focal' (got {loss!r})")
-        loss_kwargs = dict(loss_kwargs or {})
-        allowed = ("gamma", "label_smoothing") if loss == "focal" else ("label_smoothing",)
-        unknown = sorted(set(loss_kwargs) - set(allowed))
-        if unknown:
-            raise ValueError(f"ClipMLP: loss={loss!r} takes the loss_kwargs {allowed} (got {unknown})")
-        self.loss_name = loss
-        self.loss_gamma, self.label_smoothing = _focal_params("ClipMLP", loss_kwargs.get("gamma", 2.0 if loss == "focal" else 0.0),
-                                                              loss_kwargs.get("label_smoothing", 0.0))
+        self.reg_loss = None                  # regression: None = today's masked MSE, else (kind id, delta, levels or None)
+        if regression:
+            if loss is None and loss_kwargs is not None:
+                raise ValueError("ClipMLP: loss_kwargs need a loss= on a regression model (the default trains on the MSE)")
+            if loss is not None and loss not in _REGRESSION_LOSSES:
+                raise ValueError(f"ClipMLP: a regression model's loss must be one of {_REGRESSION_LOSSES} (got {loss!r})")
+            loss_kwargs = dict(loss_kwargs or {})
+            allowed = {"huber": ("delta",), "quantile": ("quantiles",)}.get(loss, ())
+            unknown = sorted(set(loss_kwargs) - set(allowed))
+            if unknown:
+                raise ValueError(f"ClipMLP: loss={loss!r} takes the loss_kwargs {allowed} (got {unknown})")
+            if loss is not None:
+                kind = "pinball" if loss == "quantile" else loss
+                levels = loss_kwargs.get("quantiles", _DEFAULT_QUANTILES) if loss == "quantile" else None
+                kind_id, _, delta, levels = _regression_params("ClipMLP", kind, loss_kwargs.get("delta", 1.0), levels)
+                self.reg_loss = (kind_id, delta, levels)
+            self.loss_name = "cross_entropy" if loss is None else loss      # (the default keeps the attribute it always had)
+            self.loss_gamma, self.label_smoothing = 0.0, 0.0
+        else:
+            loss = "cross_entropy" if loss is None else loss
+            if loss not in ("cross_entropy", "focal"):
+                raise ValueError(f"ClipMLP: loss must be 'cross_entropy' or 'focal' (got {loss!r})")
+            loss_kwargs = dict(loss_kwargs or {})
+            allowed = ("gamma", "label_smoothing") if loss == "focal" else ("label_smoothing",)
+            unknown = sorted(set(loss_kwargs) - set(allowed))
+            if unknown:
+                raise ValueError(f"ClipMLP: loss={loss!r} takes the loss_kwargs {allowed} (got {unknown})")
+            self.loss_name = loss
+            self.loss_gamma, self.label_smoothing = _focal_params("ClipMLP", loss_kwargs.get("gamma", 2.0 if loss == "focal" else 0.0),
+                                                                  loss_kwargs.get("label_smoothing", 0.0))
         if "meta" in clip_model.combinations:
             raise ValueError("ClipMLP: a clip_model with the 'meta' tower reads redshift and class -- the labels; build it "
                              "without 'meta' and load the pretrained state_dict with strict=False")
@@ -393,7 +692,8 @@ class ClipMLP(nn.Module):
         self.optimizer = optimizer            # optim.build_optimizer's name ("radam", "adam", "adamw", "sgd", "lars") or an Optimizer class (optim.LAMB)
         self.freeze_backbone = bool(freeze_backbone)
         self.mlp = MLP(input_dim=len(self.towers) * clip_model.enc_dim, hidden_dim=hidden_dim,
-                       output_dim=self.n_classes if classification else 1, num_layers=num_layers, dropout=dropout)
+                       output_dim=self.n_classes if classification else self._regression_width(), num_layers=num_layers,
+                       dropout=dropout)
         if class_weights is not None:
             w = torch.as_tensor(class_weights, dtype=torch.float32).reshape(-1)
             if w.numel() != self.n_classes:
@@ -405,7 +705,13 @@ class ClipMLP(nn.Module):
             self.clip_model.requires_grad_(False)
             self.clip_model.eval()
         self.group = None
-        self.metrics = ClassificationMetrics(self.n_classes) if classification else RegressionMetrics()
+        if classification:
+            self.metrics = ClassificationMetrics(self.n_classes)
+        elif self.reg_loss is None:
+            self.metrics = RegressionMetrics()
+        else:
+            mode = {"gaussian_nll": "gaussian", "quantile": "quantile"}.get(self.loss_name, "point")
+            self.metrics = IntervalMetrics(mode, self.reg_loss[2])
         self.ranking = None                   # opt-in: threshold-free metrics of the logits (metrics.RankingMetrics)
         if ranking_metrics and classification:
             from .metrics import RankingMetrics
@@ -417,6 +723,12 @@ class ClipMLP(nn.Module):
         self._val_batches = 0
         self._ones = {}
         self.logged = {}
+
+    def _regression_width(self):
+        """Outputs of the regression head: 1, (mu, log variance) for the Gaussian NLL, or one per quantile level."""
+        if self.reg_loss is None or self.loss_name not in ("gaussian_nll", "quantile"):
+            return 1
+        return 2 if self.loss_name == "gaussian_nll" else len(self.reg_loss[2])
 
     def log(self, name, value, **kwargs):
         # detached: a logged loss must not keep its autograd graph alive into the next step
@@ -481,6 +793,8 @@ class ClipMLP(nn.Module):
                 loss, pred = _cross_entropy(out, target, self.class_weights, self.group, sharded)
             return loss, pred, target, out
         target = batch[7].to(torch.float32).reshape(-1)
+        if self.reg_loss is not None:           # the head's whole output goes to the loss and to IntervalMetrics
+            return _regression_loss(out, target, *self.reg_loss, self.group, sharded), out, target, out
         pred = out.squeeze(1)
         return self._mse(pred, target, sharded), pred, target, out
 
@@ -522,7 +836,9 @@ class ClipMLP(nn.Module):
                 dev = next(self.mlp.parameters()).device
                 if self.classification and self.metrics.cm is None:
                     self.metrics.cm = torch.zeros((self.n_classes, self.n_classes), dtype=torch.int32, device=dev)
-                if self.regression and self.metrics.sums is None:
+                if self.regression and self.reg_loss is not None:
+                    self.metrics.ensure(dev)
+                elif self.regression and self.metrics.sums is None:
                     self.metrics.sums = torch.zeros(6, dtype=torch.float64, device=dev)
             self.metrics.all_reduce(self.group)
             if self.ranking is not None:
@@ -547,3 +863,7 @@ class ClipMLP(nn.Module):
         else:
             for k in ("L1", "L2", "R2", "OLF"):
                 self.log(f"{k}_val", res[k], **kw)
+            extra = {"gaussian_nll": (("sigma_val", "sigma_mean"), ("z2_val", "z2_mean"), ("cov1_val", "cov1"), ("cov2_val", "cov2")),
+                     "quantile": (("coverage_val", "coverage"), ("width_val", "width_mean"), ("crossing_val", "crossing"))}
+            for name, key in extra.get(self.loss_name, ()):               # (the default model's loss_name is neither)
+                self.log(name, res[key], **kw)
