@@ -1148,6 +1148,58 @@ int msn_align_uniform_bwd(const float* X, int64_t ldx, const float* Y, int64_t l
                           double lam, float* dX, int64_t lddx, float* dY, int64_t lddy, msn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * VICReg (Bardes, Ponce, LeCun 2022) as a training loss (loss.py; csrc/vicreg.hip): the centred column covariance, the loss
+ * and the product of its gradient.  X, Y (N, D) fp32 with row strides >= D, 4-byte aligned, not assumed unit-norm;
+ * 2 <= N < 2^31, 1 <= D <= 256.  Everything below is fp64 on the device, enqueue only, no atomics, no fills, no zeroed
+ * scratch; every load of X and Y is a 4-byte load, so the bits depend on the values, N and D only (not on stride, alignment
+ * or run).  Non-finite inputs are not checked and propagate.
+ *
+ * Column covariance: mean (D) and cov (D x D, symmetric bit for bit) of X,
+ *   mean_c = (1 / N) sum_i x_ic      cov_cc' = (1 / (N - 1)) sum_i (x_ic - mean_c)(x_ic' - mean_c')
+ *   Plan, a function of (N, D) alone (no device query):
+ *     means: mrows = max(64, ceil(N / 64)) rows per slab, mslabs = ceil(N / mrows); a thread adds one column of its slab in row
+ *     order, the slabs are added in slab order from slab 0 on, then one division by N;
+ *     Gram: T = ceil(D / 64) column tiles, pairs = T (T + 1) / 2 tile pairs on or above the diagonal (nothing below it is
+ *     computed), chunks = ceil(N / 32), per = max(4, ceil(chunks / ceil(512 / pairs))), slabs = ceil(chunks / per): workgroup
+ *     (pair, slab) multiplies the 32 per rows of its slab on v_mfma_f64_16x16x4_f64, the rows staged as doubles with the mean
+ *     subtracted on the way into LDS (one rounding per element; no X^T X - N mean mean^T cancellation); the finishing launch
+ *     adds the slabs' partials in slab order, divides by N - 1 and writes (c, c') and (c', c) from the same numbers.
+ *   Additions at most on a term's way
+ *     to a mean:                A_mean(N)   = mrows + mslabs
+ *     to a covariance entry:    A_cov(N, D) = 32 per + slabs     (4 per matrix instruction, 8 instructions per 32 rows, the slabs)
+ *   ws: msn_column_cov_workspace_bytes = 8 (mslabs D + 4096 slabs pairs) bytes.  Three launches.
+ *
+ * Forward (three launches): inv = (1 / (N D)) sum_ic (x_ic - y_ic)^2 with d2_i by fma in column order and the sum over the rows
+ *   in the order of msn_pair_alignment; over the two covariance matrices, s_c = sqrt(C_cc + eps),
+ *     var = (1 / D) sum_c max(0, gamma - s_c)      cov = (1 / D) sum_{c != c'} C_cc'^2   (C^2 added by fma)
+ *   one entry per thread and step over blocks = min(ceil(D^2 / 256), 64) workgroups, the xor tree, the four waves in order, one
+ *   finishing workgroup likewise:
+ *     to a sum over D x D:      A_dd(D)     = ceil(D^2 / (256 blocks)) + 9 + ceil(blocks / 256) + 9
+ *   comp (5 doubles) = (inv, var_x, var_y, cov_x, cov_y); loss (1 float) = sim inv + std (var_x + var_y) + covc (cov_x + cov_y),
+ *   rounded once from fp64; M_x, M_y (D x D doubles) are the coefficient matrices of the backward,
+ *     M = (4 covc / (D (N - 1))) offdiag(C) - diag(std [s_c < gamma] / (D (N - 1) s_c))
+ *   (the hinge is inactive at s_c == gamma).  ws: msn_vicreg_workspace_bytes = 8 (min(ceil(N / 256), 1024) + 4 blocks) bytes.
+ * Backward (one launch): P = (X - mean) M on the same instruction, a 64 x 64 tile of P per workgroup, its fp64 accumulator in
+ *   registers, the centred rows staged 32 inner columns at a time and M in chunks of 32 x 64 through LDS,
+ *     to an entry of P:         A_p(D)      = 32 ceil(D / 32)
+ *   dX = fl32(g (k (x - y) + P_x)), dY = fl32(g (-k (x - y) + P_y)), k = 2 sim / (N D), g a DEVICE float.  It reads X, Y, the
+ *   means and M_x, M_y only.  Rows past N are never read and never written (dX, dY have row strides lddx, lddy >= D).
+ * No host read anywhere: the step records into a graph.
+ * MSN_ERR_SHAPE before any launch: D outside 1..256, N < 2 or >= 2^31, a coefficient negative or not finite, gamma negative
+ * or not finite, eps not finite or <= 0, a null pointer, a misaligned pointer, a row stride below D, a workspace that is too
+ * small. */
+size_t msn_column_cov_workspace_bytes(int64_t N, int D);
+int msn_column_cov(const float* X, int64_t ldx, int64_t N, int D, double* mean, double* cov, void* ws, size_t ws_bytes,
+                   msn_stream_t stream);
+size_t msn_vicreg_workspace_bytes(int64_t N, int D);
+int msn_vicreg_fwd(const float* X, int64_t ldx, const float* Y, int64_t ldy, int64_t N, int D, const double* cov_x,
+                   const double* cov_y, double sim_coeff, double std_coeff, double cov_coeff, double gamma, double eps, float* loss,
+                   double* comp, double* M_x, double* M_y, void* ws, size_t ws_bytes, msn_stream_t stream);
+int msn_vicreg_bwd(const float* X, int64_t ldx, const float* Y, int64_t ldy, int64_t N, int D, const double* mean_x,
+                   const double* mean_y, const double* M_x, const double* M_y, const float* g, double sim_coeff, float* dX,
+                   int64_t lddx, float* dY, int64_t lddy, msn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Threshold-free classification metrics (metrics.py; csrc/rank_metrics.hip): one-vs-rest AUROC, average precision, binned
  * ROC / precision-recall curves and top-k accuracy from integer counts.  Shared by the four entry points: S (N, C) fp32
  * scores with row stride ld >= C, 4-byte aligned (every load of S is a 4-byte load: the bits do not depend on stride or

@@ -8,6 +8,9 @@ al. 2022), effective rank / RankMe (Garrido et al. 2023), and recall@k, MRR and 
     pair_field        per row r_i = sum_j exp(-t d^2_ij) and F_i = sum_j exp(-t d^2_ij) (x_i - y_j) in fp64 on the device
                       (csrc/uniformity_loss.hip: msn_pair_field, a second fp64 matrix product behind the scores): what the
                       gradient of the uniformity needs (loss.align_uniform_loss).  D <= 256.  Enqueue only.
+    column_covariance the column means and the covariance of the centred rows in fp64 on the device (csrc/vicreg.hip:
+                      msn_column_cov): what loss.vicreg_loss regularises.  D <= 256.  Enqueue only.  (covariance_spectrum still
+                      goes through probes.probe_gram.)  column_covariance_reference is its longdouble restatement.
     uniformity, cross_uniformity, alignment
                       the figures of one call: one host copy each
     covariance_spectrum, effective_rank, participation_ratio, modality_gap
@@ -281,6 +284,45 @@ def pair_field(X, Y=None, t=2.0, exclude_self=True, *, self_offset=None, out=Non
     check(L.msn_pair_field(ptr(X), ld(X), Nx, ptr(Y), ld(Y), Ny, D, float(t), off, ptr(r), ptr(F), ptr(ws), ws.numel(),
                            stream_ptr()), "msn_pair_field")
     return r, F
+
+
+COV_MAX_D = 256
+
+
+def column_covariance_reference(X):
+    """numpy longdouble restatement of column_covariance: (mean (D,), cov (D, D)) of the fp32 rows X, cov = Xc^T Xc / (N - 1)
+    over the centred rows.  No GPU needed."""
+    X = np.asarray(X, dtype=np.float32).astype(np.longdouble)
+    if X.ndim != 2 or X.shape[0] < 2:
+        raise ValueError(f"column_covariance_reference: (N, D) rows with N >= 2 needed (got {X.shape})")
+    mean = X.sum(axis=0) / X.shape[0]
+    Xc = X - mean
+    return mean, Xc.T @ Xc / (X.shape[0] - 1)
+
+
+def column_covariance(X, out=None):
+    """(mean (D,) fp64, cov (D, D) fp64) on the device: the column means of the fp32 rows X and the covariance of the centred
+    rows, cov = (X - mean)^T (X - mean) / (N - 1), symmetric bit for bit (msn_column_cov, csrc/vicreg.hip: the rows are centred
+    on their way into the fp64 matrix product, so there is no X^T X - N mean mean^T cancellation).  N >= 2, D <= 256.
+    out: (mean, cov) to write into.  Enqueue only."""
+    X = rows_on_gpu(X, "column_covariance", "embeddings")
+    N, D = X.shape
+    if N < 2:
+        raise _lib.MsnHipError(f"column_covariance: N must be at least 2 (got {N}): one row has no covariance")
+    if not 1 <= D <= COV_MAX_D:
+        raise _lib.MsnHipError(f"column_covariance: D must be in 1..{COV_MAX_D} (got {D}); wider embeddings are not built")
+    if out is None:
+        mean = torch.empty(D, dtype=torch.float64, device=X.device)
+        cov = torch.empty((D, D), dtype=torch.float64, device=X.device)
+    else:
+        mean, cov = out
+        for name, a, shape in (("mean", mean, (D,)), ("cov", cov, (D, D))):
+            if a.dtype != torch.float64 or a.device != X.device or not a.is_contiguous() or tuple(a.shape) != shape:
+                raise ValueError(f"column_covariance: out {name} must be a contiguous float64 tensor of shape {shape} on {X.device}")
+    L = lib()
+    ws = workspace(L.msn_column_cov_workspace_bytes(N, D), X.device)
+    check(L.msn_column_cov(ptr(X), ld(X), N, D, ptr(mean), ptr(cov), ptr(ws), ws.numel(), stream_ptr()), "msn_column_cov")
+    return mean, cov
 
 
 def _unit_rows(X, who):

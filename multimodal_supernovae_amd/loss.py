@@ -6,6 +6,8 @@
                                                                    -- Wang & Isola 2020: no scale, no bias (below)
     supcon_loss(embs1, embs2, labels, logit_scale, logit_bias), supcon_loss_multimodal(embeddings, labels, ...)
                                                                    -- label-aware InfoNCE (SupCon / UniCL), csrc/supcon.hip (below)
+    vicreg_loss(embs1, embs2, sim_coeff, std_coeff, cov_coeff, gamma, eps), vicreg_loss_multimodal(embeddings, ...)
+                                                                   -- Bardes, Ponce, LeCun 2022: no negatives, csrc/vicreg.hip (below)
 
 `logit_scale` is the LOG of the scale (the kernel exponentiates it, ref :22).  Tensors in,
 0-dim tensor out, differentiable w.r.t. both embedding matrices, the scale and the bias.
@@ -480,6 +482,153 @@ def align_uniform_reference(embs, alpha=2, t=2.0, lam=1.0):
         grads[i] += k[:, None] * diff
         grads[j] -= k[:, None] * diff
     return loss, grads
+
+
+# --------------------------------------------------------------------------- VICReg (Bardes, Ponce, LeCun 2022)
+VICREG_MAX_D = 256
+
+
+def _vicreg_args(embs, sim_coeff, std_coeff, cov_coeff, gamma, eps):
+    """The refusals of the C-ABI (msn_column_cov, msn_vicreg_fwd / _bwd), made before anything is enqueued."""
+    import math
+    coeffs = []
+    for name, v in (("sim_coeff", sim_coeff), ("std_coeff", std_coeff), ("cov_coeff", cov_coeff)):
+        v = float(v)
+        if not (v >= 0 and math.isfinite(v)):
+            raise ValueError(f"vicreg_loss: {name} must be finite and not negative (got {v})")
+        coeffs.append(v)
+    gamma, eps = float(gamma), float(eps)
+    if not (gamma >= 0 and math.isfinite(gamma)):
+        raise ValueError(f"vicreg_loss: gamma must be finite and not negative (got {gamma})")
+    if not (eps > 0 and math.isfinite(eps)):
+        raise ValueError(f"vicreg_loss: eps must be finite and positive (got {eps})")
+    if len(embs) < 2:
+        raise ValueError("vicreg_loss_multimodal needs at least two modalities")
+    _lib.require_gpu()
+    _device_f32(*[(f"embeddings[{k}]", e) for k, e in enumerate(embs)])
+    shape = tuple(embs[0].shape)
+    if len(shape) != 2 or any(tuple(e.shape) != shape for e in embs):
+        raise ValueError(f"vicreg_loss: (N, D) partner sets of one shape needed (got {[tuple(e.shape) for e in embs]})")
+    if shape[0] < 2:
+        raise _lib.MsnHipError(f"vicreg_loss: N must be at least 2 (got {shape[0]}): one row has no variance")
+    if not 1 <= shape[1] <= VICREG_MAX_D:
+        raise _lib.MsnHipError(f"vicreg_loss: D must be in 1..{VICREG_MAX_D} (got {shape[1]}); wider embeddings are not built")
+    return (*coeffs, gamma, eps)
+
+
+class _VICReg(torch.autograd.Function):
+    """Every modality pair i < j of one step as ONE node.  The means and the covariance of each tower run once (msn_column_cov);
+    each pair adds its invariance term and the variance and covariance terms of its two towers, so a tower's two terms and its
+    product (X - mean) M carry the weight m - 1.  Nothing is read back: the incoming gradient stays on the device."""
+
+    @staticmethod
+    def forward(ctx, sim_coeff, std_coeff, cov_coeff, gamma, eps, *embs):
+        from ._device_args import workspace
+        from .embedding_metrics import column_covariance
+        m = len(embs)
+        pairs = list(_pairs(range(m), 2))
+        embs = [e.detach().contiguous() for e in embs]
+        N, D = embs[0].shape
+        dev = embs[0].device
+        L = lib()
+        stats = [column_covariance(e) for e in embs]
+        losses, comps, Ms = [], [], []
+        for i, j in pairs:
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            comp = torch.empty(5, dtype=torch.float64, device=dev)
+            M = torch.empty((2, D, D), dtype=torch.float64, device=dev)
+            ws = workspace(L.msn_vicreg_workspace_bytes(N, D), dev)
+            check(L.msn_vicreg_fwd(ptr(embs[i]), embs[i].stride(0), ptr(embs[j]), embs[j].stride(0), N, D, ptr(stats[i][1]),
+                                   ptr(stats[j][1]), sim_coeff, std_coeff, cov_coeff, gamma, eps, ptr(loss), ptr(comp), ptr(M[0]),
+                                   ptr(M[1]), ptr(ws), ws.numel(), stream_ptr()), "msn_vicreg_fwd")
+            losses.append(loss)
+            comps.append(comp)
+            Ms.append(M)
+        ctx.m, ctx.pairs, ctx.sim_coeff = m, pairs, sim_coeff
+        ctx.save_for_backward(*embs, *[s[0] for s in stats], *Ms)
+        ctx.mark_non_differentiable(*comps)
+        total = losses[0] if len(losses) == 1 else torch.stack(losses).sum()
+        return (total, *comps)
+
+    @staticmethod
+    def backward(ctx, grad_out, *_):
+        m, pairs = ctx.m, ctx.pairs
+        s = ctx.saved_tensors
+        embs, means, Ms = s[:m], s[m:2 * m], s[2 * m:]
+        g = grad_out.to(torch.float32).reshape(()).contiguous()
+        N, D = embs[0].shape
+        L = lib()
+        d_emb = [None] * m
+        for k, (i, j) in enumerate(pairs):
+            d1, d2 = torch.empty_like(embs[i]), torch.empty_like(embs[j])
+            check(L.msn_vicreg_bwd(ptr(embs[i]), embs[i].stride(0), ptr(embs[j]), embs[j].stride(0), N, D, ptr(means[i]),
+                                   ptr(means[j]), ptr(Ms[k][0]), ptr(Ms[k][1]), ptr(g), ctx.sim_coeff, ptr(d1), D, ptr(d2), D,
+                                   stream_ptr()), "msn_vicreg_bwd")
+            d_emb[i] = d1 if d_emb[i] is None else d_emb[i].add_(d1)
+            d_emb[j] = d2 if d_emb[j] is None else d_emb[j].add_(d2)
+        return (None, None, None, None, None, *d_emb)
+
+
+def vicreg_loss_multimodal(embeddings, sim_coeff=25.0, std_coeff=25.0, cov_coeff=1.0, gamma=1.0, eps=1e-4, *,
+                           global_negatives=True, group=None, return_components=False):
+    """VICReg (Bardes, Ponce, LeCun 2022) summed over the modality pairs i < j, as align_uniform_loss_multimodal sums:
+
+        L(X, Y) = sim_coeff inv + std_coeff (var(X) + var(Y)) + cov_coeff (cov(X) + cov(Y))
+        inv = mean_ic (x_ic - y_ic)^2,  var(X) = mean_c max(0, gamma - sqrt(C_cc + eps)),  cov(X) = (1 / D) sum_{c != c'} C_cc'^2
+
+    with C the covariance of the centred columns, C = Xc^T Xc / (N - 1), for (N, D) partner sets (not assumed unit-norm),
+    N >= 2, D <= 256; no negatives, no logit scale, no bias.  float32 0-dim tensor, differentiable w.r.t. every set; the hinge
+    is inactive at sqrt(C_cc + eps) == gamma.  return_components=True adds, per pair, the fp64 device block
+    (inv, var_x, var_y, cov_x, cov_y).
+    Data parallel: each rank's own batch is one loss under the ordinary all-reduce of the gradients (global_negatives=False);
+    statistics over the rows of every rank are not built and are refused."""
+    embeddings = list(embeddings)
+    args = _vicreg_args(embeddings, sim_coeff, std_coeff, cov_coeff, gamma, eps)
+    if _is_sharded(global_negatives, group):
+        raise NotImplementedError("vicreg_loss: means and covariances over the rows of every rank are not built; pass "
+                                  "global_negatives=False (each rank's batch is its own loss; the gradients are all-reduced as usual)")
+    out = _VICReg.apply(*args, *embeddings)
+    return (out[0], list(out[1:])) if return_components else out[0]
+
+
+def vicreg_loss(e1, e2, sim_coeff=25.0, std_coeff=25.0, cov_coeff=1.0, gamma=1.0, eps=1e-4, *, global_negatives=True, group=None):
+    """vicreg_loss_multimodal of one modality pair."""
+    return vicreg_loss_multimodal([e1, e2], sim_coeff, std_coeff, cov_coeff, gamma, eps, global_negatives=global_negatives,
+                                  group=group)
+
+
+def vicreg_reference(embs, sim_coeff=25.0, std_coeff=25.0, cov_coeff=1.0, gamma=1.0, eps=1e-4, return_terms=False):
+    """numpy longdouble restatement: (loss, [gradient per set]) of vicreg_loss_multimodal.  return_terms=True adds
+    {"inv": {(i, j): .}, "var": [per set], "cov": [per set]}.  No GPU needed."""
+    import numpy as np
+    from .embedding_metrics import column_covariance_reference
+    X = [np.asarray(e, dtype=np.float32).astype(np.longdouble) for e in embs]
+    m = len(X)
+    if m < 2 or X[0].ndim != 2 or X[0].shape[0] < 2 or any(x.shape != X[0].shape for x in X):
+        raise ValueError("vicreg_reference: at least two (N, D) sets of one shape with N >= 2 needed")
+    N, D = X[0].shape
+    sim, std, covc, gamma, eps = (np.longdouble(v) for v in (sim_coeff, std_coeff, cov_coeff, gamma, eps))
+    loss = np.longdouble(0)
+    grads = [np.zeros(x.shape, dtype=np.longdouble) for x in X]
+    terms = {"inv": {}, "var": [], "cov": []}
+    for x, g in zip(X, grads):
+        mean, C = column_covariance_reference(x)
+        s = np.sqrt(np.diag(C) + eps)
+        off = C - np.diag(np.diag(C))
+        var, cov = np.maximum(gamma - s, 0).sum() / D, (off ** 2).sum() / D
+        terms["var"].append(var)
+        terms["cov"].append(cov)
+        loss += (m - 1) * (std * var + covc * cov)
+        M = 4 * covc / (D * np.longdouble(N - 1)) * off - np.diag(np.where(s < gamma, std / (D * np.longdouble(N - 1) * s), 0))
+        g += (m - 1) * ((x - mean) @ M)
+    for i, j in _pairs(range(m), 2):
+        diff = X[i] - X[j]
+        inv = (diff ** 2).sum() / (np.longdouble(N) * D)
+        terms["inv"][(i, j)] = inv
+        loss += sim * inv
+        grads[i] += 2 * sim / (np.longdouble(N) * D) * diff
+        grads[j] -= 2 * sim / (np.longdouble(N) * D) * diff
+    return (loss, grads, terms) if return_terms else (loss, grads)
 
 
 # --------------------------------------------------------------------------- label-aware contrastive loss (SupCon / UniCL)

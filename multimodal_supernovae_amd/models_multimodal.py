@@ -105,7 +105,12 @@ class MLP(nn.Module):
 class LightCurveImageCLIP(nn.Module):
     """ref src/models_multimodal.py:98-556 (contrastive branch).  A plain nn.Module exposing the
     LightningModule hooks the reference implements (training_step, validation_step,
-    configure_optimizers, on_*), driven by multimodal_supernovae_amd.trainer.Trainer."""
+    configure_optimizers, on_*), driven by multimodal_supernovae_amd.trainer.Trainer.
+
+    loss="vicreg" (loss.vicreg_loss_multimodal) takes loss_kwargs sim_coeff, std_coeff, cov_coeff, gamma and eps.  The model's
+    embeddings are unit-norm, so a column's standard deviation cannot exceed 1 / sqrt(enc_dim) on average and the paper's
+    gamma = 1 can never be met: when gamma is not given, the model passes gamma = 1 / sqrt(enc_dim) (the free functions keep the
+    paper's default).  As under "align_uniform", logit_scale and logit_bias stay in the state_dict and take no gradient."""
 
     def __init__(self, enc_dim: int = 128, logit_scale: float = 10.0, nband: int = 1,
                  transformer_kwargs: Optional[Dict] = None, transformer_spectral_kwargs: Optional[Dict] = None,
@@ -116,11 +121,18 @@ class LightCurveImageCLIP(nn.Module):
                  embedding_metrics: bool = False, loss_kwargs: Optional[Dict] = None):
         super().__init__()
         loss_kwargs = dict(loss_kwargs or {})
-        if loss_kwargs and loss != "align_uniform":
-            raise ValueError(f"loss_kwargs belongs to loss='align_uniform' (got loss={loss!r})")
-        unknown = set(loss_kwargs) - {"alpha", "t", "lam"}
-        if unknown:
-            raise ValueError(f"loss_kwargs takes alpha, t and lam (got {sorted(unknown)})")
+        if loss_kwargs and loss not in ("align_uniform", "vicreg"):
+            raise ValueError(f"loss_kwargs belongs to loss='align_uniform' or loss='vicreg' (got loss={loss!r})")
+        if loss == "vicreg":
+            unknown = set(loss_kwargs) - {"sim_coeff", "std_coeff", "cov_coeff", "gamma", "eps"}
+            if unknown:
+                raise ValueError(f"loss_kwargs takes sim_coeff, std_coeff, cov_coeff, gamma and eps (got {sorted(unknown)})")
+            # unit-norm rows: the columns' variances sum to at most 1, so the paper's gamma = 1 can never be met
+            loss_kwargs.setdefault("gamma", 1.0 / math.sqrt(enc_dim))
+        else:
+            unknown = set(loss_kwargs) - {"alpha", "t", "lam"}
+            if unknown:
+                raise ValueError(f"loss_kwargs takes alpha, t and lam (got {sorted(unknown)})")
         if regression or classification:
             raise NotImplementedError("this class is the contrastive model; the supervised regression / classification "
                                       "heads are models_finetune.ClipMLP(clip_model, regression=... / classification=...)")
@@ -153,9 +165,9 @@ class LightCurveImageCLIP(nn.Module):
             self.class_emb = nn.Embedding(n_classes, self.len_meta_input // 2)
             meta_kwargs.setdefault("dropout", 0.0)
             self.meta_encoder = MLP(output_dim=enc_dim, **meta_kwargs)
-        self.loss = loss                                      # "softmax", "sigmoid", "align_uniform" or "supcon" (reads the batch's class labels)
-        self.loss_kwargs = loss_kwargs                        # alpha, t, lam of loss="align_uniform" (loss.align_uniform_loss)
-        if loss == "align_uniform":
+        self.loss = loss                                      # "softmax", "sigmoid", "align_uniform", "vicreg" or "supcon" (reads the batch's class labels)
+        self.loss_kwargs = loss_kwargs                        # alpha, t, lam of loss="align_uniform" (loss.align_uniform_loss); sim_coeff, std_coeff, cov_coeff, gamma, eps of loss="vicreg"
+        if loss in ("align_uniform", "vicreg"):
             # the loss has no scale and no bias: both stay (the state_dict keeps its names) and take no gradient, so the
             # optimizers, the accumulator, the clipper and the averager pass them by
             self.logit_scale.requires_grad_(False)
@@ -256,6 +268,10 @@ class LightCurveImageCLIP(nn.Module):
             from .loss import align_uniform_loss_multimodal
             with markers.range("alignment + uniformity forward"):
                 return align_uniform_loss_multimodal(embs, **self.loss_kwargs, global_negatives=self.global_negatives)
+        if self.loss == "vicreg":
+            from .loss import vicreg_loss_multimodal
+            with markers.range("VICReg forward"):
+                return vicreg_loss_multimodal(embs, **self.loss_kwargs, global_negatives=self.global_negatives)
         raise ValueError(f"unknown loss {self.loss!r}")
 
     def training_step(self, batch, batch_idx):
