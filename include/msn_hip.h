@@ -1200,6 +1200,67 @@ int msn_vicreg_bwd(const float* X, int64_t ldx, const float* Y, int64_t ldy, int
                    int64_t lddx, float* dY, int64_t lddy, msn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Barlow Twins (Zbontar et al. 2021) as a training loss (loss.py; csrc/barlow.hip): the centred cross covariance of two towers
+ * with their biased variances, the loss and the product of its gradient.  X, Y (N, D) fp32 with row strides >= D, 4-byte
+ * aligned, not assumed unit-norm; 2 <= N < 2^31, 1 <= D <= 256.  Everything below is fp64 on the device, enqueue only, no
+ * atomics, no fills, no zeroed scratch; every load of X and Y is a 4-byte load, so the bits depend on the values, N and D only
+ * (not on stride, alignment or run).  Non-finite inputs are not checked and propagate.
+ *
+ *   mean_x, mean_y column means, Xc = X - mean_x, Yc = Y - mean_y
+ *   v_x[a] = (1 / N) sum_i Xc_ia^2    s_x[a] = sqrt(v_x[a] + eps)     (BatchNorm1d(affine=False): biased, eps inside the root)
+ *   cov[a][b] = (1 / N) sum_i Xc_ia Yc_ib  (D x D, not symmetric)     c[a][b] = cov[a][b] / (s_x[a] s_y[b])
+ *   on = sum_a (c_aa - 1)^2    off = sum_{a != b} c_ab^2    L = on + lambd off
+ *   G_ab = 2 (c_aa - 1) if a == b else 2 lambd c_ab    A_ab = G_ab / (N s_x[a] s_y[b])    r_a = sum_b G_ab c_ab    q_b = sum_a G_ab c_ab
+ *   dL/dX = Yc A^T + Xc diag(d_x), d_x[a] = -r_a / (N (v_x[a] + eps))    dL/dY = Xc A + Yc diag(d_y), d_y[b] = -q_b / (N (v_y[b] + eps))
+ *   (BatchNorm's mean_i(dL/dxhat) term combines the column means of the standardised partner, which are zero: left out.)
+ *
+ * Cross covariance (three launches): mean_x, mean_y, var_x, var_y (D each) and cov (D x D).
+ *   Plan, a function of (N, D) alone (no device query):
+ *     means: mrows = max(64, ceil(N / 64)) rows per slab, mslabs = ceil(N / mrows); a thread adds one column of its slab in row
+ *     order, the slabs are added in slab order from slab 0 on, then one division by N (as msn_column_cov);
+ *     Gram: T = ceil(D / 64) column tiles, pairs = T^2 tile pairs (a, b), pair = a T + b (every pair is distinct), chunks =
+ *     ceil(N / 32), per = max(4, ceil(chunks / ceil(512 / pairs))), slabs = ceil(chunks / per): workgroup (pair, slab) multiplies
+ *     the 32 per rows of its slab on v_mfma_f64_16x16x4_f64, tile a of X against tile b of Y, staged as doubles with the mean
+ *     subtracted on the way into LDS (one rounding per element; no X^T Y - N mean_x mean_y^T cancellation);
+ *     variances: from the same staged doubles, X's in the workgroups with b == 0, Y's in those with a == 0: a thread adds the
+ *     squares of the rows rr, rr + 4, ... (rr = 0..3) of its column by fma in row order, the four threads of a column are added
+ *     in the order of rr, the slabs in slab order, one division by N (no E[x^2] - mean^2);
+ *     the finishing launch adds the slabs' partials in slab order and divides by N.
+ *   Additions at most on a term's way
+ *     to a mean:                A_mean(N)   = mrows + mslabs
+ *     to a variance:            A_var(N, D) = 8 per + 4 + slabs
+ *     to a covariance entry:    A_cov(N, D) = 32 per + slabs     (4 per matrix instruction, 8 instructions per 32 rows, the slabs)
+ *   ws: msn_cross_cov_workspace_bytes = 8 (2 mslabs D + 2 slabs D + 4096 slabs pairs) bytes.
+ *
+ * Forward (two launches, D^2 work, never touches X or Y): from var_x, var_y, cov it writes corr (D x D), comp (2 doubles) =
+ *   (on, off), loss (1 float) = on + lambd off rounded once from fp64, M_x = A^T and M_y = A (D x D: both backward products read
+ *   their matrix row-major along the inner index), d_x, d_y (D).  One entry per thread and step over blocks = min(ceil(D^2 / 256),
+ *   64) workgroups, (c_aa - 1)^2 and c_ab^2 added by fma, the xor tree, the four waves in order, one finishing workgroup likewise:
+ *     to on or off:             A_dd(D)     = ceil(D^2 / (256 blocks)) + 9 + ceil(blocks / 256) + 9
+ *   r_a and q_b by one thread each, G c added by fma over the D entries of the row or column in index order:
+ *     to r_a or q_b:            A_rq(D)     = D
+ *   ws: msn_barlow_workspace_bytes = 16 blocks bytes.
+ * Backward (one launch): P_x = Yc M_x, P_y = Xc M_y on the same instruction, a 64 x 64 tile of P per workgroup, its fp64
+ *   accumulator in registers, the PARTNER's centred rows staged 32 inner columns at a time and M in chunks of 32 x 64 through LDS,
+ *     to an entry of P:         A_p(D)      = 32 ceil(D / 32)
+ *   dX = fl32(g (P_x + d_x[a] (x_ia - mean_x[a]))), dY = fl32(g (P_y + d_y[b] (y_ib - mean_y[b]))), g a DEVICE float.  Rows past N
+ *   are never read and never written (dX, dY have row strides lddx, lddy >= D).
+ * No host read anywhere: the step records into a graph.
+ * MSN_ERR_SHAPE before any launch: D outside 1..256, N < 2 or >= 2^31, lambd negative or not finite, eps not finite or <= 0, a
+ * null pointer, a misaligned pointer, a row stride below D, a workspace that is too small (the queries return 0 for a refused
+ * shape). */
+size_t msn_cross_cov_workspace_bytes(int64_t N, int D);
+int msn_cross_cov(const float* X, int64_t ldx, const float* Y, int64_t ldy, int64_t N, int D, double* mean_x, double* mean_y,
+                  double* var_x, double* var_y, double* cov, void* ws, size_t ws_bytes, msn_stream_t stream);
+size_t msn_barlow_workspace_bytes(int D);
+int msn_barlow_fwd(const double* var_x, const double* var_y, const double* cov, int64_t N, int D, double lambd, double eps,
+                   float* loss, double* comp, double* corr, double* M_x, double* M_y, double* d_x, double* d_y, void* ws,
+                   size_t ws_bytes, msn_stream_t stream);
+int msn_barlow_bwd(const float* X, int64_t ldx, const float* Y, int64_t ldy, int64_t N, int D, const double* mean_x,
+                   const double* mean_y, const double* M_x, const double* M_y, const double* d_x, const double* d_y, const float* g,
+                   float* dX, int64_t lddx, float* dY, int64_t lddy, msn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Threshold-free classification metrics (metrics.py; csrc/rank_metrics.hip): one-vs-rest AUROC, average precision, binned
  * ROC / precision-recall curves and top-k accuracy from integer counts.  Shared by the four entry points: S (N, C) fp32
  * scores with row stride ld >= C, 4-byte aligned (every load of S is a 4-byte load: the bits do not depend on stride or

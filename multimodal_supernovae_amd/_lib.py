@@ -173,6 +173,13 @@ SIGNATURES = {
                                c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "msn_vicreg_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f64, c_ptr, c_i64, c_ptr,
                                c_i64, c_ptr]),
+    "msn_cross_cov_workspace_bytes": (c_size, [c_i64, c_int]),
+    "msn_cross_cov": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "msn_barlow_workspace_bytes": (c_size, [c_int]),
+    "msn_barlow_fwd": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_f64, c_f64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                               c_size, c_ptr]),
+    "msn_barlow_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64,
+                               c_ptr, c_i64, c_ptr]),
     "msn_rank_counts_workspace_bytes": (c_size, [c_i64, c_int]),
     "msn_rank_counts": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "msn_threshold_counts": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),

@@ -11,6 +11,9 @@ al. 2022), effective rank / RankMe (Garrido et al. 2023), and recall@k, MRR and 
     column_covariance the column means and the covariance of the centred rows in fp64 on the device (csrc/vicreg.hip:
                       msn_column_cov): what loss.vicreg_loss regularises.  D <= 256.  Enqueue only.  (covariance_spectrum still
                       goes through probes.probe_gram.)  column_covariance_reference is its longdouble restatement.
+    cross_correlation the column means, the biased variances, the cross covariance and the cross correlation of two towers in
+                      fp64 on the device (csrc/barlow.hip: msn_cross_cov, msn_barlow_fwd): what loss.barlow_twins_loss drives to
+                      the identity.  D <= 256.  Enqueue only.  cross_correlation_reference is its longdouble restatement.
     uniformity, cross_uniformity, alignment
                       the figures of one call: one host copy each
     covariance_spectrum, effective_rank, participation_ratio, modality_gap
@@ -323,6 +326,75 @@ def column_covariance(X, out=None):
     ws = workspace(L.msn_column_cov_workspace_bytes(N, D), X.device)
     check(L.msn_column_cov(ptr(X), ld(X), N, D, ptr(mean), ptr(cov), ptr(ws), ws.numel(), stream_ptr()), "msn_column_cov")
     return mean, cov
+
+
+def cross_correlation_reference(X, Y, eps=1e-5):
+    """numpy longdouble restatement of cross_correlation: (mean_x, mean_y, var_x, var_y, cov, corr) of the fp32 rows X, Y, with
+    BatchNorm's statistics: var and cov divide by N (column_covariance_reference divides by N - 1), corr[a][b] = cov[a][b] /
+    (sqrt(var_x[a] + eps) sqrt(var_y[b] + eps)).  No GPU needed."""
+    X = np.asarray(X, dtype=np.float32).astype(np.longdouble)
+    Y = np.asarray(Y, dtype=np.float32).astype(np.longdouble)
+    if X.ndim != 2 or X.shape[0] < 2 or X.shape != Y.shape:
+        raise ValueError(f"cross_correlation_reference: two (N, D) sets of one shape with N >= 2 needed (got {X.shape}, {Y.shape})")
+    n = np.longdouble(X.shape[0])
+    mx, my = X.sum(axis=0) / n, Y.sum(axis=0) / n
+    Xc, Yc = X - mx, Y - my
+    vx, vy = (Xc * Xc).sum(axis=0) / n, (Yc * Yc).sum(axis=0) / n
+    cov = Xc.T @ Yc / n
+    eps = np.longdouble(eps)
+    return mx, my, vx, vy, cov, cov / np.outer(np.sqrt(vx + eps), np.sqrt(vy + eps))
+
+
+def _cross_cov(X, Y):
+    """(mean_x, mean_y, var_x, var_y, cov) of two checked (N, D) fp32 sets on one device: msn_cross_cov into fresh tensors."""
+    N, D = X.shape
+    stats = torch.empty((4, D), dtype=torch.float64, device=X.device)
+    cov = torch.empty((D, D), dtype=torch.float64, device=X.device)
+    L = lib()
+    ws = workspace(L.msn_cross_cov_workspace_bytes(N, D), X.device)
+    check(L.msn_cross_cov(ptr(X), ld(X), ptr(Y), ld(Y), N, D, ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]), ptr(cov),
+                          ptr(ws), ws.numel(), stream_ptr()), "msn_cross_cov")
+    return stats[0], stats[1], stats[2], stats[3], cov
+
+
+def _barlow_fwd(var_x, var_y, cov, N, lambd, eps):
+    """(loss, comp, corr, M (2, D, D), d (2, D)) of msn_barlow_fwd from the statistics of _cross_cov."""
+    D = cov.shape[0]
+    dev = cov.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    comp = torch.empty(2, dtype=torch.float64, device=dev)
+    corr = torch.empty((D, D), dtype=torch.float64, device=dev)
+    M = torch.empty((2, D, D), dtype=torch.float64, device=dev)
+    d = torch.empty((2, D), dtype=torch.float64, device=dev)
+    L = lib()
+    ws = workspace(L.msn_barlow_workspace_bytes(D), dev)
+    check(L.msn_barlow_fwd(ptr(var_x), ptr(var_y), ptr(cov), N, D, lambd, eps, ptr(loss), ptr(comp), ptr(corr), ptr(M[0]), ptr(M[1]),
+                           ptr(d[0]), ptr(d[1]), ptr(ws), ws.numel(), stream_ptr()), "msn_barlow_fwd")
+    return loss, comp, corr, M, d
+
+
+def cross_correlation(X, Y, eps=1e-5):
+    """(mean_x (D,), mean_y (D,), var_x (D,), var_y (D,), cov (D, D), corr (D, D)), fp64 on the device, of the fp32 rows X, Y:
+    the column means, the variances and the cross covariance of the centred rows, cov = (X - mean_x)^T (Y - mean_y) / N (not
+    symmetric), and corr[a][b] = cov[a][b] / (sqrt(var_x[a] + eps) sqrt(var_y[b] + eps)).  These are BatchNorm's statistics:
+    the variance and the covariance divide by N, where column_covariance divides by N - 1.  The rows are centred on their way
+    into the fp64 matrix product (msn_cross_cov, csrc/barlow.hip), so nothing cancels.  N >= 2, D <= 256.  Enqueue only."""
+    import math
+    eps = float(eps)
+    if not (eps > 0 and math.isfinite(eps)):
+        raise ValueError(f"cross_correlation: eps must be finite and positive (got {eps})")
+    X = rows_on_gpu(X, "cross_correlation", "embeddings")
+    Y = rows_on_gpu(Y, "cross_correlation", "embeddings")
+    if tuple(X.shape) != tuple(Y.shape) or X.device != Y.device:
+        raise ValueError(f"cross_correlation: two (N, D) sets of one shape on one device needed (got {tuple(X.shape)}, {tuple(Y.shape)})")
+    N, D = X.shape
+    if N < 2:
+        raise _lib.MsnHipError(f"cross_correlation: N must be at least 2 (got {N}): one row has no variance")
+    if not 1 <= D <= COV_MAX_D:
+        raise _lib.MsnHipError(f"cross_correlation: D must be in 1..{COV_MAX_D} (got {D}); wider embeddings are not built")
+    mx, my, vx, vy, cov = _cross_cov(X, Y)
+    corr = _barlow_fwd(vx, vy, cov, N, 0.0, eps)[2]
+    return mx, my, vx, vy, cov, corr
 
 
 def _unit_rows(X, who):

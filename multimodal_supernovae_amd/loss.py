@@ -8,6 +8,9 @@
                                                                    -- label-aware InfoNCE (SupCon / UniCL), csrc/supcon.hip (below)
     vicreg_loss(embs1, embs2, sim_coeff, std_coeff, cov_coeff, gamma, eps), vicreg_loss_multimodal(embeddings, ...)
                                                                    -- Bardes, Ponce, LeCun 2022: no negatives, csrc/vicreg.hip (below)
+    barlow_twins_loss(embs1, embs2, lambd, eps), barlow_twins_loss_multimodal(embeddings, ...)
+                                                                   -- Zbontar et al. 2021: the cross correlation of two towers driven to
+                                                                      the identity, csrc/barlow.hip (below)
 
 `logit_scale` is the LOG of the scale (the kernel exponentiates it, ref :22).  Tensors in,
 0-dim tensor out, differentiable w.r.t. both embedding matrices, the scale and the bias.
@@ -628,6 +631,138 @@ def vicreg_reference(embs, sim_coeff=25.0, std_coeff=25.0, cov_coeff=1.0, gamma=
         loss += sim * inv
         grads[i] += 2 * sim / (np.longdouble(N) * D) * diff
         grads[j] -= 2 * sim / (np.longdouble(N) * D) * diff
+    return (loss, grads, terms) if return_terms else (loss, grads)
+
+
+# --------------------------------------------------------------------------- Barlow Twins (Zbontar et al. 2021)
+BARLOW_MAX_D = 256
+
+
+def _barlow_args(embs, lambd, eps):
+    """The refusals of the C-ABI (msn_cross_cov, msn_barlow_fwd / _bwd), made before anything is enqueued."""
+    import math
+    lambd, eps = float(lambd), float(eps)
+    if not (lambd >= 0 and math.isfinite(lambd)):
+        raise ValueError(f"barlow_twins_loss: lambd must be finite and not negative (got {lambd})")
+    if not (eps > 0 and math.isfinite(eps)):
+        raise ValueError(f"barlow_twins_loss: eps must be finite and positive (got {eps})")
+    if len(embs) < 2:
+        raise ValueError("barlow_twins_loss_multimodal needs at least two modalities")
+    _lib.require_gpu()
+    _device_f32(*[(f"embeddings[{k}]", e) for k, e in enumerate(embs)])
+    shape = tuple(embs[0].shape)
+    if len(shape) != 2 or any(tuple(e.shape) != shape for e in embs):
+        raise ValueError(f"barlow_twins_loss: (N, D) partner sets of one shape needed (got {[tuple(e.shape) for e in embs]})")
+    if shape[0] < 2:
+        raise _lib.MsnHipError(f"barlow_twins_loss: N must be at least 2 (got {shape[0]}): one row has no variance")
+    if not 1 <= shape[1] <= BARLOW_MAX_D:
+        raise _lib.MsnHipError(f"barlow_twins_loss: D must be in 1..{BARLOW_MAX_D} (got {shape[1]}); wider embeddings are not built")
+    return lambd, eps
+
+
+class _BarlowTwins(torch.autograd.Function):
+    """Every modality pair i < j of one step as ONE node.  Each pair runs its own statistics (msn_cross_cov: the means and
+    variances of both towers and their cross covariance) and the D^2 assembly (msn_barlow_fwd) in forward; the means, M and d are
+    saved, and each pair's backward launch adds into its two towers' gradients.  Nothing is read back: the incoming gradient
+    stays on the device."""
+
+    @staticmethod
+    def forward(ctx, lambd, eps, *embs):
+        from .embedding_metrics import _barlow_fwd, _cross_cov
+        m = len(embs)
+        pairs = list(_pairs(range(m), 2))
+        embs = [e.detach().contiguous() for e in embs]
+        N = embs[0].shape[0]
+        losses, comps, saved = [], [], []
+        for i, j in pairs:
+            mx, my, vx, vy, cov = _cross_cov(embs[i], embs[j])
+            loss, comp, _, M, d = _barlow_fwd(vx, vy, cov, N, lambd, eps)
+            losses.append(loss)
+            comps.append(comp)
+            saved += [mx, my, M, d]
+        ctx.m, ctx.pairs = m, pairs
+        ctx.save_for_backward(*embs, *saved)
+        ctx.mark_non_differentiable(*comps)
+        total = losses[0] if len(losses) == 1 else torch.stack(losses).sum()
+        return (total, *comps)
+
+    @staticmethod
+    def backward(ctx, grad_out, *_):
+        m, pairs = ctx.m, ctx.pairs
+        s = ctx.saved_tensors
+        embs, saved = s[:m], s[m:]
+        g = grad_out.to(torch.float32).reshape(()).contiguous()
+        N, D = embs[0].shape
+        L = lib()
+        d_emb = [None] * m
+        for k, (i, j) in enumerate(pairs):
+            mx, my, M, d = saved[4 * k:4 * k + 4]
+            d1, d2 = torch.empty_like(embs[i]), torch.empty_like(embs[j])
+            check(L.msn_barlow_bwd(ptr(embs[i]), embs[i].stride(0), ptr(embs[j]), embs[j].stride(0), N, D, ptr(mx), ptr(my), ptr(M[0]),
+                                   ptr(M[1]), ptr(d[0]), ptr(d[1]), ptr(g), ptr(d1), D, ptr(d2), D, stream_ptr()), "msn_barlow_bwd")
+            d_emb[i] = d1 if d_emb[i] is None else d_emb[i].add_(d1)
+            d_emb[j] = d2 if d_emb[j] is None else d_emb[j].add_(d2)
+        return (None, None, *d_emb)
+
+
+def barlow_twins_loss_multimodal(embeddings, lambd=5e-3, eps=1e-5, *, global_negatives=True, group=None, return_components=False):
+    """Barlow Twins (Zbontar, Jing, Misra, LeCun, Deny 2021) summed over the modality pairs i < j:
+
+        L(X, Y) = sum_a (c_aa - 1)^2 + lambd sum_{a != b} c_ab^2,    c = Xhat^T Yhat / N
+
+    with Xhat, Yhat the columns standardised as BatchNorm1d(affine=False) does in training (biased variance, eps inside the
+    root), for (N, D) partner sets (not assumed unit-norm), N >= 2, D <= 256; no negatives, no logit scale, no bias, no scale
+    factor on the loss.  float32 0-dim tensor, differentiable w.r.t. every set.  return_components=True adds, per pair, the
+    fp64 device block (on, off).
+    Data parallel: each rank's own batch is one loss under the ordinary all-reduce of the gradients (global_negatives=False);
+    statistics over the rows of every rank are not built and are refused."""
+    embeddings = list(embeddings)
+    args = _barlow_args(embeddings, lambd, eps)
+    if _is_sharded(global_negatives, group):
+        raise NotImplementedError("barlow_twins_loss: means and correlations over the rows of every rank are not built; pass "
+                                  "global_negatives=False (each rank's batch is its own loss; the gradients are all-reduced as usual)")
+    out = _BarlowTwins.apply(*args, *embeddings)
+    return (out[0], list(out[1:])) if return_components else out[0]
+
+
+def barlow_twins_loss(e1, e2, lambd=5e-3, eps=1e-5, *, global_negatives=True, group=None):
+    """barlow_twins_loss_multimodal of one modality pair."""
+    return barlow_twins_loss_multimodal([e1, e2], lambd, eps, global_negatives=global_negatives, group=group)
+
+
+def barlow_twins_reference(embs, lambd=5e-3, eps=1e-5, return_terms=False):
+    """numpy longdouble restatement: (loss, [gradient per set]) of barlow_twins_loss_multimodal.  return_terms=True adds
+    {"on": {(i, j): .}, "off": {(i, j): .}, "corr": {(i, j): c}, "magnitude": [per set]}, the last being the sum over the set's
+    pairs of |Yc A^T| + |Xc diag(d)|, the magnitudes of the two terms of its gradient (they nearly cancel where c is close to
+    +-1, so an error is measured against them and not against their difference).  No GPU needed."""
+    import numpy as np
+    X = [np.asarray(e, dtype=np.float32).astype(np.longdouble) for e in embs]
+    m = len(X)
+    if m < 2 or X[0].ndim != 2 or X[0].shape[0] < 2 or any(x.shape != X[0].shape for x in X):
+        raise ValueError("barlow_twins_reference: at least two (N, D) sets of one shape with N >= 2 needed")
+    N, D = X[0].shape
+    n, lam, eps = np.longdouble(N), np.longdouble(lambd), np.longdouble(eps)
+    diag = np.eye(D, dtype=bool)
+    loss = np.longdouble(0)
+    grads = [np.zeros(x.shape, dtype=np.longdouble) for x in X]
+    terms = {"on": {}, "off": {}, "corr": {}, "magnitude": [np.zeros(x.shape, dtype=np.longdouble) for x in X]}
+    for i, j in _pairs(range(m), 2):
+        xc, yc = X[i] - X[i].sum(axis=0) / n, X[j] - X[j].sum(axis=0) / n
+        sx, sy = np.sqrt((xc * xc).sum(axis=0) / n + eps), np.sqrt((yc * yc).sum(axis=0) / n + eps)
+        ss = np.outer(sx, sy)
+        c = (xc.T @ yc) / n / ss
+        on, off = ((np.diag(c) - 1) ** 2).sum(), (np.where(diag, 0, c) ** 2).sum()
+        G = np.where(diag, 2 * (c - 1), 2 * lam * c)
+        A = G / (n * ss)
+        r, q = (G * c).sum(axis=1), (G * c).sum(axis=0)
+        px, ox = yc @ A.T, xc * (-r / (n * sx * sx))
+        py, oy = xc @ A, yc * (-q / (n * sy * sy))
+        grads[i] += px + ox
+        grads[j] += py + oy
+        terms["magnitude"][i] += np.abs(px) + np.abs(ox)
+        terms["magnitude"][j] += np.abs(py) + np.abs(oy)
+        terms["on"][(i, j)], terms["off"][(i, j)], terms["corr"][(i, j)] = on, off, c
+        loss += on + lam * off
     return (loss, grads, terms) if return_terms else (loss, grads)
 
 

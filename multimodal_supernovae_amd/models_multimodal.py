@@ -110,7 +110,10 @@ class LightCurveImageCLIP(nn.Module):
     loss="vicreg" (loss.vicreg_loss_multimodal) takes loss_kwargs sim_coeff, std_coeff, cov_coeff, gamma and eps.  The model's
     embeddings are unit-norm, so a column's standard deviation cannot exceed 1 / sqrt(enc_dim) on average and the paper's
     gamma = 1 can never be met: when gamma is not given, the model passes gamma = 1 / sqrt(enc_dim) (the free functions keep the
-    paper's default).  As under "align_uniform", logit_scale and logit_bias stay in the state_dict and take no gradient."""
+    paper's default).  As under "align_uniform", logit_scale and logit_bias stay in the state_dict and take no gradient.
+
+    loss="barlow" (loss.barlow_twins_loss_multimodal) takes loss_kwargs lambd and eps.  The loss standardises every column
+    itself, so unit-norm rows need no other default; logit_scale and logit_bias are frozen as above."""
 
     def __init__(self, enc_dim: int = 128, logit_scale: float = 10.0, nband: int = 1,
                  transformer_kwargs: Optional[Dict] = None, transformer_spectral_kwargs: Optional[Dict] = None,
@@ -121,14 +124,18 @@ class LightCurveImageCLIP(nn.Module):
                  embedding_metrics: bool = False, loss_kwargs: Optional[Dict] = None):
         super().__init__()
         loss_kwargs = dict(loss_kwargs or {})
-        if loss_kwargs and loss not in ("align_uniform", "vicreg"):
-            raise ValueError(f"loss_kwargs belongs to loss='align_uniform' or loss='vicreg' (got loss={loss!r})")
+        if loss_kwargs and loss not in ("align_uniform", "vicreg", "barlow"):
+            raise ValueError(f"loss_kwargs belongs to loss='align_uniform', loss='vicreg' or loss='barlow' (got loss={loss!r})")
         if loss == "vicreg":
             unknown = set(loss_kwargs) - {"sim_coeff", "std_coeff", "cov_coeff", "gamma", "eps"}
             if unknown:
                 raise ValueError(f"loss_kwargs takes sim_coeff, std_coeff, cov_coeff, gamma and eps (got {sorted(unknown)})")
             # unit-norm rows: the columns' variances sum to at most 1, so the paper's gamma = 1 can never be met
             loss_kwargs.setdefault("gamma", 1.0 / math.sqrt(enc_dim))
+        elif loss == "barlow":
+            unknown = set(loss_kwargs) - {"lambd", "eps"}
+            if unknown:
+                raise ValueError(f"loss_kwargs takes lambd and eps (got {sorted(unknown)})")
         else:
             unknown = set(loss_kwargs) - {"alpha", "t", "lam"}
             if unknown:
@@ -165,9 +172,9 @@ class LightCurveImageCLIP(nn.Module):
             self.class_emb = nn.Embedding(n_classes, self.len_meta_input // 2)
             meta_kwargs.setdefault("dropout", 0.0)
             self.meta_encoder = MLP(output_dim=enc_dim, **meta_kwargs)
-        self.loss = loss                                      # "softmax", "sigmoid", "align_uniform", "vicreg" or "supcon" (reads the batch's class labels)
-        self.loss_kwargs = loss_kwargs                        # alpha, t, lam of loss="align_uniform" (loss.align_uniform_loss); sim_coeff, std_coeff, cov_coeff, gamma, eps of loss="vicreg"
-        if loss in ("align_uniform", "vicreg"):
+        self.loss = loss                                      # "softmax", "sigmoid", "align_uniform", "vicreg", "barlow" or "supcon" (reads the batch's class labels)
+        self.loss_kwargs = loss_kwargs                        # alpha, t, lam of loss="align_uniform" (loss.align_uniform_loss); sim_coeff, std_coeff, cov_coeff, gamma, eps of loss="vicreg"; lambd, eps of loss="barlow"
+        if loss in ("align_uniform", "vicreg", "barlow"):
             # the loss has no scale and no bias: both stay (the state_dict keeps its names) and take no gradient, so the
             # optimizers, the accumulator, the clipper and the averager pass them by
             self.logit_scale.requires_grad_(False)
@@ -272,6 +279,10 @@ class LightCurveImageCLIP(nn.Module):
             from .loss import vicreg_loss_multimodal
             with markers.range("VICReg forward"):
                 return vicreg_loss_multimodal(embs, **self.loss_kwargs, global_negatives=self.global_negatives)
+        if self.loss == "barlow":
+            from .loss import barlow_twins_loss_multimodal
+            with markers.range("Barlow Twins forward"):
+                return barlow_twins_loss_multimodal(embs, **self.loss_kwargs, global_negatives=self.global_negatives)
         raise ValueError(f"unknown loss {self.loss!r}")
 
     def training_step(self, batch, batch_idx):
