@@ -1261,6 +1261,48 @@ int msn_barlow_bwd(const float* X, int64_t ldx, const float* Y, int64_t ldy, int
                    float* dX, int64_t lddx, float* dY, int64_t lddy, msn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The sums of centred kernel alignment, CKA (Kornblith et al. 2019; the debiased minibatch form of Nguyen et al. 2021 with the
+ * HSIC estimator of Song et al. 2012) (embedding_metrics.py: hsic_sums, cka, CKA; csrc/cka.hip).  X (N, Dx), Y (N, Dy) fp32 with
+ * row strides >= D, 4-byte aligned, rows are partners; 2 <= N < 2^31, 1 <= Dx, Dy <= 1024 (they may differ).  Everything is fp64
+ * on the device, enqueue only, no atomics, no fills, no zeroed scratch, no host read; every load of X and Y is a 4-byte load, so
+ * the bits depend on the values, N, Dx, Dy only (not on stride, alignment or run).  Rows past N are never read.  Non-finite inputs
+ * are not checked and propagate.  Neither N x N matrix is written.
+ *
+ * xc, yc: the rows with the column means subtracted in fp64 ((double)x - mean, one rounding).  kernel 0 (linear): K_ij = xc_i . xc_j;
+ * kernel 1 (RBF): K_ij = exp(-d2_ij inv2s2_x), d2_ij = max(0, n_i + n_j - 2 xc_i . xc_j), n_i = |xc_i|^2, inv2s2 = 1 / (2 sigma^2);
+ * L likewise over Y.  sigma_x, sigma_y > 0 are used as given; 0 derives sigma^2 = sigma_scale^2 (2 / (N - 1)) sum_i n_i, the mean
+ * of d2 over i != j, on the device (equal rows: the sum is 0, inv2s2 is inf, and the set's sums are NaN).  The linear kernel
+ * ignores the three.  With rK_i = sum_j K_ij:
+ *   out[c][0 .. 7] = KL = sum_ij K_ij L_ij, KK, LL, rKL = sum_i rK_i rL_i, rKK, rLL, sK = sum_i rK_i, sL
+ * c = 0 over i != j, c = 1 with the diagonal K_ii = n_i (linear) or exactly 1 (RBF), from the row norms, never from d2.
+ *
+ * The plan, a function of N alone:
+ *   mrows = max(64, ceil(N / 64)), mslabs = ceil(N / mrows);  nparts = ceil(N / 256);
+ *   T = ceil(N / 64), per = max(2, ceil(T / ceil(1024 / T))), slabs = ceil(T / per).
+ * Launches (five, RBF six): column sums over slabs of mrows rows in row order; means (the slabs in order, / N); one thread per row
+ * adds (x - mean)^2 by fma in column order and its workgroup's sum goes to a partial; (RBF) one workgroup adds the partials and
+ * writes inv2s2; workgroup (ti, slab) of 256 threads visits the 64 x 64 tiles tj = slab per .. in order, stages the centred rows of
+ * both tiles 32 columns at a time (zeros past D and past N) and runs v_mfma_f64_16x16x4_f64 into one accumulator set for X and a
+ * second for Y, then finishes the 16 pairs of a lane (i == j, i >= N, j >= N skipped): K L, K K, L L by fma, the row sums over the
+ * 16 lanes of a row by xor shuffles 8, 4, 2, 1, rows accumulated over tj in order; one finishing workgroup (thread u owns the rows
+ * u, u + 256, ...) adds the slabs of a row in slab order and forms everything else.
+ *   Additions at most on a term's way
+ *     to a mean:                          A_mean      = mrows + mslabs
+ *     to a norm n_i:                      A_norm(D)   = D
+ *     to the sum of the norms (sigma):    A_sigma     = 9 + ceil(nparts / 256) + 9
+ *     to a dot product xc_i . xc_j:       A_dot(D)    = 32 ceil(D / 32)
+ *     of a K_ij to a row sum rK_i:        A_row       = 2 + 4 + per + 1 + slabs + 1    (the last one adds the diagonal)
+ *     of a K_ij L_ij to KL (KK, LL):      A_scalar    = 16 per + 9 + ceil(T slabs / 256) + 9 + 1    (the last one: the diagonal's sum)
+ *     of a row's term to rKL .. sL and to the diagonal's sums:   A_finish = ceil(N / 256) + 9
+ *   ws: msn_hsic_workspace_bytes = 8 (mslabs (Dx + Dy) + (Dx + Dy) + 2 N + 2 nparts + 2 + 2 slabs N + 3 T slabs) bytes.
+ * MSN_ERR_SHAPE before any launch: Dx or Dy outside 1..1024, N < 2 or >= 2^31, a row stride below D, an unknown kernel, a negative
+ * or non-finite sigma, sigma_scale not finite and > 0, a null or misaligned pointer, a workspace that is too small (the query
+ * returns 0 for a refused shape). */
+size_t msn_hsic_workspace_bytes(int64_t N, int Dx, int Dy);
+int msn_hsic_sums(const float* X, int64_t ldx, int Dx, const float* Y, int64_t ldy, int Dy, int64_t N, int kernel, double sigma_x,
+                  double sigma_y, double sigma_scale, double* out, void* ws, size_t ws_bytes, msn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Threshold-free classification metrics (metrics.py; csrc/rank_metrics.hip): one-vs-rest AUROC, average precision, binned
  * ROC / precision-recall curves and top-k accuracy from integer counts.  Shared by the four entry points: S (N, C) fp32
  * scores with row stride ld >= C, 4-byte aligned (every load of S is a 4-byte load: the bits do not depend on stride or

@@ -180,6 +180,8 @@ SIGNATURES = {
                                c_size, c_ptr]),
     "msn_barlow_bwd": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64,
                                c_ptr, c_i64, c_ptr]),
+    "msn_hsic_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
+    "msn_hsic_sums": (c_int, [c_ptr, c_i64, c_int, c_ptr, c_i64, c_int, c_i64, c_int, c_f64, c_f64, c_f64, c_ptr, c_ptr, c_size, c_ptr]),
     "msn_rank_counts_workspace_bytes": (c_size, [c_i64, c_int]),
     "msn_rank_counts": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "msn_threshold_counts": (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr]),

@@ -14,19 +14,32 @@ al. 2022), effective rank / RankMe (Garrido et al. 2023), and recall@k, MRR and 
     cross_correlation the column means, the biased variances, the cross covariance and the cross correlation of two towers in
                       fp64 on the device (csrc/barlow.hip: msn_cross_cov, msn_barlow_fwd): what loss.barlow_twins_loss drives to
                       the identity.  D <= 256.  Enqueue only.  cross_correlation_reference is its longdouble restatement.
+    hsic_sums         the sixteen sums centred kernel alignment is made of, in fp64 on the device, for two sets whose widths may
+                      differ (csrc/cka.hip: msn_hsic_sums carries a Gram tile of X and one of Y at once and never writes an
+                      N x N matrix): linear or RBF kernel, with and without the diagonal.  D <= 1024.  Enqueue only.
+    hsic_from_sums, cka_from_sums
+                      host halves: biased HSIC (tr(KHLH) / (n - 1)^2) or the debiased estimator of Song et al. 2012 from the
+                      sums, and CKA = HSIC(K, L) / sqrt(HSIC(K, K) HSIC(L, L)) (Kornblith et al. 2019); no GPU needed
+    cka, cka_matrix   the figure of one call, and the layers-by-layers matrix of two lists of sets: one host copy each
+    CKA               reset / update(X, Y) / compute(): minibatch CKA (Nguyen et al. 2021), debiased by default
+    hsic_sums_reference, hsic_reference, cka_reference
+                      numpy longdouble restatements over explicit N x N matrices; hsic_reference and cka_reference take the
+                      matrix definitions and do not go through the sums
     uniformity, cross_uniformity, alignment
                       the figures of one call: one host copy each
     covariance_spectrum, effective_rank, participation_ratio, modality_gap
                       host halves over probes.probe_gram's matrix, numpy fp64: importable and testable without a GPU
     recall_at_k, mean_reciprocal_rank, median_rank, retrieval_metrics
                       over the integer ranks of utils.retrieval_ranks
-    EmbeddingMetrics  reset / update(e1, e2) / compute() over a validation epoch
+    EmbeddingMetrics  reset / update(e1, e2) / compute() over a validation epoch; cka=True adds linear CKA, biased and debiased
     pair_potential_reference, pair_alignment_reference, pair_field_reference
                       numpy longdouble restatements of the kernels, importable without a GPU
 
 No scipy or scikit-learn at run time.  Nothing here issues a collective: with several ranks, gather the embeddings before the
-call, as for a kNN probe.  Not built: CKA, collectives, sample weights, D > 1024; of the alignment + uniformity loss
-(loss.align_uniform_loss): D > 256, global negatives across ranks, alpha other than 1 and 2.
+call, as for a kNN probe.  Not built: collectives, sample weights, D > 1024; of the alignment + uniformity loss
+(loss.align_uniform_loss): D > 256, global negatives across ranks, alpha other than 1 and 2; of CKA: a median-heuristic
+bandwidth (the derived one is the mean squared distance), kernels other than linear and RBF, CKA as a training loss, and sharing
+HSIC(K, K) across the cells of cka_matrix.
 """
 import numpy as np
 import torch
@@ -397,6 +410,237 @@ def cross_correlation(X, Y, eps=1e-5):
     return mx, my, vx, vy, cov, corr
 
 
+# ------------------------------------------------------------------------------------------ centred kernel alignment
+HSIC_KERNELS = {"linear": 0, "rbf": 1}
+HSIC_SUMS = ("KL", "KK", "LL", "rKL", "rKK", "rLL", "sK", "sL")          # the columns of hsic_sums; row 0 without, row 1 with i == j
+_HSIC_PAIRS = {"KL": (0, 3, 6, 7), "KK": (1, 4, 6, 6), "LL": (2, 5, 7, 7)}  # the product sum, the row-sum product, the two totals
+
+
+def _hsic_kernel(kernel, who):
+    if kernel not in HSIC_KERNELS:
+        raise ValueError(f"{who}: kernel must be 'linear' or 'rbf' (got {kernel!r})")
+    return HSIC_KERNELS[kernel]
+
+
+def _sigma_pair(sigma, sigma_scale, who):
+    """(sigma_x, sigma_y, sigma_scale) as floats, None for a bandwidth to derive."""
+    pair = tuple(sigma) if isinstance(sigma, (tuple, list)) else (sigma, sigma)
+    if len(pair) != 2:
+        raise ValueError(f"{who}: sigma must be None, a float or a pair (got {sigma!r})")
+    pair = tuple(None if v is None else float(v) for v in pair)
+    for v in pair:
+        if v is not None and not (v > 0 and np.isfinite(v)):
+            raise ValueError(f"{who}: an explicit sigma must be finite and positive (got {v}); None derives it")
+    scale = float(sigma_scale)
+    if not (scale > 0 and np.isfinite(scale)):
+        raise ValueError(f"{who}: sigma_scale must be finite and positive (got {sigma_scale})")
+    return pair[0], pair[1], scale
+
+
+def _kernel_matrix(Z, kernel, sigma, scale):
+    """The n x n longdouble kernel matrix of the fp32 rows Z after centring, with its diagonal (|zc_i|^2, or exactly 1)."""
+    Z = np.asarray(Z, dtype=np.float32).astype(np.longdouble)
+    n = Z.shape[0]
+    Zc = Z - Z.sum(axis=0) / np.longdouble(n)
+    if kernel == "linear":
+        return Zc @ Zc.T
+    d2 = np.stack([((Zc - z) ** 2).sum(axis=1) for z in Zc])           # the direct form: nothing cancels
+    np.fill_diagonal(d2, 0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        s2 = np.longdouble(sigma) ** 2 if sigma is not None else np.longdouble(scale) ** 2 * (d2.sum() / (np.longdouble(n) * (n - 1)))
+        K = np.exp(-d2 / (2 * s2))                                     # equal rows, derived bandwidth: 0 / 0
+    np.fill_diagonal(K, np.nan if np.isnan(K).any() else 1)          # a set without a bandwidth has no diagonal either
+    return K
+
+
+def _reference_matrices(X, Y, kernel, sigma, sigma_scale, who):
+    _hsic_kernel(kernel, who)
+    sx, sy, scale = _sigma_pair(sigma, sigma_scale, who)
+    X, Y = np.asarray(X, dtype=np.float32), np.asarray(Y, dtype=np.float32)
+    if X.ndim != 2 or Y.ndim != 2 or X.shape[0] != Y.shape[0] or X.shape[0] < 2 or X.shape[1] < 1 or Y.shape[1] < 1:
+        raise ValueError(f"{who}: X (N, Dx) and Y (N, Dy) with N >= 2 needed (got {X.shape} and {Y.shape})")
+    return _kernel_matrix(X, kernel, sx, scale), _kernel_matrix(Y, kernel, sy, scale)
+
+
+def hsic_sums_reference(X, Y, kernel="linear", sigma=None, sigma_scale=1.0):
+    """numpy longdouble restatement of hsic_sums over the explicit N x N matrices: a (2, 8) longdouble array, HSIC_SUMS by column,
+    row 0 without and row 1 with the pairs i == j.  The RBF distances are the direct form sum_c (x_ic - x_jc)^2 and a derived
+    bandwidth is sigma_scale^2 times their mean over i != j.  No GPU needed."""
+    K, L = _reference_matrices(X, Y, kernel, sigma, sigma_scale, "hsic_sums_reference")
+    K0, L0 = K.copy(), L.copy()
+    np.fill_diagonal(K0, 0)
+    np.fill_diagonal(L0, 0)
+    out = np.empty((2, 8), dtype=np.longdouble)
+    for c, (A, B) in enumerate(((K0, L0), (K, L))):
+        rA, rB = A.sum(axis=1), B.sum(axis=1)
+        out[c] = [(A * B).sum(), (A * A).sum(), (B * B).sum(), rA @ rB, rA @ rA, rB @ rB, rA.sum(), rB.sum()]
+    return out
+
+
+def _sums_array(sums, who):
+    s = np.asarray(sums)
+    if s.shape != (2, 8):
+        raise ValueError(f"{who}: sums must be the (2, 8) block of hsic_sums (got {s.shape})")
+    return s if s.dtype == np.longdouble else s.astype(np.float64)
+
+
+def hsic_from_sums(sums, n, pair="KL", debiased=False):
+    """HSIC of a pair of kernels ("KL", "KK" or "LL") from the (2, 8) block of hsic_sums over n rows:
+        biased    (P1 - (2 / n) R1 + S1 S1' / n^2) / (n - 1)^2                                   = tr(KHLH) / (n - 1)^2
+        debiased  (P0 + S0 S0' / ((n - 1)(n - 2)) - (2 / (n - 2)) R0) / (n (n - 3)), n >= 4       (Song et al. 2012)
+    with P the sum of products, R the sum of row-sum products and S, S' the totals, the index the diagonal convention.  In fp64;
+    a longdouble block is kept in longdouble, every rational factor formed there.  nan for a debiased n < 4."""
+    if pair not in _HSIC_PAIRS:
+        raise ValueError(f"hsic_from_sums: pair must be 'KL', 'KK' or 'LL' (got {pair!r})")
+    s = _sums_array(sums, "hsic_from_sums")
+    n = int(n)
+    if n < 2:
+        raise ValueError(f"hsic_from_sums: n must be at least 2 (got {n})")
+    f = s.dtype.type
+    ip, ir, ia, ib = _HSIC_PAIRS[pair]
+    if debiased:
+        if n < 4:
+            return f("nan")
+        P, R, A, B = s[0, ip], s[0, ir], s[0, ia], s[0, ib]
+        return (P + A * B / (f(n - 1) * f(n - 2)) - f(2) / f(n - 2) * R) / (f(n) * f(n - 3))
+    P, R, A, B = s[1, ip], s[1, ir], s[1, ia], s[1, ib]
+    return (P - f(2) / f(n) * R + A * B / (f(n) * f(n))) / (f(n - 1) * f(n - 1))
+
+
+def _cka_of(hkl, hkk, hll):
+    """HSIC(K, L) / sqrt(HSIC(K, K) HSIC(L, L)) as a float; nan when a term of the denominator is not finite and positive."""
+    if not (np.isfinite(hkk) and np.isfinite(hll) and hkk > 0 and hll > 0):
+        return float("nan")
+    return float(hkl / np.sqrt(hkk * hll))
+
+
+def cka_from_sums(sums, n, debiased=False):
+    """CKA = HSIC(K, L) / sqrt(HSIC(K, K) HSIC(L, L)) from the (2, 8) block of hsic_sums over n rows.  nan when a term of the
+    denominator is <= 0 or not finite, and for a debiased n < 4; the debiased figure may be negative."""
+    return _cka_of(*(hsic_from_sums(sums, n, pair, debiased) for pair in ("KL", "KK", "LL")))
+
+
+def _matrix_hsic(K, L, debiased):
+    n = K.shape[0]
+    f = np.longdouble
+    if not debiased:
+        H = np.eye(n, dtype=f) - np.ones((n, n), dtype=f) / f(n)
+        return np.trace(K @ H @ L @ H) / (f(n - 1) * f(n - 1))
+    if n < 4:
+        return f("nan")
+    Kt, Lt = K.copy(), L.copy()
+    np.fill_diagonal(Kt, 0)
+    np.fill_diagonal(Lt, 0)
+    one = np.ones(n, dtype=f)
+    return (np.trace(Kt @ Lt) + (one @ Kt @ one) * (one @ Lt @ one) / (f(n - 1) * f(n - 2))
+            - f(2) / f(n - 2) * (one @ Kt @ (Lt @ one))) / (f(n) * f(n - 3))
+
+
+def hsic_reference(X, Y, kernel="linear", debiased=False, sigma=None, sigma_scale=1.0):
+    """(HSIC(K, L), HSIC(K, K), HSIC(L, L)) in longdouble from the matrix definitions: tr(KHLH) / (n - 1)^2, or Song et al.'s
+    tr(K~ L~) + 1'K~1 1'L~1 / ((n - 1)(n - 2)) - (2 / (n - 2)) 1'K~L~1 over n (n - 3) with the diagonals removed.  No GPU needed."""
+    K, L = _reference_matrices(X, Y, kernel, sigma, sigma_scale, "hsic_reference")
+    return _matrix_hsic(K, L, debiased), _matrix_hsic(K, K, debiased), _matrix_hsic(L, L, debiased)
+
+
+def cka_reference(X, Y, kernel="linear", debiased=False, sigma=None, sigma_scale=1.0):
+    """numpy longdouble CKA from the matrix definitions (hsic_reference), not through the sums: an independent route."""
+    return _cka_of(*hsic_reference(X, Y, kernel, debiased, sigma, sigma_scale))
+
+
+def hsic_sums(X, Y, kernel="linear", sigma=None, sigma_scale=1.0, out=None):
+    """out (2, 8) fp64 on the device: HSIC_SUMS of the centred kernels K over X (N, Dx) and L over Y (N, Dy), rows are partners,
+    row 0 over i != j and row 1 with the diagonal (msn_hsic_sums).  kernel "linear" (x_i . x_j of the centred rows) or "rbf"
+    (exp(-|x_i - x_j|^2 / (2 sigma^2))); sigma a float or a pair (sigma_x, sigma_y), None for sigma^2 = sigma_scale^2 times the mean
+    squared distance over i != j, formed on the device and never read here.  N >= 2, Dx, Dy <= 1024.  Enqueue only."""
+    who = "hsic_sums"
+    kid = _hsic_kernel(kernel, who)
+    sx, sy, scale = _sigma_pair(sigma, sigma_scale, who)
+    X = rows_on_gpu(X, who, "embeddings")
+    Y = rows_on_gpu(Y, who, "embeddings")
+    if Y.device != X.device:
+        raise _lib.MsnHipError(f"{who}: X and Y must live on the same GPU")
+    if X.shape[0] != Y.shape[0]:
+        raise ValueError(f"{who}: X and Y must hold the same number of rows (got {X.shape[0]} and {Y.shape[0]})")
+    (N, Dx), Dy = X.shape, Y.shape[1]
+    if N < 2:
+        raise _lib.MsnHipError(f"{who}: N must be at least 2 (got {N})")
+    if not (1 <= Dx <= MAX_D and 1 <= Dy <= MAX_D):
+        raise _lib.MsnHipError(f"{who}: Dx and Dy must be in 1..{MAX_D} (got {Dx} and {Dy}); wider embeddings are not built")
+    if out is None:
+        out = torch.empty((2, 8), dtype=torch.float64, device=X.device)
+    elif out.shape != (2, 8) or out.dtype != torch.float64 or out.device != X.device or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous float64 (2, 8) tensor on {X.device}")
+    L = lib()
+    ws = workspace(L.msn_hsic_workspace_bytes(N, Dx, Dy), X.device)
+    check(L.msn_hsic_sums(ptr(X), ld(X), Dx, ptr(Y), ld(Y), Dy, N, kid, sx or 0.0, sy or 0.0, scale, ptr(out), ptr(ws), ws.numel(),
+                          stream_ptr()), "msn_hsic_sums")
+    return out
+
+
+def cka(X, Y, kernel="linear", debiased=False, sigma=None, sigma_scale=1.0):
+    """Centred kernel alignment of two sets of partner rows as a float: hsic_sums, one host copy, cka_from_sums."""
+    sums = hsic_sums(X, Y, kernel, sigma, sigma_scale)
+    return cka_from_sums(sums.cpu().numpy(), X.shape[0], debiased)
+
+
+def cka_matrix(feats_a, feats_b, kernel="linear", debiased=False, sigma=None, sigma_scale=1.0):
+    """The (len(feats_a), len(feats_b)) numpy array of cka(a, b): the layers-by-layers picture of two lists of (N, D) sets over
+    the same N rows (the widths are free).  A host loop over hsic_sums into one buffer, one host copy at the end; HSIC(K, K) is
+    formed again in every cell."""
+    feats_a, feats_b = list(feats_a), list(feats_b)
+    if not feats_a or not feats_b:
+        raise ValueError("cka_matrix: two non-empty lists of (N, D) sets needed")
+    N = feats_a[0].shape[0]
+    buf = None
+    for i, a in enumerate(feats_a):
+        for j, b in enumerate(feats_b):
+            if a.shape[0] != N or b.shape[0] != N:
+                raise ValueError(f"cka_matrix: every set must hold the same {N} rows (got {a.shape[0]} and {b.shape[0]})")
+            if buf is None:
+                _lib.require_gpu()
+                buf = torch.empty((len(feats_a), len(feats_b), 2, 8), dtype=torch.float64, device=getattr(a, "device", None))
+            hsic_sums(a, b, kernel, sigma, sigma_scale, out=buf[i, j])
+    h = buf.cpu().numpy()
+    return np.array([[cka_from_sums(h[i, j], N, debiased) for j in range(len(feats_b))] for i in range(len(feats_a))])
+
+
+class CKA:
+    """Minibatch CKA (Nguyen et al. 2021) over an epoch: update(X, Y) enqueues hsic_sums of a batch and keeps its (2, 8) block and
+    its size; compute() makes one host copy and returns
+
+        sum_b HSIC(K_b, L_b) / sqrt(sum_b HSIC(K_b, K_b) sum_b HSIC(L_b, L_b)),
+
+    debiased by default (the biased estimator depends on the batch size).  The widths of X and Y may differ from each other, not
+    between batches.  nan by cka_from_sums' rules, and for a debiased batch of fewer than 4 rows."""
+
+    def __init__(self, kernel="linear", debiased=True, sigma=None, sigma_scale=1.0):
+        _hsic_kernel(kernel, "CKA")
+        _sigma_pair(sigma, sigma_scale, "CKA")
+        self.kernel, self.debiased, self.sigma, self.sigma_scale = kernel, bool(debiased), sigma, sigma_scale
+        self.reset()
+
+    def reset(self):
+        self._sums, self._n, self._widths = [], [], None
+
+    def update(self, X, Y):
+        sums = hsic_sums(X, Y, self.kernel, self.sigma, self.sigma_scale)
+        widths = (X.shape[1], Y.shape[1])
+        if self._widths is not None and widths != self._widths:
+            raise ValueError(f"CKA.update: the widths changed from {self._widths} to {widths}")
+        self._widths = widths
+        self._sums.append(sums)
+        self._n.append(X.shape[0])
+        return self
+
+    def compute(self):
+        if not self._sums:
+            raise ValueError("CKA.compute: nothing added yet")
+        h = torch.stack(self._sums).cpu().numpy()
+        return _cka_of(*(sum(hsic_from_sums(h[b], n, pair, self.debiased) for b, n in enumerate(self._n))
+                         for pair in ("KL", "KK", "LL")))
+
+
 def _unit_rows(X, who):
     """L2-normalised rows (ops.l2norm_fwd, which takes D a multiple of 4: the rule of the kNN probes' cosine metric)."""
     from . import ops
@@ -445,16 +689,17 @@ class EmbeddingMetrics:
     pair kernels and the retrieval ranks, makes one host copy and returns
 
         n, alignment, uniformity_a, uniformity_b, uniformity (their mean), uniformity_cross (partners left out),
-        modality_gap, erank_a, erank_b, erank (the smaller), and retrieval_metrics' keys.
+        modality_gap, erank_a, erank_b, erank (the smaller), and retrieval_metrics' keys;
+        with cka=True also cka (linear, biased) and cka_debiased of the two sets (hsic_sums, in the same host copy).
 
     normalize: L2-normalise the rows first (D a multiple of 4).  center: take the spectra of the centred sets; center=False
     is RankMe.  No collective is issued: with several ranks the caller gathers the embeddings first, as for a kNN probe."""
 
-    def __init__(self, t=2.0, top_k=(1, 5, 10), normalize=True, center=True):
+    def __init__(self, t=2.0, top_k=(1, 5, 10), normalize=True, center=True, cka=False):
         if not (t > 0 and np.isfinite(t)):
             raise ValueError(f"EmbeddingMetrics: t must be finite and positive (got {t})")
         self.t, self.top_k = float(t), _top_k(top_k)
-        self.normalize, self.center = bool(normalize), bool(center)
+        self.normalize, self.center, self.cka = bool(normalize), bool(center), bool(cka)
         self.reset()
 
     def reset(self):
@@ -487,7 +732,7 @@ class EmbeddingMetrics:
         N, D = A.shape
         M = (D + 1) * (D + 1)
         # one buffer, one copy: four pair results, the two Gram matrices, the two rank vectors (exact as doubles)
-        buf = torch.empty(8 + 2 * M + 2 * N, dtype=torch.float64, device=A.device)
+        buf = torch.empty(8 + 2 * M + 2 * N + (16 if self.cka else 0), dtype=torch.float64, device=A.device)
         pair_alignment(A, B, out=buf[0:2])
         if N >= 2:
             pair_potential(A, None, self.t, "within", out=buf[2:4])
@@ -498,10 +743,15 @@ class EmbeddingMetrics:
         buf[8:8 + M].copy_(self.gram_a.reshape(-1))
         buf[8 + M:8 + 2 * M].copy_(self.gram_b.reshape(-1))
         buf[8 + 2 * M:8 + 2 * M + N].copy_(retrieval_ranks(B, A))          # a -> b
-        buf[8 + 2 * M + N:].copy_(retrieval_ranks(A, B))                   # b -> a
+        buf[8 + 2 * M + N:8 + 2 * M + 2 * N].copy_(retrieval_ranks(A, B))  # b -> a
+        if self.cka:
+            if N >= 2:
+                hsic_sums(A, B, out=buf[8 + 2 * M + 2 * N:].view(2, 8))
+            else:
+                buf[8 + 2 * M + 2 * N:].fill_(float("nan"))
         h = buf.cpu().numpy()
         Ga, Gb = h[8:8 + M].reshape(D + 1, D + 1), h[8 + M:8 + 2 * M].reshape(D + 1, D + 1)
-        r_a2b, r_b2a = h[8 + 2 * M:8 + 2 * M + N].astype(np.int64), h[8 + 2 * M + N:].astype(np.int64)
+        r_a2b, r_b2a = h[8 + 2 * M:8 + 2 * M + N].astype(np.int64), h[8 + 2 * M + N:8 + 2 * M + 2 * N].astype(np.int64)
         within, cross = N * (N - 1) / 2, N * (N - 1)
         out = {"n": N, "alignment": float(h[0]) / N}
         if N >= 2:
@@ -515,4 +765,8 @@ class EmbeddingMetrics:
         out["erank_b"] = effective_rank(covariance_spectrum(Gb, D, self.center))
         out["erank"] = min(out["erank_a"], out["erank_b"])
         out.update(_retrieval_from_ranks(r_a2b, r_b2a, self.top_k))
+        if self.cka:
+            sums = h[8 + 2 * M + 2 * N:].reshape(2, 8)
+            out["cka"] = cka_from_sums(sums, N, False) if N >= 2 else float("nan")
+            out["cka_debiased"] = cka_from_sums(sums, N, True) if N >= 2 else float("nan")
         return out
