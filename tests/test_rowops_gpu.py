@@ -56,6 +56,9 @@ def test_l2norm_fwd_bwd(rows, cols):
 @pytest.mark.parametrize("B,T,e,nband", [(3, 12, 16, 1), (3, 12, 16, 2), (5, 200, 64, 2), (2, 1024, 32, 1),
                                         (4, 30, 384, 3), (2, 10, 6, 1)])
 def test_time_embed_fwd_bwd(B, T, e, nband):
+    """against the oracle's formula evaluated in fp64 and, element by element, against the fp64 reference and derived bounds of
+    tests/rownorm_refs.py (the sine of an angle of 9000 rad is off by u |t omega| = 5e-4 from the rounding of the angle alone)"""
+    import rownorm_refs as R
     from multimodal_supernovae_amd import ops
     from oracle.encoders import time_positional_encoding
     g = _g(B + T + e)
@@ -65,22 +68,28 @@ def test_time_embed_fwd_bwd(B, T, e, nband):
     band = torch.randn(nband, e, generator=g) if nband > 1 else None
     norm = 17945.14
     omega = torch.exp(torch.arange(0, e, 2).float() * (-math.log(norm) / e))
-    wr, bwr = w.clone().requires_grad_(), bw.clone().requires_grad_()
-    ref = x[:, :, None] * wr + bwr + time_positional_encoding(t, e, norm)
+    wr, bwr = w.double().requires_grad_(), bw.double().requires_grad_()
+    ref = x.double()[:, :, None] * wr + bwr + time_positional_encoding(t.double(), e, norm)
     if nband > 1:
-        bandr = band.clone().requires_grad_()
+        bandr = band.double().requires_grad_()
         ref = ref + bandr[torch.arange(nband).repeat_interleave(T // nband)][None]
+    pinned = R.te_forward_ref(x, t, w, bw, omega, band)
+    torch.testing.assert_close(pinned["out"], ref.detach(), rtol=0, atol=1e-12)
     out = ops.time_embed_fwd(x.cuda(), t.cuda(), w.cuda(), bw.cuda(), omega.cuda(),
                              band.cuda() if band is not None else None)
-    # sin/cos of arguments up to 9000 rad: fp32 argument rounding (1 ulp of t*omega ~ 5e-4) bounds parity
-    torch.testing.assert_close(out.cpu(), ref.detach(), rtol=1e-4, atol=2e-3 if nband == 1 else 5e-5)
+    bad, ratios = R.failures({"out": out}, pinned)
+    assert not bad, (bad, ratios)
+    torch.testing.assert_close(out.cpu().double(), ref.detach(), rtol=1e-4, atol=2e-3 if nband == 1 else 5e-5)
     dy = torch.randn(B, T, e, generator=g)
-    ref.backward(dy)
+    ref.backward(dy.double())
     dw, dbw, dband = ops.time_embed_bwd(dy.cuda(), x.cuda(), nband)
-    torch.testing.assert_close(dw.cpu(), wr.grad, rtol=1e-4, atol=1e-3)
-    torch.testing.assert_close(dbw.cpu(), bwr.grad, rtol=1e-4, atol=1e-3)
+    got = dict(dw=dw, dbw=dbw, **({"dband": dband} if nband > 1 else {}))
+    bad, ratios = R.failures(got, R.te_backward_ref(dy, x, nband))
+    assert not bad, (bad, ratios)
+    torch.testing.assert_close(dw.cpu().double(), wr.grad, rtol=1e-4, atol=1e-3)
+    torch.testing.assert_close(dbw.cpu().double(), bwr.grad, rtol=1e-4, atol=1e-3)
     if nband > 1:
-        torch.testing.assert_close(dband.cpu(), bandr.grad, rtol=1e-4, atol=1e-3)
+        torch.testing.assert_close(dband.cpu().double(), bandr.grad, rtol=1e-4, atol=1e-3)
 
 
 @pytest.mark.parametrize("mode", ["mean", "max"])
